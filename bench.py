@@ -8,10 +8,15 @@ against the kept HMMs (wh_align_dev), result gather to the host.  With N > 1 ran
 queries are sharded contiguously (the eHMM is replicated), and the only collective is
 the all-gather of the per-query top-k records over RCCL.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline
+(value, ms_per_step, stage times of the timed steps, config).  --full adds everything else the line used to
+carry: the consensus and merge stages, the rooflines, the distributions, the level-1 end-to-end stage, the
+`also` workloads and the CPU baseline (each can still be left out with its --no-* option).
+--dump-outputs DIR writes what the last timed step returned (top-k table, column offsets, a seeded sample of
+the aligned columns) as DIR/<name>.npy in float32 / float64, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -189,6 +194,35 @@ def level1_stage(fam, synth_ehmm, names, seqs, k, alphabet, workdir, nq=20000, d
                          **{"engine_" + kk: round(v, 3) for kk, v in eng.timings.items()}},
             "rows_written": rows,
             "note": "text queries in -> two merged FASTA files out through witch_amd.gcmm (level 1), warm process, fresh model handle; outside the timed region"}
+
+
+DUMP_LIMIT_BYTES = 60_000_000      # below 64 MB however counted, .npy headers included
+DUMP_COL_PAIRS = 16384          # aligned pairs whose columns are written (a fixed, seeded sample when there are more)
+
+
+def dump_outputs(outdir, out):
+    """What the caller of the hot path receives from hot_path_step (the last timed step): the top-k table in full,
+    the per-pair column offsets in full, and the aligned columns of a seeded sample of at most DUMP_COL_PAIRS pairs
+    (all of them for a small run), with the indices of the sampled pairs.  Integers are written as float64 (exact)
+    or, for the columns (one small int32 per query residue), float32 (exact below 2^24).  At most DUMP_LIMIT_BYTES in all."""
+    idx, w, nk, nu, cols, co = (t.numpy() for t in out)
+    arrays = {"topk_index": idx.astype(np.float64), "topk_weight": w.astype(np.float64),
+              "topk_n_kept": nk.astype(np.float64), "topk_n_used": nu.astype(np.float64),
+              "align_col_offsets": co.astype(np.float64)}
+    # seeded sample of pairs, cut where their columns would pass the byte limit (long queries), written in pair order
+    npairs = len(co) - 1
+    pick = np.random.default_rng(20251205).permutation(npairs)[:DUMP_COL_PAIRS]
+    room = (DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values()) - 8 * len(pick)) // 4
+    pick = np.sort(pick[np.cumsum(co[pick + 1] - co[pick]) <= room])
+    arrays["align_cols_sample_pairs"] = pick.astype(np.float64)
+    arrays["align_cols_sample"] = (np.concatenate([cols[co[p]:co[p + 1]] for p in pick]) if len(pick)
+                                   else np.zeros(0, dtype=np.int32)).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def crc_of(*arrays):
@@ -395,9 +429,13 @@ def main():
     ap.add_argument("--workload", default="dna_100k_x200", choices=sorted(WORKLOADS))
     ap.add_argument("--nq", type=int, default=0, help="override the query count (development only)")
     ap.add_argument("--nh", type=int, default=0, help="override the HMM count (development only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-level1", action="store_true", help="skip the level-1 end-to-end stage (reported beside the hot-path value)")
-    ap.add_argument("--no-also", action="store_true", help="skip the workloads reported beside the headline (dna_100k_x200_m1000 in full, a 3 000-query slice of aa_50k_x500, the reference's example data x 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is reported beside the headline: consensus and merge stages, rooflines, distributions, "
+                         "level-1 end-to-end stage, the 'also' workloads and the CPU baseline (a plain run times the hot path only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-level1", action="store_true", help="with --full: skip the level-1 end-to-end stage (reported beside the hot-path value)")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the workloads reported beside the headline (dna_100k_x200_m1000 in full, a 3 000-query slice of aa_50k_x500, the reference's example data x 4)")
     args = ap.parse_args()
     if os.environ.get("WITCH_BENCH_WATCHDOG"):      # tests: a run that stops says where (every thread's stack on stderr), then goes on
         import faulthandler
@@ -466,7 +504,7 @@ def main():
         npairs = ncols = 0
         class_ms = {}                            # (cells per lane, kernel family) -> [ms, launches] of the scoring launches
         for st in range(args.steps):
-            out, npairs, ncols = hot_path_step(e, res_t, off_t, maxlen, k, gather, keep_device=(st == args.steps - 1))
+            out, npairs, ncols = hot_path_step(e, res_t, off_t, maxlen, k, gather, keep_device=(args.full and st == args.steps - 1))
             for which in (0, 1, 2, 4):
                 ms, n = e.last_kernel_ms(which)
                 kern_ms[which] += ms
@@ -481,14 +519,17 @@ def main():
             tmax = torch.tensor([dt], device="cpu" if rehearsal else "cuda", dtype=torch.float64)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
-        # ---- outside the timed region: the next stage (weighted consensus) and the value distributions
-        cons_ms = consensus_stage(e, synth_ehmm, fam, off_t, maxlen, k) if hi > lo else 0.0
-        merge_info = None
-        try:
-            if hi > lo and rank == 0:
-                merge_info = merge_stage(fam, seqs[lo:hi], off_t, hot_path_step.dev["nu"], WORKLOADS[args.workload][0])
-        except Exception as ex:           # an extra stage must never take the bench line down
-            merge_info = ("failed: %s" % ex, 0, 0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, out)
+        # ---- outside the timed region (--full only): the next stage (weighted consensus) and the value distributions
+        cons_ms, merge_info = 0.0, None
+        if args.full:
+            cons_ms = consensus_stage(e, synth_ehmm, fam, off_t, maxlen, k) if hi > lo else 0.0
+            try:
+                if hi > lo and rank == 0:
+                    merge_info = merge_stage(fam, seqs[lo:hi], off_t, hot_path_step.dev["nu"], WORKLOADS[args.workload][0])
+            except Exception as ex:           # an extra stage must never take the bench line down
+                merge_info = ("failed: %s" % ex, 0, 0)
         e.set_timing(False)
 
         if rank == 0:
@@ -498,50 +539,6 @@ def main():
             L = float(np.mean(lens_local)) if hi > lo else 0.0
             qps = nq_total * args.steps / dt
             n_local = hi - lo
-            # ---- rooflines per SURVEY.md section 8(d) (score_roofline above)
-            cells_step = float(lens_local.sum() * M.sum())              # every local query x every model
-            stamp, stamp_src = profile_stamp(args.workload, not args.nq and not args.nh and world == 1)
-            roofline = score_roofline(M, lens_local, class_ms, kern_ms[0], kern_n[0], args.steps, H, stamp, stamp_src)
-            traffic_align = stamp.get("align_kernel_hbm_bytes_per_launch") if stamp else None
-            traffic_src = stamp_src
-            # Alignment.  Algorithmic bytes by sweep path (wh_last_align_paths): a pair aligned at full width moves
-            # 52 B per L x M cell (Forward rows written + read 24, posteriors 16, OA rows 12);
-            # a pair aligned on a node window moves 44 B per L x W cell, W = 256 or 512 nodes (its Forward cells
-            # written 8 and read 8, posteriors 16, OA rows 12) - the cells outside the window are computed by the
-            # Forward sweep but need not be stored.  Path shares are applied to the pass's totals (sum of L, sum of
-            # L x M over the aligned pairs).  The stage time spans the pass's launches (one per model size class,
-            # plus the log-space redo pass when pairs leave float32 range).
-            align_ms = kern_ms[2] / args.steps
-            ap = hot_path_step.align_paths
-            n_ap = max(1, sum(ap.values()))
-            f256, f512 = ap["window256"] / n_ap, ap["window512"] / n_ap
-            a_bytes = (hot_path_step.aligned_residues * 44.0 * (256 * f256 + 512 * f512)
-                       + hot_path_step.aligned_cells * 52.0 * (1.0 - f256 - f512)) if sum(ap.values()) else hot_path_step.aligned_cells * 52.0
-            a_gbs = a_bytes / (align_ms * 1e-3) / 1e9 if align_ms > 0 else 0.0
-            # SURVEY 8(d) prices alignment at 52 B per L x M cell whatever the kernel stores; with the node window the kernel
-            # moves 3-4 x fewer bytes than that, so the survey's figure no longer describes it (it would read > 1 of the HBM
-            # peak) - printed beside the window-based figure that the roofline uses, not instead of it
-            s8d_bytes = hot_path_step.aligned_cells * 52.0
-            s8d_gbs = s8d_bytes / (align_ms * 1e-3) / 1e9 if align_ms > 0 else 0.0
-            roofline_align = {"bound": "hbm", "kernel": "wh::generic_align_kernel" if int(np.max(e.M)) > 3072 else "wh::align_kernel", "achieved": round(a_gbs, 1), "peak": 8000.0,
-                              "unit": "GB/s", "frac": round(a_gbs / 8000.0, 4), "algorithmic_bytes_per_step": a_bytes,
-                              "survey_8d": {"bytes_per_step": s8d_bytes, "bytes_per_cell": 52, "equivalent_GBps": round(s8d_gbs, 1), "frac_of_peak": round(s8d_gbs / 8000.0, 4),
-                                            "note": "52 B x L x M per aligned pair as SURVEY.md 8(d) prices it; the kernel does not move these bytes (node window), so this is a rate of algorithmic work, not of HBM traffic"},
-                              "bytes_per_cell": {"full_width": 52, "window": 44}, "pairs_by_path": ap,
-                              "cells_per_step": hot_path_step.aligned_cells, "stage_ms": round(align_ms, 3),
-                              "launches_per_step": kern_n[2] / args.steps, "traffic": traffic_align, "traffic_source": traffic_src}
-            t_s, t_a = kern_ms[0] / args.steps, align_ms
-            combined = (t_s * roofline["frac"] + t_a * roofline_align["frac"]) / (t_s + t_a) if t_s + t_a > 0 else 0.0
-            # ---- the three distributions SURVEY.md 8(d) asks for with every run
-            nu_h = np.bincount(out[3].numpy(), minlength=k + 1).tolist()
-            dist3 = {"n_used": {str(i): int(c) for i, c in enumerate(nu_h) if c},
-                     "multidomain_frac": round(hot_path_step.multidomain / max(1, n_local * H), 8)}
-            ns = min(256, n_local)
-            if ns > 0:
-                _, _, det = e.score(res[:offs[ns]], offs[:ns + 1], want_detail=True)
-                nreg = np.array([d.nregions for d in det])
-                dist3["regions_per_pair"] = {str(i): int(c) for i, c in enumerate(np.bincount(nreg)) if c}
-                dist3["regions_per_pair_sample"] = "first %d queries x %d HMMs" % (ns, H)
             line = {
                 "metric": "query-seqs aligned/sec (100k queries x 200-HMM eHMM)",
                 "value": round(qps, 2), "unit": "queries/s", "n_gpus": world, "steps": args.steps,
@@ -560,21 +557,68 @@ def main():
                                       "align": round(kern_ms[2] / args.steps, 3),
                                       "score_parts": {"scoring_kernels": round(kern_ms[0] / args.steps, 3),
                                                       "multidomain_resolver": round(kern_ms[4] / args.steps, 3)}},
-                "extra_stage_ms": {"consensus_rank0": round(cons_ms, 3),
-                                   "merge_rank0_wall": (round(merge_info[0], 3) if merge_info and not isinstance(merge_info[0], str) else (merge_info[0] if merge_info else None)),
-                                   "merge_rows_x_width": ([merge_info[1], merge_info[2]] if merge_info else None),
-                                   "note": "weighted consensus DP (next row #1, HIP-event time) and final merge (next row #2, wh_merge wall time incl. upload of the codes and download of the two matrices) over this rank's queries, outside the timed region"},
-                "roofline": roofline, "roofline_align": roofline_align,
-                "roofline_time_weighted_frac": round(combined, 4),
-                "distributions": dist3,
             }
-            if not args.no_level1 and world == 1:
+            if args.full:
+                # ---- rooflines per SURVEY.md section 8(d) (score_roofline above)
+                cells_step = float(lens_local.sum() * M.sum())              # every local query x every model
+                stamp, stamp_src = profile_stamp(args.workload, not args.nq and not args.nh and world == 1)
+                roofline = score_roofline(M, lens_local, class_ms, kern_ms[0], kern_n[0], args.steps, H, stamp, stamp_src)
+                traffic_align = stamp.get("align_kernel_hbm_bytes_per_launch") if stamp else None
+                traffic_src = stamp_src
+                # Alignment.  Algorithmic bytes by sweep path (wh_last_align_paths): a pair aligned at full width moves
+                # 52 B per L x M cell (Forward rows written + read 24, posteriors 16, OA rows 12);
+                # a pair aligned on a node window moves 44 B per L x W cell, W = 256 or 512 nodes (its Forward cells
+                # written 8 and read 8, posteriors 16, OA rows 12) - the cells outside the window are computed by the
+                # Forward sweep but need not be stored.  Path shares are applied to the pass's totals (sum of L, sum of
+                # L x M over the aligned pairs).  The stage time spans the pass's launches (one per model size class,
+                # plus the log-space redo pass when pairs leave float32 range).
+                align_ms = kern_ms[2] / args.steps
+                ap = hot_path_step.align_paths
+                n_ap = max(1, sum(ap.values()))
+                f256, f512 = ap["window256"] / n_ap, ap["window512"] / n_ap
+                a_bytes = (hot_path_step.aligned_residues * 44.0 * (256 * f256 + 512 * f512)
+                           + hot_path_step.aligned_cells * 52.0 * (1.0 - f256 - f512)) if sum(ap.values()) else hot_path_step.aligned_cells * 52.0
+                a_gbs = a_bytes / (align_ms * 1e-3) / 1e9 if align_ms > 0 else 0.0
+                # SURVEY 8(d) prices alignment at 52 B per L x M cell whatever the kernel stores; with the node window the kernel
+                # moves 3-4 x fewer bytes than that, so the survey's figure no longer describes it (it would read > 1 of the HBM
+                # peak) - printed beside the window-based figure that the roofline uses, not instead of it
+                s8d_bytes = hot_path_step.aligned_cells * 52.0
+                s8d_gbs = s8d_bytes / (align_ms * 1e-3) / 1e9 if align_ms > 0 else 0.0
+                roofline_align = {"bound": "hbm", "kernel": "wh::generic_align_kernel" if int(np.max(e.M)) > 3072 else "wh::align_kernel", "achieved": round(a_gbs, 1), "peak": 8000.0,
+                                  "unit": "GB/s", "frac": round(a_gbs / 8000.0, 4), "algorithmic_bytes_per_step": a_bytes,
+                                  "survey_8d": {"bytes_per_step": s8d_bytes, "bytes_per_cell": 52, "equivalent_GBps": round(s8d_gbs, 1), "frac_of_peak": round(s8d_gbs / 8000.0, 4),
+                                                "note": "52 B x L x M per aligned pair as SURVEY.md 8(d) prices it; the kernel does not move these bytes (node window), so this is a rate of algorithmic work, not of HBM traffic"},
+                                  "bytes_per_cell": {"full_width": 52, "window": 44}, "pairs_by_path": ap,
+                                  "cells_per_step": hot_path_step.aligned_cells, "stage_ms": round(align_ms, 3),
+                                  "launches_per_step": kern_n[2] / args.steps, "traffic": traffic_align, "traffic_source": traffic_src}
+                t_s, t_a = kern_ms[0] / args.steps, align_ms
+                combined = (t_s * roofline["frac"] + t_a * roofline_align["frac"]) / (t_s + t_a) if t_s + t_a > 0 else 0.0
+                # ---- the three distributions SURVEY.md 8(d) asks for with every run
+                nu_h = np.bincount(out[3].numpy(), minlength=k + 1).tolist()
+                dist3 = {"n_used": {str(i): int(c) for i, c in enumerate(nu_h) if c},
+                         "multidomain_frac": round(hot_path_step.multidomain / max(1, n_local * H), 8)}
+                ns = min(256, n_local)
+                if ns > 0:
+                    _, _, det = e.score(res[:offs[ns]], offs[:ns + 1], want_detail=True)
+                    nreg = np.array([d.nregions for d in det])
+                    dist3["regions_per_pair"] = {str(i): int(c) for i, c in enumerate(np.bincount(nreg)) if c}
+                    dist3["regions_per_pair_sample"] = "first %d queries x %d HMMs" % (ns, H)
+                line.update({
+                    "extra_stage_ms": {"consensus_rank0": round(cons_ms, 3),
+                                       "merge_rank0_wall": (round(merge_info[0], 3) if merge_info and not isinstance(merge_info[0], str) else (merge_info[0] if merge_info else None)),
+                                       "merge_rows_x_width": ([merge_info[1], merge_info[2]] if merge_info else None),
+                                       "note": "weighted consensus DP (next row #1, HIP-event time) and final merge (next row #2, wh_merge wall time incl. upload of the codes and download of the two matrices) over this rank's queries, outside the timed region"},
+                    "roofline": roofline, "roofline_align": roofline_align,
+                    "roofline_time_weighted_frac": round(combined, 4),
+                    "distributions": dist3,
+                })
+            if args.full and not args.no_level1 and world == 1:
                 try:
                     line["level1_e2e"] = level1_stage(fam, synth_ehmm, names, seqs, k, WORKLOADS[args.workload][0], workdir, 20000, local_rank)
                     line["level1_e2e_queries_per_s"] = line["level1_e2e"]["queries_per_s"]
                 except Exception as ex:       # an extra stage must never take the bench line down
                     line["level1_e2e"] = {"failed": "%s: %s" % (type(ex).__name__, ex)}
-            if not args.no_also and world == 1 and args.workload == "dna_100k_x200" and not args.nq and not args.nh:
+            if args.full and not args.no_also and world == 1 and args.workload == "dna_100k_x200" and not args.nq and not args.nh:
                 line["also"] = []
                 for wl_, steps_, nq_, note_, golden_ in (
                         ("dna_100k_x200_m1000", 2, None, None, None),
@@ -587,7 +631,7 @@ def main():
                         line["also"].append(also_block(wl_, steps_, 1, local_rank, nq_, note_, golden_))
                     except Exception as ex:       # an extra workload must never take the bench line down
                         line["also"].append({"workload": wl_, "failed": "%s: %s" % (type(ex).__name__, ex)})
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 threads = min(os.cpu_count() or 1, 64)
                 # about 15 s of CPU work on 64 host threads: 384 queries of the headline (150 nt x 200 models of ~900
                 # nodes = 1.0e10 cells); other workloads get the same number of cells

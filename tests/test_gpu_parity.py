@@ -752,14 +752,14 @@ def test_randomised_small_cases(seed, orc, tmp_path):
 
 
 def test_bench_line_contract(tmp_path):
-    """bench.py prints ONE JSON line with the driver's keys, the roofline object and the CPU baseline."""
+    """bench.py --full prints ONE JSON line with the driver's keys, the roofline object and the CPU baseline."""
     _need_gpu()
     import json
     import os
     import subprocess
     import sys
     from tests.conftest import ROOT
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nq", "192", "--nh", "6", "--steps", "1", "--warmup", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nq", "192", "--nh", "6", "--steps", "1", "--warmup", "0", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -782,6 +782,44 @@ def test_bench_line_contract(tmp_path):
     assert j["extra_stage_ms"]["consensus_rank0"] > 0
     cb = j["cpu_baseline"]
     assert cb["kind"] in ("port", "reference") and cb["cores"] >= 1 and cb["value"] > 0 and cb["sample"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run times the hot path only: --steps timed steps, the headline keys and ms_per_step, none of
+    what --full adds.  --dump-outputs writes the last step's results as float32 / float64 .npy files within 64 MB,
+    and a second run with the same arguments writes the same arrays."""
+    _need_gpu()
+    import json
+    import os
+    import subprocess
+    import sys
+    from tests.conftest import ROOT
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("out%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nq", "192", "--nh", "6", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+            assert k in j, k
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "queries/s" and j["dtype"] == "f32"
+        assert j["ms_per_step"] > 0 and abs(j["value"] - 192 * 1e3 / j["ms_per_step"]) < 0.01 * j["value"]
+        for k in ("roofline", "roofline_align", "distributions", "extra_stage_ms", "level1_e2e", "also", "cpu_baseline"):
+            assert k not in j, k
+        files = sorted(os.listdir(d))
+        assert "topk_index.npy" in files and "align_cols_sample.npy" in files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64e6
+        arrays = {f[:-len(".npy")]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert arrays["topk_index"].shape == (192, j["config"]["k"])
+        assert int(arrays["topk_n_used"].sum()) == j["config"]["aligned_pairs_per_step"]
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 def test_ab_slot_kernel_agrees(golden_case):
@@ -1624,7 +1662,7 @@ def test_multi_rank_rehearsal_equals_one_rank(tmp_path, ranks):
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    common = ["--steps", "1", "--warmup", "0", "--nq", "3001", "--nh", "12", "--no-cpu-baseline"]
+    common = ["--steps", "1", "--warmup", "0", "--nq", "3001", "--nh", "12", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common,
                         capture_output=True, text=True, timeout=900, env=env)
@@ -2098,7 +2136,7 @@ def test_two_rank_rehearsal_of_the_protein_shape(tmp_path):
     import subprocess
     import sys
     from tests.conftest import ROOT
-    common = ["--workload", "aa_50k_x500", "--steps", "1", "--warmup", "0", "--nq", "2000", "--no-cpu-baseline"]
+    common = ["--workload", "aa_50k_x500", "--steps", "1", "--warmup", "0", "--nq", "2000", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     env.pop("WITCH_FORCE_COLLECTIVES", None)
     import pathlib

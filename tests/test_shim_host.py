@@ -36,9 +36,26 @@ def _hmm(tmp_path):
 
 
 @pytest.fixture()
-def server(tmp_path):
+def sock_dir(tmp_path):
+    """A directory for AF_UNIX sockets.  Their paths may not exceed 107 bytes, which pytest's tmp_path under a long
+    $TMPDIR does; then a short private directory under /tmp is used instead (removed afterwards)."""
+    if len(str(tmp_path)) <= 64:
+        yield tmp_path
+        return
+    import pathlib
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="wh_sock_", dir="/tmp")
+    try:
+        yield pathlib.Path(d)
+    finally:
+        shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture()
+def server(sock_dir):
     from witch_amd.shim.server import Server
-    sock = str(tmp_path / "s.sock")
+    sock = str(sock_dir / "s.sock")
     srv = Server(FakeBackend(), sock)
     ready = threading.Event()
     threading.Thread(target=srv.serve_forever, args=(ready,), daemon=True).start()
@@ -153,14 +170,14 @@ def test_evalues_follow_hmmer_formula(golden_case):
     assert n > 0 or case.name.startswith("example")
 
 
-def test_only_one_server_survives_a_stampede(tmp_path):
+def test_only_one_server_survives_a_stampede(sock_dir):
     """WITCH fires num_cpus hmmsearch calls at once; every client that cannot connect launches a
     server.  The flock on <socket>.lock (taken before the socket or the GPU is touched) leaves exactly
     one; the socket lives in a directory private to the user."""
     import sys
     import time
     from witch_amd.shim.server import request
-    d = tmp_path / "rt"
+    d = sock_dir / "rt"
     sock = str(d / "witch_hip" / "server.sock")
     env = dict(os.environ, PYTHONPATH=ROOT, WITCH_HIP_IDLE_TIMEOUT="30")
     procs = [subprocess.Popen([sys.executable, "-m", "witch_amd.shim.server", "--socket", sock], env=env,

@@ -27,7 +27,7 @@ def main():
         "consensus_kernel_hbm_bytes_per_launch": t.get("consensus_kernel", {}).get("hbm_bytes_per_launch"),
         "resolve_kernel_hbm_bytes_per_launch": t.get("resolve_kernel", {}).get("hbm_bytes_per_launch"),
         "source": "profiles/%s_traffic.json (tools/profile_round.sh %s: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / SQ counters, separate passes of "
-                  "`python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-level1 --no-also`; gfx950 FETCH_SIZE correction applied)%s"
+                  "`python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-level1 --no-also`; gfx950 FETCH_SIZE correction applied)%s"
                   % (tag, tag, (" " + sys.argv[4]) if len(sys.argv) > 4 else ""),
     }
     json.dump(out, open(os.path.join(ROOT, "profiles", "traffic.json"), "w"), indent=1)
