@@ -45,8 +45,8 @@ extern "C" {
 #define WH_EIO        -2   /* cannot open / parse an HMM file                */
 #define WH_ENODEV     -3   /* no usable HIP device                           */
 #define WH_EHIP       -4   /* a HIP runtime call failed                      */
-#define WH_ERANGE     -5   /* model (> 16384 nodes) or query longer than this build supports */
-#define WH_ENOMEM     -6
+#define WH_ERANGE     -5   /* query longer than this build supports, or too many pairs in one call (models: any length) */
+#define WH_ENOMEM     -6   /* device memory: also a call whose workspace for ONE workgroup does not fit (wh_last_error: the figures) */
 
 #define WH_ALPH_DNA    0
 #define WH_ALPH_RNA    1
@@ -220,7 +220,7 @@ int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches);
 /* Timing mode only: the scoring launches of the last wh_score[_dev] call, in launch order - the cells-per-lane class of the
  * launch's models (16 = models of 961..1024 nodes ...), the kernel family (0 phase-call wh::k7::score_kernel7, 1
  * pass-synchronous wh::score_big_kernel, 2 any-size wh::generic_front_kernel, 3 several-waves-per-pair wh::wide::score_wide_kernel with
- * cells_per_lane = 24 x waves) and its HIP-event duration.  Returns the number
+ * cells_per_lane = (cells per virtual lane: 12, 16, 24 or 48) x waves) and its HIP-event duration.  Returns the number
  * of launches (the first <cap> are written); bench.py names the measured dominant kernel from it. */
 int wh_last_score_launches(wh_ehmm *e, int32_t *cells_per_lane, int32_t *kind, double *ms, int cap);
 /* When enabled, every kernel launch is bracketed by HIP events (bench/roofline use). */

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Throughput of the any-size kernels (wh_generic.hip): <nq> fragments against <nh> models of ~<root> nodes.
+"""Throughput of the kernels that serve models beyond 3 072 nodes: <nq> fragments against <nh> models of ~<root> nodes,
+scored (cells/s over the scoring kernels + the resolver queue; which kernel classes served the call: kind 2 = float64
+any-size front end, kind 3 = several waves per pair with <cells per lane x waves>) and aligned.
 usage: tools/bench_anysize.py [root=6000] [nq=2000] [qlen=150] [nh=2]"""
 import os
 import sys
@@ -33,6 +35,7 @@ for it in range(2):
     ms4, _ = e.last_kernel_ms(4)
     print("iter %d: %d queries of %d x %d models (M %d..%d): front end %.1f ms, resolver queue %.1f ms, %.3g cells/s, wall %.2f s"
           % (it, nq, qlen, e.H, e.M.min(), e.M.max(), ms0, ms4, cells / ((ms0 + ms4) * 1e-3), t1 - t0), flush=True)
+    print("  scoring launches (cells per lane, kind, ms): %s" % e.last_score_launches(), flush=True)
 pq = list(range(nq))
 ph = [0] * nq
 for it in range(2):

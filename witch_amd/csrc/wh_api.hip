@@ -80,6 +80,8 @@ struct Knobs {
 };
 static const int kScorePathSlot = 128;   // d_counter[128..143]: eight 64-bit counters of the last scoring call: six paths (wh_last_score_paths), bytes of Forward rows stored, spare (wh_last_score_counters); [96..123] belong to wh_align_dev
 static const int kLongListSlot = 148;    // d_counter[148]: pairs flagged WH_FLAG_TRUNC after the resolver (long-list pass)
+static const int kWideScoreSlot = 160;   // d_counter[160..175]: work-queue heads of the wide scoring launches, one per (cells per lane, waves) class
+static const int kWideScoreClasses = 16; // (13 exist: 12 x 5..8, 16 x 7..8, 24 x 6..8, 48 x 5..8; WH_FORCE_WIDE adds smaller workgroups of one of them)
 static const int kResolveErrSlot = 146;  // d_counter[140]: queue records the resolver found in a segment of another model (never, for a well-formed segment list)
 static const int kStagedMaxBatches = 1 << 15;   // staged launches: batches per scoring call (32 counters each: 4 MB)
 static const int kMaxLaunches = 60;   // work-queue heads in d_counter (slot 63 belongs to the consensus kernel)
@@ -94,9 +96,9 @@ struct wh_ehmm {
   std::map<int, std::vector<int32_t>> by_q;   // Q class -> model positions
   std::vector<int32_t> generic;               // models beyond the register-resident classes (wh_generic.hip)
   std::vector<int32_t> generic_front;         // ... of them, those SCORED by the float64 front end (the others: wide_by_w)
-  std::map<int, std::vector<int32_t>> wide_by_w;   // cells per lane * 16 + waves per pair -> models scored by wh_score_wide.hip (3 073 - 12 288 nodes)
+  std::map<int, std::vector<int32_t>> wide_by_w;   // cells per lane * 16 + waves per pair -> models scored by wh_score_wide.hip (3 073 - 24 576 nodes)
   unsigned resolver_launches = 0;             // see ResolveArgs::launch_id
-  int force_wide_q = 0;                       // WH_FORCE_WIDE=<4|12|24>: cells per lane of every model's wide tables (tests)
+  int force_wide_q = 0;                       // WH_FORCE_WIDE=<4|12|16|24|48>: cells per lane of every model's wide tables (tests)
   bool force_wide = false;                    // WH_FORCE_WIDE: EVERY model is scored by the wide kernel (test hook)
   DevBuf d_wscratch;                          // Forward slabs of the wide kernel's workgroups
   DevBuf d_hmms, d_tables, d_nseq, d_index, d_lists, d_counter, d_scratch;
@@ -216,17 +218,18 @@ wh_ehmm *wh_ehmm_load(const char *const *hmm_paths, const int32_t *hmm_index, co
   // Parsing the text files and laying out the tables is host work per model (a few ms per 1 500-node model):
   // done on a small thread pool, then concatenated in model order so that the buffers do not depend on timing.
   struct Built { int rc = WH_OK; std::string err; int Q = -1, wideW = 0; std::vector<float> fw, bw, em, emn, wfw, wbw, wem; std::vector<double> gfw, gem, gsum; };
-  // WH_FORCE_WIDE=<4|24>: every model that fits 8 waves of that many cells per lane ALSO gets wide tables and is scored by the
+  // WH_FORCE_WIDE=<4|12|16|24|48>: every model that fits 8 waves of that many cells per lane ALSO gets wide tables and is scored by the
   // several-waves-per-pair kernel (tests run the golden cases through it; production: models beyond 3 072 nodes only)
   const int force_wide_q = getenv("WH_FORCE_WIDE") ? atoi(getenv("WH_FORCE_WIDE")) : 0;
-  e->force_wide = force_wide_q == 4 || force_wide_q == kWideQ || force_wide_q == kWideQReg || force_wide_q == kWideQReg2;
+  e->force_wide = force_wide_q == 4 || force_wide_q == kWideQ || force_wide_q == kWideQReg || force_wide_q == kWideQReg2 || force_wide_q == kWideQBig;
   e->force_wide_q = e->force_wide ? force_wide_q : 0;
   const bool force_wide = e->force_wide;
-  // cells per lane of a model's wide tables: 12 (transition tables in registers) up to 6 144 nodes, 24 beyond
-  // (12 up to 6 144 nodes, 16 up to 8 192: transition tables in registers; 24 beyond: tables from L2)
+  // cells per lane of a model's wide tables: 12 up to 6 144 nodes, 16 up to 8 192 (transition tables in registers);
+  // 24 up to 12 288 and 48 up to 24 576 (tables from L2); larger models have no wide tables (float64 kernels)
   auto wide_q_of = [force_wide, force_wide_q](int M) {
     if (force_wide) return force_wide_q;
-    return M <= kWideQReg * kWave * kWideWavesMax ? kWideQReg : M <= kWideQReg2 * kWave * kWideWavesMax ? kWideQReg2 : kWideQ;
+    return M <= kWideQReg * kWave * kWideWavesMax ? kWideQReg : M <= kWideQReg2 * kWave * kWideWavesMax ? kWideQReg2
+         : M <= kWideQ * kWave * kWideWavesMax ? kWideQ : kWideQBig;
   };
   std::vector<Built> built((size_t)n);
   {
@@ -241,7 +244,6 @@ wh_ehmm *wh_ehmm_load(const char *const *hmm_paths, const int32_t *hmm_index, co
         h.index = hmm_index ? hmm_index[i] : i;
         if (nseq) h.nseq = nseq[i];
         b.Q = choose_Q(h.M);
-        if (b.Q < 0) continue;
         if (b.Q <= kMaxQ) build_tables(h, b.Q, b.fw, b.bw, b.em);     // (the any-size kernels read the float64 tables only)
         if (b.Q > kMaxQ || force_wide) {
           const int wide_q = wide_q_of(h.M);
@@ -279,10 +281,6 @@ wh_ehmm *wh_ehmm_load(const char *const *hmm_paths, const int32_t *hmm_index, co
       return nullptr;
     }
     const int Q = b.Q;
-    if (Q < 0) {
-      set_error("%s: model length %d exceeds this build's limit of %d nodes", hmm_paths[i], h.M, kMaxQGen * kWave);
-      return nullptr;
-    }
     DevHMM &d = e->dev[(size_t)i];
     d.M = h.M; d.Q = Q; d.Mpad = Q * kWave; d.K = h.K; d.Kp = h.Kp; d.nseq = h.nseq; d.index = h.index; d.qclass = Q;
     d.fw_off = (int64_t)tables.size(); tables.insert(tables.end(), b.fw.begin(), b.fw.end());
@@ -527,9 +525,30 @@ static int plan_block1(const wh_ehmm *e, int Q, int K, int Lcap, int wmax, int *
 
 // Resident workgroups are capped so that <per_block> bytes of per-wave workspace each fit in
 // about 70 % of the free HBM (the work-item counter loops tolerate fewer workgroups than CUs).
-static int clamp_blocks(int blocks, size_t per_block, const DevBuf &have) {
-  if (blocks <= 1 || per_block == 0) return blocks;
+// -1 when not even ONE workgroup's workspace fits (the buffer <have> counts as free: it is given
+// back first): the error names the model length, the query length cap and the figures, and the
+// caller refuses the call with WH_ENOMEM before it launches anything more.
+// (<M> is the longest model's node count, or for the consensus kernel (<backbone>) the backbone's column count)
+static bool one_block_fits(size_t per_block, const DevBuf &have, int M, int Lcap, const char *what, bool backbone = false) {
+  if (per_block <= have.cap) return true;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return true;     // (the allocation itself will say)
+  if (per_block <= free_b + have.cap) return true;
+  set_error("%s: the workspace of one workgroup does not fit on the device (%s %d %s, queries of up to %d residues: "
+            "%zu bytes per workgroup, %zu bytes free)", what, backbone ? "a backbone of" : "models of up to", M, backbone ? "columns" : "nodes",
+            Lcap, per_block, free_b + have.cap);
+  return false;
+}
+// floats of one workgroup's slab of the wide scoring kernel: Forward rows [row][2][Q4][NL] (+ per-row lane masks)
+static size_t wide_score_stride(int Lc, int wq, int W, bool sparse) {
+  const size_t st = (size_t)(Lc + 1) * 2 * wq * W * kWave + (sparse ? (size_t)(Lc + 1) * W * 2 + 4 : 0);
+  return (st + 3) & ~(size_t)3;
+}
+static int clamp_blocks(int blocks, size_t per_block, const DevBuf &have, int M, int Lcap, const char *what, bool backbone = false) {
+  if (blocks < 1 || per_block == 0) return blocks;
   if ((size_t)blocks * per_block <= have.cap) return blocks;
+  if (!one_block_fits(per_block, have, M, Lcap, what, backbone)) return -1;
+  if (blocks == 1) return blocks;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return blocks;
   const size_t budget = (size_t)((double)(free_b + have.cap) * 0.7);
@@ -692,6 +711,22 @@ int wh_score_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets
   if (nq * (int64_t)e->hmms.size() >= 0x7FFFFFFF) {
     set_error("wh_score_dev: %lld queries x %zu models is 2^31 pairs or more; score the queries in chunks", (long long)nq, e->hmms.size());
     return WH_ERANGE;
+  }
+  // The float64 front end's slab of one wave and the wide kernel's slab of one workgroup must fit on the device (models
+  // beyond the one-wave float32 kernels, long queries): otherwise the call is refused before anything is launched.  (The
+  // resolver's and the long-list pass's slabs depend on what the scoring launches queue: they are checked when planned.)
+  if (nq > 0 && !e->generic.empty()) {
+    const int Lc = std::max(max_len, 1);
+    if (!one_block_fits(((generic_front_doubles(Lc, e->max_Q) + 1) & ~(size_t)1) * sizeof(double), e->d_rmx, e->max_M, Lc, "any-size front end"))
+      return WH_ENOMEM;
+  }
+  if (nq > 0 && !e->wide_by_w.empty()) {
+    const int Lc = std::max(max_len, 1);
+    if ((int)e->wide_by_w.size() > kWideScoreClasses) { set_error("too many classes of long models (%zu)", e->wide_by_w.size()); return WH_ERANGE; }
+    for (auto &kv : e->wide_by_w)
+      if (wide_lds_bytes(Lc) <= kLdsBudget &&
+          !one_block_fits(wide_score_stride(Lc, kv.first >> 4, kv.first & 15, !getenv("WH_WIDE_DENSE")) * sizeof(float), e->d_wscratch, e->max_M, Lc, "wide scoring"))
+        return WH_ENOMEM;
   }
   // The queue of pairs with a multidomain region is sized by ESTIMATE (a per-pair record is 296 bytes; the worst case,
   // one record per pair, was 3.4 GB at the headline for a class that is 0.005 % of its pairs).  The kernels count every
@@ -918,7 +953,8 @@ static int score_dev_pass(wh_ehmm *e, const uint8_t *d_residues, const int64_t *
       a.spec_stride = specg ? (size_t)8 * a.SP : quadk ? (size_t)(5 * kScoreSpecArrays + 1) * a.SP : 0;
       if (quadk) { specg = true; a.p2win = 0; a.QB = std::max(a.QB, waves * 8); a.n_qblocks = (int)((nq + a.QB - 1) / a.QB); a.n_items = a.n_list * a.n_qblocks; }   // (HBM region per wave; items of two quads per wave)
       int blocks = std::min(a.n_items, big ? e->cu_count : e->cu_count * std::max(1, 8 / waves));
-      blocks = clamp_blocks(blocks, (size_t)waves * (a.scratch_stride + a.spec_stride) * sizeof(float), e->d_scratch);
+      blocks = clamp_blocks(blocks, (size_t)waves * (a.scratch_stride + a.spec_stride) * sizeof(float), e->d_scratch, e->max_M, a.Lcap, "scoring");
+      if (blocks < 0) return WH_ENOMEM;
       if (pass == 0) {
         need_scratch = std::max(need_scratch, (size_t)blocks * waves * a.scratch_stride * sizeof(float));
         if (specg) need_spec = std::max(need_spec, (size_t)blocks * waves * a.spec_stride * sizeof(float));
@@ -971,7 +1007,7 @@ static int score_dev_pass(wh_ehmm *e, const uint8_t *d_residues, const int64_t *
     }
   }
   if (nq > 0 && !e->wide_by_w.empty()) {
-    // ---- models of 3 073 - 12 288 nodes: several wavefronts per pair, float32 (wh_score_wide.hip); one launch per
+    // ---- models of 3 073 - 24 576 nodes: several wavefronts per pair, float32 (wh_score_wide.hip); one launch per
     // waves-per-pair class.  A query batch too long for the kernel's LDS block falls back to the float64 front end below.
     const int Lc = std::max(max_len, 1);
     const size_t wlds0 = wide_lds_bytes(Lc);
@@ -994,8 +1030,8 @@ static int score_dev_pass(wh_ehmm *e, const uint8_t *d_residues, const int64_t *
         a.hmm_list = (const int32_t *)e->d_lists.p + woff; a.n_list = (int)kv.second.size();
         woff += kv.second.size();
         a.residues = d_residues; a.offsets = d_offsets; a.nq = nq;
-        if (wclass > 8) { set_error("too many classes of long models"); return WH_ERANGE; }
-        a.counter = (int *)e->d_counter.p + 68 + wclass++;
+        if (wclass >= kWideScoreClasses) { set_error("too many classes of long models"); return WH_ERANGE; }
+        a.counter = (int *)e->d_counter.p + kWideScoreSlot + wclass++;
         a.em_lds = em_lds ? 1 : 0;
         a.Lcap = Lc; a.SP = (Lc + 1 + 3) / 4 * 4;
         a.decibits = d_decibits; a.flags = d_flags; a.fwd_bits = d_fwd_bits; a.detail = d_detail;
@@ -1004,12 +1040,12 @@ static int score_dev_pass(wh_ehmm *e, const uint8_t *d_residues, const int64_t *
         if (resolve) { a.rrecs = (ResolveRec *)e->d_rrecs.p; a.rcount = (int *)e->d_counter.p + 64; a.rcap = (int)e->rq_cap; }
         a.qorder = qorder_all;
         a.sparse = getenv("WH_WIDE_DENSE") ? 0 : 1;
-        a.scratch_stride = (size_t)(Lc + 1) * 2 * wq * W * kWave + (a.sparse ? (size_t)(Lc + 1) * W * 2 + 4 : 0);
-        a.scratch_stride = (a.scratch_stride + 3) & ~(size_t)3;
+        a.scratch_stride = wide_score_stride(Lc, wq, W, a.sparse != 0);
         const int64_t n_items = nq * (int64_t)a.n_list;
         const int per_cu = (W <= 4 && 2 * wlds <= kLdsBudget) ? 2 : 1;
         int blocks = (int)std::min<int64_t>(n_items, (int64_t)e->cu_count * per_cu);
-        blocks = clamp_blocks(blocks, a.scratch_stride * sizeof(float), e->d_wscratch);
+        blocks = clamp_blocks(blocks, a.scratch_stride * sizeof(float), e->d_wscratch, e->max_M, Lc, "wide scoring");
+        if (blocks < 0) return WH_ENOMEM;
         if (e->d_wscratch.ensure((size_t)blocks * a.scratch_stride * sizeof(float))) return WH_ENOMEM;
         a.scratch = (float *)e->d_wscratch.p;
         HIPCHK(hipMemsetAsync(a.counter, 0, sizeof(int), s));
@@ -1071,7 +1107,8 @@ static int score_dev_pass(wh_ehmm *e, const uint8_t *d_residues, const int64_t *
     if (glds > kLdsBudget) { set_error("query length %d does not fit the any-size kernel's LDS", max_len); return WH_ERANGE; }
     const int64_t n_items = nq * (int64_t)n_gen;
     int blocks = (int)std::min<int64_t>(n_items, (int64_t)e->cu_count * std::min<size_t>(12, kLdsBudget / glds));
-    blocks = clamp_blocks(blocks, g.slab_stride * sizeof(double), e->d_rmx);
+    blocks = clamp_blocks(blocks, g.slab_stride * sizeof(double), e->d_rmx, e->max_M, Lc, "any-size front end");
+    if (blocks < 0) return WH_ENOMEM;
     if (e->d_rmx.ensure((size_t)blocks * g.slab_stride * sizeof(double))) return WH_ENOMEM;
     g.slab = (double *)e->d_rmx.p;
     HIPCHK(hipMemsetAsync(g.counter, 0, sizeof(int), s));
@@ -1273,7 +1310,8 @@ static int score_dev_pass(wh_ehmm *e, const uint8_t *d_residues, const int64_t *
         const int economy = std::max(32, n_multi / (4 * waves));
         if ((size_t)blocks > have) blocks = std::max((int)std::min<size_t>(have, (size_t)blocks), std::min(blocks, economy));
       }
-      blocks = clamp_blocks(blocks, (size_t)waves * (r.mx_stride * sizeof(double) + r.seg_stride * sizeof(int32_t)), e->d_rmx);
+      blocks = clamp_blocks(blocks, (size_t)waves * (r.mx_stride * sizeof(double) + r.seg_stride * sizeof(int32_t)), e->d_rmx, e->max_M, Lc, "resolver");
+      if (blocks < 0) return WH_ENOMEM;
       if (e->d_rmx.ensure((size_t)blocks * waves * r.mx_stride * sizeof(double)) || e->d_rsegs.ensure((size_t)blocks * waves * r.seg_stride * sizeof(int32_t)))
         return WH_ENOMEM;
       r.mx = (double *)e->d_rmx.p; r.segs = (int32_t *)e->d_rsegs.p;
@@ -1361,7 +1399,8 @@ static int score_dev_pass(wh_ehmm *e, const uint8_t *d_residues, const int64_t *
           g.rext = (int32_t *)e->d_rext.p; g.rext_stride = rext_stride; g.ext_cap = ext_cap;
           const size_t glds = generic_lds_bytes(Lc);
           int gblocks = (int)std::min<int64_t>(n_round, (int64_t)e->cu_count * std::min<size_t>(12, kLdsBudget / glds));
-          gblocks = clamp_blocks(gblocks, g.slab_stride * sizeof(double), e->d_rmx);
+          gblocks = clamp_blocks(gblocks, g.slab_stride * sizeof(double), e->d_rmx, e->max_M, Lc, "long-list front end");
+          if (gblocks < 0) return WH_ENOMEM;
           if (e->d_rmx.ensure((size_t)gblocks * g.slab_stride * sizeof(double))) return WH_ENOMEM;
           g.slab = (double *)e->d_rmx.p;
           HIPCHK(hipMemsetAsync(g.counter, 0, sizeof(int), s));
@@ -1566,6 +1605,15 @@ int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets
     cnt[(size_t)ph[(size_t)p] + 1]++;
   }
   for (int h = 0; h < H; h++) cnt[(size_t)h + 1] += cnt[(size_t)h];
+  // a pair on a model beyond the register kernels may end on the float64 kernel: refuse the call before anything is
+  // launched when not even one wave's slab of that kernel fits on the device
+  for (int h = 0; h < H; h++)
+    if (cnt[(size_t)h + 1] > cnt[(size_t)h] && e->dev[(size_t)h].Q > kMaxQ) {
+      const int Lc = std::max(max_len, 1);
+      if (!one_block_fits(((generic_align_doubles(Lc, e->max_Q) + 1) & ~(size_t)1) * sizeof(double), e->d_rmx, e->max_M, Lc, "any-size alignment"))
+        return WH_ENOMEM;
+      break;
+    }
   std::vector<int32_t> order((size_t)npairs), cursor(cnt.begin(), cnt.end() - 1);
   for (int64_t p = 0; p < npairs; p++) order[(size_t)cursor[(size_t)ph[(size_t)p]]++] = (int32_t)p;
   if (e->d_order.ensure(sizeof(int32_t) * (size_t)npairs)) return WH_ENOMEM;
@@ -1656,7 +1704,8 @@ int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets
     int blocks = std::min(n, e->cu_count * std::max(1, 8 / waves));
     a.scratch_stride = (size_t)(a.Lcap + 1) * 5 * Q * kWave;
     a.spec_stride = plans[pl][5] < 0 ? (size_t)kAlignSpecArrays * a.SP : 0;
-    blocks = clamp_blocks(blocks, (size_t)waves * (a.scratch_stride + a.spec_stride) * sizeof(float), e->d_ascratch);
+    blocks = clamp_blocks(blocks, (size_t)waves * (a.scratch_stride + a.spec_stride) * sizeof(float), e->d_ascratch, e->max_M, a.Lcap, "alignment");
+    if (blocks < 0) return WH_ENOMEM;
     if (pass == 0) {
       need_scratch = std::max(need_scratch, (size_t)blocks * waves * a.scratch_stride * sizeof(float));
       if (plans[pl][5] < 0) need_spec = std::max(need_spec, (size_t)blocks * waves * a.spec_stride * sizeof(float));
@@ -1723,13 +1772,13 @@ int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets
     std::vector<int32_t> gitems;
     const int Lc0 = std::max(max_len, 1);
     // models of 3 073 - 12 288 nodes: the several-waves-per-pair alignment kernel (wh_score_wide.hip); pairs that leave
-    // float32 range there, longer queries and larger models go to the float64 kernel below
+    // float32 range there, longer queries and larger models (the 48-cell scoring class included) go to the float64 kernel below
     const size_t walds = wide_align_lds_bytes(Lc0);
     const bool use_wide = walds <= kLdsBudget && !e->wide_by_w.empty() && !e->knobs.no_wide_align;
     std::map<int, std::vector<int32_t>> witems;
     for (int64_t p = 0; p < npairs; p++) {
       const DevHMM &dm = e->dev[(size_t)ph[(size_t)p]];
-      if (use_wide && dm.wideW > 0 && (dm.Q > kMaxQ || e->force_wide)) witems[dm.wideQ * 16 + dm.wideW].push_back((int32_t)p);
+      if (use_wide && dm.wideW > 0 && dm.wideQ != kWideQBig && (dm.Q > kMaxQ || e->force_wide)) witems[dm.wideQ * 16 + dm.wideW].push_back((int32_t)p);
       else if (dm.Q > kMaxQ) gitems.push_back((int32_t)p);
     }
     if (!witems.empty()) {
@@ -1757,7 +1806,8 @@ int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets
         wa.K = e->K; wa.Kp = e->Kp;
         wa.scratch_stride = (size_t)(Lc0 + 1) * 5 * wq * W * kWave;
         int blocks = (int)std::min<size_t>(kv.second.size(), (size_t)e->cu_count);
-        blocks = clamp_blocks(blocks, wa.scratch_stride * sizeof(float), e->d_wscratch);
+        blocks = clamp_blocks(blocks, wa.scratch_stride * sizeof(float), e->d_wscratch, e->max_M, Lc0, "wide alignment");
+        if (blocks < 0) return WH_ENOMEM;
         if (e->d_wscratch.ensure((size_t)blocks * wa.scratch_stride * sizeof(float))) return WH_ENOMEM;
         wa.scratch = (float *)e->d_wscratch.p;
         HIPCHK(hipMemsetAsync(wa.counter, 0, sizeof(int), s));
@@ -1793,7 +1843,8 @@ int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets
       const size_t glds = (size_t)Lc + 64;
       if (glds > kLdsBudget) { set_error("query length %d does not fit the any-size kernel's LDS", max_len); return WH_ERANGE; }
       int blocks = (int)std::min<size_t>(gitems.size(), (size_t)e->cu_count * std::min<size_t>(12, kLdsBudget / glds));
-      blocks = clamp_blocks(blocks, g.slab_stride * sizeof(double), e->d_rmx);
+      blocks = clamp_blocks(blocks, g.slab_stride * sizeof(double), e->d_rmx, e->max_M, Lc, "any-size alignment");
+      if (blocks < 0) return WH_ENOMEM;
       if (e->d_rmx.ensure((size_t)blocks * g.slab_stride * sizeof(double))) return WH_ENOMEM;
       g.slab = (double *)e->d_rmx.p;
       HIPCHK(hipMemsetAsync(g.counter, 0, sizeof(int), s));
@@ -1881,7 +1932,8 @@ int wh_consensus_dev(wh_ehmm *e, const int64_t *d_offsets, int64_t nq, int32_t m
     if (row_in_hbm) waves = 4;
     const size_t lds = row_in_hbm ? 0 : (size_t)waves * (a.Wcap + 2) * sizeof(double);
     int blocks = (int)std::min<int64_t>((nq + waves - 1) / waves, (int64_t)e->cu_count * 2);
-    blocks = clamp_blocks(blocks, (size_t)waves * ((size_t)(a.Lcap + 1) * (a.Wcap + 2) + (size_t)a.Lcap * a.KMAX * 12 + (size_t)a.Lcap * 4 + (size_t)(a.Wcap + 2) * 8), e->d_back);
+    blocks = clamp_blocks(blocks, (size_t)waves * ((size_t)(a.Lcap + 1) * (a.Wcap + 2) + (size_t)a.Lcap * a.KMAX * 12 + (size_t)a.Lcap * 4 + (size_t)(a.Wcap + 2) * 8), e->d_back, backbone_length, a.Lcap, "consensus", true);
+    if (blocks < 0) return WH_ENOMEM;
     const size_t nw = (size_t)blocks * waves;
     if (row_in_hbm) {
       if (e->d_crow.ensure(nw * (size_t)(a.Wcap + 2) * sizeof(double))) return WH_ENOMEM;

@@ -11,12 +11,12 @@ namespace wh {
 
 constexpr int kWave = 64;          // CDNA wavefront width
 constexpr int kMaxQ = 48;          // cells per lane of the register-resident kernels -> M <= 64*kMaxQ = 3072
-constexpr int kMaxQGen = 256;      // ... of the any-size float64 kernels (wh_generic.hip) -> M <= 16384
 constexpr int kMaxQFast = 24;      // up to here both transition orientations stay resident in LDS
 constexpr int kQRegMax = 16;       // up to this Q the transition tables live in VGPRs
 constexpr int kWideQ = 24;         // cells per lane of the several-waves-per-pair scoring kernel
 constexpr int kWideQReg = 12;      // ... its variant with the transition tables in registers: models of up to 8 x 64 x 12 = 6 144 nodes
 constexpr int kWideQReg2 = 16;     // ... and the same with 16 cells per lane: up to 8 192 nodes (no room for the row-ahead requests of P4)
+constexpr int kWideQBig = 48;      // ... and with 48 cells per lane: models of 12 289 - 24 576 nodes (scoring only)
 constexpr int kWideWavesMax = 8;   // ... and its largest workgroup: models of up to 8 x 64 x 24 = 12 288 nodes
 // per-wave LDS block of the scoring kernels: region list (i, j) x WH_MAX_ENVELOPES, 8 spare ints, and the
 // envelope results (envsc, domcorr) x WH_MAX_ENVELOPES staged for the multidomain resolver's record
@@ -67,7 +67,7 @@ enum { BW_MM = 0, BW_IM, BW_DM, BW_MI, BW_II, BW_MD, BW_DD, BW_E, BW_NARR, BW_P 
 // Kernels copy it to LDS only if they ask for it (wh_score7.hip, WH_K7_MAXQP); measured on MI355X
 // it does not pay: +3 % kernel time at two waves per SIMD, +0.5 % at three.
 
-int  choose_Q(int M);     // cells per lane for a model of M nodes, or -1 if unsupported
+int  choose_Q(int M);     // cells per lane for a model of M nodes
 void build_tables(const HostHMM &h, int Q, std::vector<float> &fw, std::vector<float> &bw,
                   std::vector<float> &em, int lanes = kWave);   // lanes > 64: the several-waves-per-pair kernel (wh_score_wide.hip)
 // float64 tables of the multidomain resolver: 8 forward arrays and Kp emission rows, value of node

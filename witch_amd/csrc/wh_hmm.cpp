@@ -189,8 +189,8 @@ int choose_Q(int M) {
   q = (q + 3) / 4 * 4;
   if (q < 4) q = 4;
   // instantiated classes: 4..24 (both orientations resident in LDS), 28..48 (pass-synchronous swap); beyond:
-  // the any-size float64 kernels (wh_generic.hip), which take Q as a run-time value
-  if (q > kMaxQGen) return -1;
+  // the any-size float64 kernels (wh_generic.hip), which take Q as a run-time value: no ceiling (what does not fit
+  // the device is refused per call, wh_api.hip)
   return q;
 }
 

@@ -178,7 +178,7 @@ size_t resolve_dcache_doubles();
 size_t resolve_tail_row_doubles();
 
 // models of any size (wh_generic.hip)
-// several wavefronts per pair (wh_score_wide.hip): models of 3 073 - 12 288 nodes
+// several wavefronts per pair (wh_score_wide.hip): models of 3 073 - 24 576 nodes (scoring), 3 073 - 12 288 (alignment)
 struct WideArgs {
   const DevHMM *hmms;
   const float *tables;

@@ -21,6 +21,7 @@
 // clustering reproduces Easel's vertex order exactly (parallel link tests, serial stack updates).
 // -DWH_RESOLVE_DEBUG compiles the device printf dumps in (option WH_RDBG; tests/dbg/dbg_resolve.py):
 // off by default, device printf alone costs the kernel half of its register budget.
+#include <climits>
 #include <hip/hip_runtime.h>
 
 #include "wh_launch.h"
@@ -82,18 +83,18 @@ __device__ __forceinline__ bool seg_linked(int i1, int j1, int k1, int m1, int i
 }  // namespace
 
 // LDS per wave (4-byte units).  What the traces use - the domains of the current trace, their null2 vectors, the emitting
-// state per residue (int16) - and what the clustering uses afterwards - Easel's two vertex stacks (uint16) - are never
+// state per residue (int16; int32 when a model has more than 32 767 nodes) - and what the clustering uses afterwards - Easel's two vertex stacks (uint16) - are never
 // alive together and share one block (round 4: 19 -> 11 KB per wave at 2 000-residue queries, which makes room for a
 // model's float64 transition arrays beside eight waves).  The end-point histograms of the cluster statistics live in the
 // wave's HBM slab.
-__host__ __device__ inline size_t resolve_uni_ints(int Lcap) {
+__host__ __device__ inline bool resolve_stk32(int Mmax) { return Mmax > 32767; }
+__host__ __device__ inline size_t resolve_uni_ints(int Lcap, int Mmax) {
   const int Lp = (Lcap + 4) & ~1;
-  const size_t traces = (size_t)kDomMax * (4 + 32) + Lp / 2 + 2, clustering = kSegLds;
+  const size_t traces = (size_t)kDomMax * (4 + 32) + (resolve_stk32(Mmax) ? Lp : Lp / 2) + 2, clustering = kSegLds;
   return ((traces > clustering ? traces : clustering) + 1) & ~(size_t)1;
 }
 __host__ __device__ inline size_t resolve_lds_ints(int Lcap, int Mmax) {
-  (void)Mmax;
-  return (((size_t)(Lcap + 8) / 4 + 2 + 1) & ~(size_t)1) /*seq*/ + resolve_uni_ints(Lcap) + 128 /*64 float64 bins of the E-state row pass*/ + 4 * kEnvMax + 3 * kClusMax + 16
+  return (((size_t)(Lcap + 8) / 4 + 2 + 1) & ~(size_t)1) /*seq*/ + resolve_uni_ints(Lcap, Mmax) + 128 /*64 float64 bins of the E-state row pass*/ + 4 * kEnvMax + 3 * kClusMax + 16
          + 2 * 2 * kHist /*WH_STATS: fetch keys of the previous and the current trace*/;
 }
 // waves per SIMD the kernel is compiled for (registers per lane = 512 / WH_RES_OCC)
@@ -150,10 +151,14 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
   int *dom = uni;                                                 // traces: kDomMax x (sqfrom, sqto, hmmfrom, hmmto)
   float *dnull = reinterpret_cast<float *>(dom + 4 * kDomMax);   // kDomMax x 32
   short *stk = reinterpret_cast<short *>(dnull + 32 * kDomMax);  // emitting state of each residue: +k match, -k insert
+  int *stk32 = reinterpret_cast<int *>(stk);                      // ... the same in 32 bits when a node index does not fit 16
+  const bool wide_stk = resolve_stk32(a.Mmax);
+  auto stk_get = [&](int p) -> int { return wide_stk ? stk32[p] : (int)stk[p]; };
+  auto stk_set = [&](int p, int v) { if (wide_stk) stk32[p] = v; else stk[p] = (short)v; };
   const int SEGCAP = a.seg_cap;
   unsigned short *s_a = reinterpret_cast<unsigned short *>(uni); // clustering (after the traces): Easel's vertex stacks, same block
   unsigned short *s_b = s_a + kSegLds;
-  double *bins = reinterpret_cast<double *>(uni + resolve_uni_ints(a.Lcap));   // 64 float64 bins of the E-state row pass (8-byte aligned)
+  double *bins = reinterpret_cast<double *>(uni + resolve_uni_ints(a.Lcap, a.Mmax));   // 64 float64 bins of the E-state row pass (8-byte aligned)
   int *misc = reinterpret_cast<int *>(bins + 64);                // 4 x kEnvMax + 3 x kClusMax ints: envelope list of the pair (detail), cluster list of a region
   unsigned long long *hprev = reinterpret_cast<unsigned long long *>(misc + 4 * kEnvMax + 3 * kClusMax + 16), *hcur = hprev + kHist;
   (void)Lp;
@@ -448,7 +453,7 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
                 rng.x = (unsigned)__builtin_amdgcn_readlane((int)run_x, run_j + n - 1);
                 if (s0 == stM) {
                   if (sqto == 0) { sqto = i - 1; hmmto = k - 1; }
-                  if (lane < n) stk[i - 1 - lane] = (short)(k - 1 - lane);
+                  if (lane < n) stk_set(i - 1 - lane, k - 1 - lane);
                   i -= n; k -= n;
                   sqfrom = i; hmmfrom = k;
                 } else if (s0 == stD) {
@@ -583,8 +588,8 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
           else if (s1 == stM) {
             if (sqto == 0) { sqto = i; hmmto = k; }
             sqfrom = i; hmmfrom = k;
-            if (lane == 0) stk[i] = (short)k;
-          } else if (s1 == stI) { if (lane == 0) stk[i] = (short)-k; }
+            if (lane == 0) stk_set(i, k);
+          } else if (s1 == stI) { if (lane == 0) stk_set(i, -k); }
           else if (s1 == stB) {
             if (ndom < kDomMax) {
               if (lane == 0) { dom[4 * ndom] = sqfrom; dom[4 * ndom + 1] = sqto; dom[4 * ndom + 2] = hmmfrom; dom[4 * ndom + 3] = hmmto; }
@@ -614,8 +619,8 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
             for (int p0 = df; p0 <= dt; p0 += 64) {
               const int p = p0 + lane;
               const bool valid = p <= dt;
-              const int kk = valid ? (int)stk[p] : 0;
-              const int km = (valid && p > df) ? (int)stk[p - 1] : -32768, kp = (valid && p < dt) ? (int)stk[p + 1] : -32768;
+              const int kk = valid ? stk_get(p) : 0;
+              const int km = (valid && p > df) ? stk_get(p - 1) : INT_MIN, kp = (valid && p < dt) ? stk_get(p + 1) : INT_MIN;
               const bool isM = valid && kk > 0;
               nI += __builtin_popcountll(__ballot(valid && kk <= 0));
               const bool st = isM && km != kk - 1 && kk > 1, en = isM && kp != kk + 1;
@@ -660,7 +665,7 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
           // (two positions per lane and step: the reads of both are requested before either is used; a lane's
           // positions are still added in ascending order)
           for (int pos = df + lane; pos <= dt; pos += 128) {
-            const int kk0 = stk[pos], kk1 = pos + 64 <= dt ? stk[pos + 64] : 0;
+            const int kk0 = stk_get(pos), kk1 = pos + 64 <= dt ? stk_get(pos + 64) : 0;
             const bool has1 = pos + 64 <= dt;
             float4 v0[5], v1[5];
             const int nq4 = a.K == 4 ? 1 : 5;

@@ -1,4 +1,4 @@
-// Scoring kernel for models of 3 073 - 12 288 nodes: SEVERAL wavefronts per (query, HMM) pair.
+// Scoring kernel for models of 3 073 - 24 576 nodes: SEVERAL wavefronts per (query, HMM) pair.
 //
 // `hmmbuild --symfrac 0.0` (witch_msa/gcmm/algorithm.py:463-470) makes every populated backbone column a node, so
 // the upper subsets of a large backbone (16S: 5-12 k columns) exceed what ONE wavefront holds in registers
@@ -1301,6 +1301,16 @@ hipError_t launch_score_wide(int Q, const WideArgs &a, int blocks, int waves, si
       case 7: return launch_wide_t<kWideQReg2, 448, true>(a, blocks, waves, lds, s);
       case 8: return launch_wide_t<kWideQReg2, 512, true>(a, blocks, waves, lds, s);
       default: return launch_wide_t<kWideQReg2, 0, true>(a, blocks, waves, lds, s);   // WH_FORCE_WIDE=16 on small models
+    }
+  }
+  if (Q == kWideQBig && !a.em_lds) {
+    // 48 cells per lane, tables from L2: models of 12 289 - 24 576 nodes (five to eight waves)
+    switch (waves) {
+      case 5: return launch_wide_t<kWideQBig, 320, false>(a, blocks, waves, lds, s);
+      case 6: return launch_wide_t<kWideQBig, 384, false>(a, blocks, waves, lds, s);
+      case 7: return launch_wide_t<kWideQBig, 448, false>(a, blocks, waves, lds, s);
+      case 8: return launch_wide_t<kWideQBig, 512, false>(a, blocks, waves, lds, s);
+      default: return launch_wide_t<kWideQBig, 0, false>(a, blocks, waves, lds, s);   // WH_FORCE_WIDE=48 on smaller models
     }
   }
   if (Q != kWideQ || a.em_lds) return hipErrorInvalidValue;
