@@ -187,7 +187,8 @@ int wh_last_score_counters(wh_ehmm *e, int64_t *out8);
  * pairs as the calls score.  tests/test_gpu_parity.py draws its headline-size oracle samples per path from it. */
 int wh_set_path_buffer(wh_ehmm *e, uint8_t *d_paths);
 
-/* Scoring passes the last wh_score call REPEATED (0 or 1).  The queue that hands pairs with a multidomain region to the
+/* Scoring passes the last wh_score call REPEATED (0 to 2: the loop in wh_score_dev allows two repeats, and a pass repeated
+ * because a staged batch ran out of envelope units - WH_SCORE_KERNEL=10 / 11 - counts as well).  The queue that hands pairs with a multidomain region to the
  * resolver stage is sized by estimate (5 % of the pairs, or 1.25 x the largest share an earlier call on the handle
  * queued); a call that needs more slots counts them, grows the queue and scores once more - same results, about twice
  * the scoring time of that one call.  Negative: error. */

@@ -1,0 +1,238 @@
+// Internal header of the host side of libwitch_hip.so: what wh_api.hip (handles, options, getters, host-pointer entry
+// points), wh_host_score.hip (wh_score_dev) and wh_host_align.hip (wh_align_dev) share.  No kernel file includes it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <vector>
+
+#include "wh_launch.h"
+
+namespace wh {
+const char *last_error();
+}
+
+using namespace wh;
+
+#define HIPCHK(expr)                                                                  \
+  do {                                                                                \
+    hipError_t _e = (expr);                                                           \
+    if (_e != hipSuccess) {                                                           \
+      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+      return WH_EHIP;                                                                 \
+    }                                                                                 \
+  } while (0)
+
+struct DevBuf {
+  void *p = nullptr;
+  size_t cap = 0;
+  int ensure(size_t bytes) {
+    if (bytes <= cap) return WH_OK;
+    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+    size_t want = bytes + bytes / 8 + 256;
+    if (hipMalloc(&p, want) != hipSuccess) {
+      set_error("hipMalloc of %zu bytes failed", want);
+      return WH_ENOMEM;
+    }
+    cap = want;
+    return WH_OK;
+  }
+  void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
+};
+
+struct KernelTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  double ms = 0.0;
+  int launches = 0;
+  bool pending = false;
+};
+
+// Development knobs.  Read from the environment ONCE, at wh_ehmm_load;
+// wh_set_option changes them on a live handle (tools/ab_score.py).  None is needed in production.
+struct Knobs {
+  int kernel = 7;            // 7 phase-call scoring kernel (one query per wavefront); 8 its second compilation (A/B slot);
+                             // 9 two queries per wavefront where a batch fits (wh_score9.hip; measured slower, kept for A/B: DESIGN.md);
+                             // 10 staged launches (wh_staged.hip) for the size classes and batches they serve, 7 for the rest
+  float keep_scale = 0.f;    // Forward-row spill threshold relative to E(row); 0 = the kernel's default
+  int spill_band = 1;        // 0: envelope Forward rows stored at every lane block that passes keep_scale (A/B; the two-query kernel has no band)
+  int max_waves = 0;         // cap on waves per workgroup (0 = planner's choice)
+  bool force_specg = false;  // force the HBM special-state mode
+  bool no_logspace = false;  // skip the log-space alignment pass
+  bool no_wide_align = false; // models beyond 3 072 nodes are aligned by the float64 kernel only (A/B and debugging)
+  bool no_window = false;    // envelope Backward sweeps run full width (no node window; A/B and debugging)
+  bool no_p2win = false;     // the multihit Backward sweep runs full width only (A/B and debugging)
+  bool no_long_list = false; // WH_NO_LONG_LIST: pairs with more than WH_MAX_ENVELOPES regions keep WH_FLAG_TRUNC (no second pass; tests)
+  bool no_resolve = false;   // multidomain regions stay ONE envelope (round-1 behaviour) instead of HMMER's stochastic resolver
+  int rqueue_cap = 0;        // test hook: size the resolver's queue for this many pairs instead of the estimate (forces the overflow re-run)
+  int item_g = 0;            // queries per wave in a work item of the phase-call kernels (0 = 32; A/B)
+  int st_units = 0;          // staged launches: envelope units (Forward slabs) per batch (0 = sized from the free HBM)
+  bool stats = false, trace = false;
+  int dbg = 0;
+  int rdbg = 0;              // resolver: print the first <n> sampled segments and the cluster statistics of every region
+};
+
+// ---- d_counter: 256 ints in HBM, zeroed at load.  Every owner of a slot or range, in one place: the kernels and the
+// wh_last_* getters depend on these numbers.  [60..62], [68..79], [89..95], [124..127], [144..145], [147], [149..159]
+// and [176..255] are free.
+enum CounterSlot {
+  kSlotLaunch0 = 0,         // [0..59] work-queue heads of the launches of ONE call, in launch order: the one-wave scoring
+  kMaxLaunches = 60,        //   classes (wh_score_dev) or the alignment launches (wh_align_dev: both passes)
+  kSlotConsensus = 63,      // work-queue head of the consensus kernel
+  kSlotResolveCount = 64,   // resolver: length of the queue of pairs with a multidomain region ...
+  kSlotResolveWork = 65,    // ... and the work-queue head of the resolver launch (reset together)
+  kSlotGenericFront = 66,   // work-queue head of the float64 front end (main launch and long-list pass)
+  kSlotGenericAlign = 67,   // ... of the float64 alignment kernel
+  kSlotWideAlign = 80,      // [80..88] ... of the wide alignment launches, one per (cells per lane, waves) class
+  kWideAlignClasses = 9,
+  kSlotAlignStat = 96,      // [96..123] wh_align_dev: window statistics of the last call (AlignArgs::wstat), among them
+  kAlignStatInts = 28,
+  kSlotAlignCycles = 100,   //   [100..107] four 64-bit cycle counters (AlignArgs::wcyc)
+  kSlotScorePath = 128,     // [128..143] eight 64-bit counters of the last scoring call: six paths (wh_last_score_paths),
+  kScorePathInts = 16,      //   bytes of Forward rows stored, spare (wh_last_score_counters)
+  kSlotResolveErr = 146,    // queue records the resolver found in a segment of another model (never, for a well-formed segment list)
+  kSlotLongList = 148,      // pairs flagged WH_FLAG_TRUNC after the resolver (long-list pass)
+  kSlotWideScore = 160,     // [160..175] work-queue heads of the wide scoring launches, one per (cells per lane, waves) class
+  kWideScoreClasses = 16,   //   (13 exist: 12 x 5..8, 16 x 7..8, 24 x 6..8, 48 x 5..8; WH_FORCE_WIDE adds smaller workgroups of one of them)
+  kCounterInts = 256
+};
+static_assert(kSlotLaunch0 + kMaxLaunches <= kSlotConsensus && kSlotConsensus < kSlotResolveCount && kSlotResolveWork == kSlotResolveCount + 1 &&
+              kSlotResolveWork < kSlotGenericFront && kSlotGenericFront < kSlotGenericAlign && kSlotGenericAlign < kSlotWideAlign, "d_counter slots overlap");
+static_assert(kSlotWideAlign + kWideAlignClasses <= kSlotAlignStat && kSlotAlignCycles >= kSlotAlignStat && kSlotAlignCycles + 8 <= kSlotAlignStat + kAlignStatInts &&
+              kSlotAlignCycles % 2 == 0 && kSlotAlignStat + kAlignStatInts <= kSlotScorePath && kSlotScorePath % 2 == 0, "d_counter slots overlap");
+static_assert(kSlotScorePath + kScorePathInts <= kSlotResolveErr && kSlotResolveErr < kSlotLongList && kSlotLongList < kSlotWideScore &&
+              kSlotWideScore + kWideScoreClasses <= kCounterInts, "d_counter slots overlap or leave the buffer");
+
+struct wh_ehmm {
+  Knobs knobs;
+  int device = 0;
+  int alphabet = 0, K = 0, Kp = 0;
+  int cu_count = 256;
+  std::vector<HostHMM> hmms;
+  std::vector<DevHMM> dev;          // host copy of the descriptors
+  std::map<int, std::vector<int32_t>> by_q;   // Q class -> model positions
+  std::vector<int32_t> generic;               // models beyond the register-resident classes (wh_generic.hip)
+  std::vector<int32_t> generic_front;         // ... of them, those SCORED by the float64 front end (the others: wide_by_w)
+  std::map<int, std::vector<int32_t>> wide_by_w;   // cells per lane * 16 + waves per pair -> models scored by wh_score_wide.hip (3 073 - 24 576 nodes)
+  unsigned resolver_launches = 0;             // see ResolveArgs::launch_id
+  int force_wide_q = 0;                       // WH_FORCE_WIDE=<4|12|16|24|48>: cells per lane of every model's wide tables (tests)
+  bool force_wide = false;                    // WH_FORCE_WIDE: EVERY model is scored by the wide kernel (test hook)
+  DevBuf d_wscratch;                          // Forward slabs of the wide kernel's workgroups
+  DevBuf d_hmms, d_tables, d_nseq, d_index, d_lists, d_counter, d_scratch;
+  DevBuf d_ascratch;                        // per-wave slabs of the alignment kernels (allocated while the scoring kernels run)
+  DevBuf d_gtab, d_rrecs, d_rmx, d_rsegs;   // multidomain resolver: float64 tables, pair queue, matrix slabs, segment arrays
+  int last_resolved = 0;                    // pairs the resolver finished in the last wh_score call
+  int64_t last_long_list = 0;               // ... of them, pairs of the long-list pass (more than WH_MAX_ENVELOPES regions)
+  DevBuf d_tlist, d_rext;                   // long-list pass: pair positions, their region lists
+  int64_t rq_cap = 0;                       // records the queue of the current scoring call holds
+  double rq_rate = 0.0;                     // largest share of queued pairs any call on this handle has seen (sizes the next queue)
+  int64_t rq_floor = 0;                     // ... at least this many (set when a call overflowed its estimate; the call then runs again)
+  int last_queue_reruns = 0;                // scoring passes the last wh_score call repeated because its queue overflowed (0 to 2: the resolver's queue overflowed, or a staged batch ran out of envelope units)
+  // staged launches (wh_staged.hip): per-batch state in HBM
+  DevBuf d_p2bak;                           // 20- / 24-cell classes: P1's per-row arrays of every resident wave while its P2 window sweep works in place
+  DevBuf d_st_pairs, d_st_p1spec, d_st_units, d_st_p3spec, d_st_slabs, d_st_cnt;
+  double st_upp = 1.25;                     // envelope units per pair the next call's batches are sized for (learned: 1.25 x the largest seen)
+  int st_last_NB = 0;                       // pairs per batch of the last full-split class launch
+  bool st_off = false;                      // a batch of the current call ran out of units: the call is repeated with the fused kernel
+  int last_staged_batches = 0;              // batches the staged launches of the last scoring call went through
+  std::vector<int> st_cnt_host;             // the batches' counters of the last call (read back once, at the end of the scoring pass)
+  uint8_t *path_buf = nullptr;              // wh_set_path_buffer: device array [nq x H] the next scoring calls fill with WH_PATH_* bits
+  // staging for the host-pointer entry points
+  DevBuf s_res, s_off, s_deci, s_flags, s_fwd, s_det, s_idx, s_w, s_nk, s_nu, s_pq, s_ph, s_co, s_cols, s_pos;
+  DevBuf d_rkeys, d_rorder, d_rchunks, d_qorder, d_order, d_items, d_recs, d_spec, d_back, d_cwj, d_cwv, d_cwn, d_crow, c_buf[10];
+  uint32_t degen[32];
+  bool timing = false;
+  KernelTimer timers[5];
+  int max_M = 0;
+  int max_Q = 4;                              // largest cells-per-lane of any model (sizes the float64 slabs)
+  int last_align_redo = 0;          // pairs of the last wh_align call that went through the log-space pass
+  int last_align_unaligned = 0;     // ... that the any-size kernel could not align (float64 range)
+  int64_t last_align_paths[4] = {0, 0, 0, 0};   // pairs of the last wh_align call: 256-node window, window rejected, no window, 512-node window
+  std::vector<int64_t> last_unaligned_pairs;   // their pair numbers (wh_last_align_status)
+  // timing only: one event in front of every scoring launch of the last call (+ one behind the last), its cells-per-lane class
+  // and kernel family (0 phase-call, 1 pass-synchronous, 2 any-size front end): wh_last_score_launches
+  std::vector<hipEvent_t> cls_ev;
+  std::vector<int> cls_q, cls_kind;
+  int cls_n = 0;
+  int *counter(int slot) const { return (int *)d_counter.p + slot; }      // a slot of the table above
+};
+
+// one event per scoring launch (timing mode only); events are created once and reused
+static inline int class_mark(wh_ehmm *e, hipStream_t s, int Q, int kind) {
+  if (!e->timing) return WH_OK;
+  if ((int)e->cls_ev.size() <= e->cls_n) { hipEvent_t ev; HIPCHK(hipEventCreate(&ev)); e->cls_ev.push_back(ev); e->cls_q.push_back(0); e->cls_kind.push_back(0); }
+  HIPCHK(hipEventRecord(e->cls_ev[(size_t)e->cls_n], s));
+  e->cls_q[(size_t)e->cls_n] = Q; e->cls_kind[(size_t)e->cls_n] = kind;
+  e->cls_n++;
+  return WH_OK;
+}
+
+static inline int timer_begin(wh_ehmm *e, int which, hipStream_t s) {
+  KernelTimer &t = e->timers[which];
+  t.pending = false; t.ms = 0.0; t.launches = 0;
+  if (!e->timing) return WH_OK;
+  if (!t.e0) { HIPCHK(hipEventCreate(&t.e0)); HIPCHK(hipEventCreate(&t.e1)); }
+  HIPCHK(hipEventRecord(t.e0, s));
+  return WH_OK;
+}
+static inline int timer_end(wh_ehmm *e, int which, hipStream_t s, int launches) {
+  KernelTimer &t = e->timers[which];
+  t.launches = launches;
+  if (!e->timing) return WH_OK;
+  HIPCHK(hipEventRecord(t.e1, s));
+  t.pending = true;
+  return WH_OK;
+}
+
+static const size_t kLdsBudget = 160 * 1024 - 512;
+static const size_t kLdsHeader = 16;   // work-item slot in front of the tables (keeps them 16-byte aligned)
+static inline int row_stride(int Lc) { return (Lc + 1 + 3) / 4 * 4; }        // floats of one per-row array: rows 0..Lc, 16-byte multiple
+static inline int residue_words(int Lc) { return (Lc + 3) / 4 + 4; }         // words of a wave's residue buffer
+// LDS of a workgroup: <header> bytes, the model's tables, <w> wave blocks of <wave_words> words; and the most waves (from
+// <w> down, 0 = none) of which <per_cu> such workgroups fit a CU.  (The alignment planner tests without the header.)
+static inline size_t lds_bytes(size_t header, size_t table, int w, int wave_words) { return header + table + (size_t)w * wave_words * sizeof(float); }
+static inline int fit_waves(size_t header, size_t table, int w, int wave_words, int per_cu = 1) {
+  while (w >= 1 && per_cu * lds_bytes(header, table, w, wave_words) > kLdsBudget) w--;
+  return w;
+}
+// Long models (pass-synchronous scoring and alignment): ONE orientation resident, four waves - one per SIMD, the kernel
+// uses the whole register file; the emission rows beside it where they fit (Klds = K), else read from L2 (Klds = 0).
+static inline bool plan_long_model(int Q, int K, int wave_words, int *Klds, size_t *lds) {
+  *Klds = K;
+  size_t table = (size_t)(K + 8) * Q * kWave * sizeof(float);
+  if (lds_bytes(kLdsHeader, table, 4, wave_words) > kLdsBudget) { *Klds = 0; table = (size_t)8 * Q * kWave * sizeof(float); }
+  *lds = lds_bytes(kLdsHeader, table, 4, wave_words);
+  return *lds <= kLdsBudget;
+}
+
+// Resident workgroups are capped so that <per_block> bytes of per-wave workspace each fit in
+// about 70 % of the free HBM (the work-item counter loops tolerate fewer workgroups than CUs).
+// -1 when not even ONE workgroup's workspace fits (the buffer <have> counts as free: it is given
+// back first): the error names the model length, the query length cap and the figures, and the
+// caller refuses the call with WH_ENOMEM before it launches anything more.
+// (<M> is the longest model's node count, or for the consensus kernel (<backbone>) the backbone's column count)
+static inline bool one_block_fits(size_t per_block, const DevBuf &have, int M, int Lcap, const char *what, bool backbone = false) {
+  if (per_block <= have.cap) return true;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return true;     // (the allocation itself will say)
+  if (per_block <= free_b + have.cap) return true;
+  set_error("%s: the workspace of one workgroup does not fit on the device (%s %d %s, queries of up to %d residues: "
+            "%zu bytes per workgroup, %zu bytes free)", what, backbone ? "a backbone of" : "models of up to", M, backbone ? "columns" : "nodes",
+            Lcap, per_block, free_b + have.cap);
+  return false;
+}
+static inline int clamp_blocks(int blocks, size_t per_block, const DevBuf &have, int M, int Lcap, const char *what, bool backbone = false) {
+  if (blocks < 1 || per_block == 0) return blocks;
+  if ((size_t)blocks * per_block <= have.cap) return blocks;
+  if (!one_block_fits(per_block, have, M, Lcap, what, backbone)) return -1;
+  if (blocks == 1) return blocks;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return blocks;
+  const size_t budget = (size_t)((double)(free_b + have.cap) * 0.7);
+  const size_t fit = budget / per_block;
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)blocks, fit));
+}
