@@ -51,11 +51,15 @@ constexpr int kSpML = SP_ML, kSpMH = SP_MH, kSpArr = SP_NARR;
 #endif
 constexpr bool kMaskedAcc = true;   // P4: only lanes that own a stored Forward block accumulate
 
+// log() / exp() in double, out of line: inlined, each call site left its polynomial's constants in registers that the kernel then
+// kept alive across every sweep of a pair (the same instructions either way)
+__device__ __noinline__ static double dlog(double x) { return log(x); }
+__device__ __noinline__ static double dexp(double x) { return exp(x); }
 __device__ __forceinline__ float flogsum0_v7(float b) {
   const float mx = b > 0.f ? b : 0.f, mn = b > 0.f ? 0.f : b;
   if (mn == -INFINITY || (mx - mn) >= 15.7f) return mx;
   const int idx = (int)((mx - mn) * 1000.0f);
-  return mx + (float)log(1.0 + exp((double)-idx / 1000.0));
+  return mx + (float)dlog(1.0 + dexp((double)-idx / 1000.0));
 }
 
 // what every sweep needs to find its tables and its per-wave LDS block
@@ -90,10 +94,18 @@ static_assert(sizeof(WaveCtx) <= 80, "WaveCtx must stay register-passed (see com
 __device__ __forceinline__ int ctxK(const WaveCtx &c) { return c.alpha & 255; }
 __device__ __forceinline__ int ctxKp(const WaveCtx &c) { return (c.alpha >> 8) & 255; }
 __device__ __forceinline__ int ctxKlds(const WaveCtx &c) { return (c.alpha >> 16) & 255; }
+// a value every lane of the wave holds alike, moved to scalar registers: it then survives a sweep's call without a vector register
+__device__ __forceinline__ float uniform_f(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x))); }
+__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+  return (int64_t)(((unsigned long long)hi << 32) | lo);
+}
 struct P4Out { float mass, domcorr; };
 struct RegOut { int nenv, nreg, flags; };   // flags: WH_FLAG_* | multidomain mask of the stored regions << 8 (12 bytes: stays in return registers)
 
 struct FwdOut { float xC; int ef; int nst; };      // C(L), its scale exponent; STORE: lane blocks the sweep stored (rows x kept lanes)
+// (every member is the same in all lanes: sums over the wave and scalar counts)
+__device__ __forceinline__ FwdOut uniform_fwd(FwdOut o) { return FwdOut{uniform_f(o.xC), __builtin_amdgcn_readfirstlane(o.ef), __builtin_amdgcn_readfirstlane(o.nst)}; }
 
 // ---------------------------------------------------------------- P1 / P3
 // (the sweep without STORE is the multihit one, P1: it also leaves the dominant-path mask in n2tab[30..31] for P2's window)
@@ -1033,7 +1045,7 @@ __device__ __forceinline__ void assemble_score(int L, int Ld_tot, float seqbias_
   float pre_score = (float)(((double)fwdsc - (double)nullsc) / LOG2);
   float seq_score = (float)(((double)fwdsc - (double)(nullsc + seqbias)) / LOG2);
   sb2 = flogsum0_v7(lomega + sb2);
-  sum_score += (float)((double)(L - Ld_tot) * log((double)((float)L / (float)(L + 3))));
+  sum_score += (float)((double)(L - Ld_tot) * dlog((double)((float)L / (float)(L + 3))));
   const float pre2 = (float)(((double)sum_score - (double)nullsc) / LOG2);
   sum_score = (float)(((double)sum_score - (double)(nullsc + sb2)) / LOG2);
   if (Ld_tot > 0 && sum_score > seq_score) { seq_score = sum_score; pre_score = pre2; flags |= WH_FLAG_OVERRIDE; }
@@ -1095,16 +1107,16 @@ __device__ __forceinline__ float envelope_attempts(const ScoreArgs &a, WaveCtx &
 #pragma unroll 1
   for (int attempt = first; attempt < 3; attempt++) {
     const float keep_scale = attempt < 2 ? (a.keep_scale > 0.f ? a.keep_scale : kKeepScale7) : -1.0f;
-    const FwdOut f3 = sweep_forward<Q, true, TH, SG>(c, (lds_u8 *)eseq, Ld, cu, keep_scale, attempt == 0 ? band : kAllLanes);
+    const FwdOut f3 = uniform_fwd(sweep_forward<Q, true, TH, SG>(c, (lds_u8 *)eseq, Ld, cu, keep_scale, attempt == 0 ? band : kAllLanes));
     ec.spill += (unsigned long long)f3.nst * (8 * Q);
     // the rows were written by other lanes of this wave: order the stores before the loads
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    envsc = (float)((double)f3.ef * LOG2 + log((double)(f3.xC * cu.move)));
+    envsc = uniform_f((float)((double)f3.ef * LOG2 + dlog((double)(f3.xC * cu.move))));
     domcorr = 0.f;
     if (!(f3.xC > 0.f)) break;
     WH_TICK7(7);
     const P4Out p4 = envelope_backward<Q, TH, SG>(a, c, eseq, Ld, cu, f3, attempt == 2, false, ec, lane, attempt == 0 ? band : kAllLanes);
-    domcorr = p4.domcorr;
+    domcorr = uniform_f(p4.domcorr);
     WH_TICK7(8);
     if (attempt < 2 && !(fabsf((float)Ld - p4.mass) <= spill_tol(attempt == 0) * (float)Ld)) continue;
     if (attempt == 2) flags |= WH_FLAG_EXACT;
@@ -1239,7 +1251,7 @@ __global__ __launch_bounds__(TH) void score_kernel7(ScoreArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem_raw[];
   volatile int *s_item_p = reinterpret_cast<volatile int *>(smem_raw);
   float *smem = smem_raw + 4;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nwaves = blockDim.x >> 6;
   constexpr int TBL = Q * kWave;
   float *emL = smem;
   float *trL = smem + (size_t)a.K * TBL;
@@ -1267,9 +1279,9 @@ __global__ __launch_bounds__(TH) void score_kernel7(ScoreArgs a) {
     __syncthreads();                       // every wave has left the previous item's deal: its counter may be reset
     if (threadIdx.x == 0) { *s_item_p = atomicAdd(a.counter, 1); s_item_p[1] = 0; }
     __syncthreads();
-    const int item = *s_item_p;
+    const int item = __builtin_amdgcn_readfirstlane(*s_item_p);
     if (item >= a.n_items) break;
-    const int h = a.hmm_list[item / a.n_qblocks];
+    const int h = __builtin_amdgcn_readfirstlane(a.hmm_list[item / a.n_qblocks]);
     const int64_t q_lo = (int64_t)(item % a.n_qblocks) * a.QB;
     const int64_t q_hi = q_lo + a.QB < a.nq ? q_lo + a.QB : a.nq;
     if (h != cur_h) {
@@ -1296,9 +1308,9 @@ __global__ __launch_bounds__(TH) void score_kernel7(ScoreArgs a) {
       if (lane == 0) k_ = atomicAdd(const_cast<int *>(s_item_p) + 1, 1);
       const int64_t qpos = q_lo + __builtin_amdgcn_readfirstlane(k_);
       if (qpos >= q_hi) break;
-      const int64_t qi = a.qorder ? a.qorder[qpos] : qpos;
-      const int64_t off = a.offsets[qi];
-      const int L = (int)(a.offsets[qi + 1] - off);
+      const int64_t qi = a.qorder ? uniform_i64(a.qorder[qpos]) : qpos;
+      const int64_t off = uniform_i64(a.offsets[qi]);
+      const int L = __builtin_amdgcn_readfirstlane((int)(a.offsets[qi + 1] - off));
       const size_t out = (size_t)qi * a.H + h;
       int flags = 0, decibits = 0;
       float fwd_bits_out = -INFINITY;
@@ -1316,12 +1328,12 @@ __global__ __launch_bounds__(TH) void score_kernel7(ScoreArgs a) {
         long long t_last = a.stats ? __builtin_readcyclecounter() : 0;
         // ---------------- P1
         const LenCfg cm = len_config(L, true);
-        const FwdOut f1 = sweep_forward<Q, false, TH, SG>(c, (lds_u8 *)seq, L, cm, 0.f);
-        const double fwd_nats = (double)f1.ef * LOG2 + log((double)(f1.xC * cm.move));
-        const float fwdsc = (float)fwd_nats;
+        const FwdOut f1 = uniform_fwd(sweep_forward<Q, false, TH, SG>(c, (lds_u8 *)seq, L, cm, 0.f));
+        const double fwd_nats = (double)f1.ef * LOG2 + dlog((double)(f1.xC * cm.move));
+        const float fwdsc = uniform_f((float)fwd_nats);
         const float p1 = (float)L / (float)(L + 1);
-        const float nullsc = (float)((double)(float)L * log((double)p1) + log(1.0 - (double)p1));
-        fwd_bits_out = (float)((fwd_nats - (double)nullsc) / LOG2);
+        const float nullsc = uniform_f((float)((double)(float)L * dlog((double)p1) + dlog(1.0 - (double)p1)));
+        fwd_bits_out = uniform_f((float)((fwd_nats - (double)nullsc) / LOG2));
         if (dp) dp->fwd_bits = fwd_bits_out;
         if (f1.xC > 0.f && isfinite(fwdsc)) {
           WH_TICK7(4);
@@ -1469,10 +1481,10 @@ __global__ __launch_bounds__(TH) void score_kernel7q(ScoreArgs a) {
           long long t_last = a.stats ? __builtin_readcyclecounter() : 0;
           const LenCfg cm = len_config(L, true);
           const FwdOut f1 = sweep_forward<Q, false, TH, false>(c, (lds_u8 *)seq, L, cm, 0.f);
-          const double fwd_nats = (double)f1.ef * LOG2 + log((double)(f1.xC * cm.move));
+          const double fwd_nats = (double)f1.ef * LOG2 + dlog((double)(f1.xC * cm.move));
           const float fwdsc = (float)fwd_nats;
           const float p1 = (float)L / (float)(L + 1);
-          const float nullsc = (float)((double)(float)L * log((double)p1) + log(1.0 - (double)p1));
+          const float nullsc = (float)((double)(float)L * dlog((double)p1) + dlog(1.0 - (double)p1));
           fwd_bits_out = (float)((fwd_nats - (double)nullsc) / LOG2);
           if (dp) dp->fwd_bits = fwd_bits_out;
           if (f1.xC > 0.f && isfinite(fwdsc)) {
@@ -1494,7 +1506,7 @@ __global__ __launch_bounds__(TH) void score_kernel7q(ScoreArgs a) {
               const FwdOut f3 = sweep_forward<Q, true, TH, false>(c, (lds_u8 *)eseq, Ld, cu, keep_scale, band);
               ec.spill += (unsigned long long)f3.nst * (8 * Q);
               __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-              const float envsc = (float)((double)f3.ef * LOG2 + log((double)(f3.xC * cu.move)));
+              const float envsc = (float)((double)f3.ef * LOG2 + dlog((double)(f3.xC * cu.move)));
               WH_TICK7(7);
               float domcorr = 0.f;
               bool done = !(f3.xC > 0.f);
