@@ -55,7 +55,7 @@ extern "C" {
 #define WH_FLAG_REPORTED  1   /* pair appears in hmmsearch's per-sequence table          */
 #define WH_FLAG_MULTI     2   /* a region was multidomain (HMMER's stochastic class)     */
 #define WH_FLAG_OVERRIDE  4   /* reconstruction score overrode the Forward score         */
-#define WH_FLAG_TRUNC     8   /* a list of the pair overflowed and part of it was dropped: see below       */
+#define WH_FLAG_TRUNC     8   /* part of the pair was left out of its score (never for a well-formed call: see below) */
 #define WH_FLAG_EXACT    16   /* an envelope failed the sparse-spill certificate and was redone dense */
 
 /* Envelopes a wh_pair_detail record LISTS.  The SCORE of a pair has no such limit (hmmsearch has none: SURVEY A.4, called at
@@ -63,9 +63,13 @@ extern "C" {
  * time inside the same call by the long-list pass (float64 front end with the region list in HBM + a resolver launch of
  * its own; wh_last_score_counters out8[7] counts such pairs), every region and every envelope enters its score, and it
  * comes back WITHOUT WH_FLAG_TRUNC; its detail record lists the first WH_MAX_ENVELOPES envelopes, nregions is the full
- * count.  What can still set WH_FLAG_TRUNC: ONE multidomain region with more than 32 domains in a sampled trace or more
- * than 64 significant clusters (tandem repeats of up to 28 copies are tested), more than four million overflowing pairs
- * in one call, or the development knobs WH_NO_LONG_LIST / WH_NO_RESOLVE. */
+ * count.  Nor is there a limit INSIDE a multidomain region: the resolver keeps 32 domains of a sampled trace, 8 192
+ * sampled segments and 64 significant clusters of a region in fixed lists; a region that needs more (a tandem repeat of
+ * more than 32 copies) is counted to the end, and its pair is scored again inside the same call by the big-region pass -
+ * the same resolver with those lists in HBM, sized from the counts (wh_last_region_overflow).  What can still set
+ * WH_FLAG_TRUNC: a malformed record in the resolver's queue (an internal error; a region outside its sequence), more
+ * than four million pairs for the long-list pass in one call, or the development knobs WH_NO_LONG_LIST /
+ * WH_NO_BIG_REGION / WH_NO_RESOLVE.  The value stays 8 for binary compatibility. */
 #define WH_MAX_ENVELOPES 16
 
 /* Which code path a pair took through the scoring kernels (optional per-pair byte, wh_set_path_buffer; written by
@@ -180,6 +184,11 @@ int wh_last_score_paths(wh_ehmm *e, int64_t *paths6);
  * line (one-wavefront-per-pair kernels only).  out8[7] = pairs of the last call that went through the long-list pass
  * (more regions than WH_MAX_ENVELOPES; see there). */
 int wh_last_score_counters(wh_ehmm *e, int64_t *out8);
+/* The big-region pass of the last scoring call: out4[0] = pairs it scored again because one multidomain region needed
+ * longer lists than the resolver's fixed ones (see WH_MAX_ENVELOPES), out4[1] = the most domains in one sampled trace,
+ * [2] = the most sampled segments and [3] = the most significant clusters of such a region (0 where that list was long
+ * enough).  All 0: no pair went through the pass, which then cost nothing beyond four ints in the call's one read-back. */
+int wh_last_region_overflow(wh_ehmm *e, int64_t *out4);
 
 /* Optional per-PAIR record of the same: a device array of nq x H bytes that the scoring calls made after this one fill
  * with WH_PATH_* bits (NULL switches it off again).  Written by the staged launches only (WH_SCORE_KERNEL=10; pairs

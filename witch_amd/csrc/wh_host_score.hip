@@ -692,13 +692,10 @@ static int print_resolver_stats(const ScoreCall &c, const ResolveArgs &r, int n_
   return WH_OK;
 }
 
-// one resolver launch (wh_resolve.hip, one wavefront per queued pair) over the first <n_multi> records of the queue;
-// <rext>: the long-list pass, whose records keep their regions in HBM
-static int resolve_queue(const ScoreCall &c, int n_multi, const int32_t *rext, int64_t rext_stride, int *rlaunches) {
+// what every resolver launch of a call shares: tables, queue, outputs, the layout of a wave's matrix slab
+static ResolveArgs resolve_args(const ScoreCall &c, const int32_t *rext, int64_t rext_stride) {
   wh_ehmm *e = c.e;
-  hipStream_t s = c.s;
   const int Lc = c.Lc, Qmax = e->max_Q;
-  const size_t rlds = resolve_lds_bytes(Lc, e->max_M);
   ResolveArgs r;
   memset(&r, 0, sizeof r);
   r.rext = rext; r.rext_stride = rext_stride;
@@ -720,6 +717,108 @@ static int resolve_queue(const ScoreCall &c, int n_multi, const int32_t *rext, i
   r.launch_id = ++e->resolver_launches;
   r.err = e->counter(kSlotResolveErr);
   r.null2_gather = c.res_null2_gather ? 1 : 0;
+  return r;
+}
+
+// the big-region block of the counters (wh_launch.h: kBigAfterErr) in front of a resolver launch: counts zeroed, the list
+// the launch appends to (<cap> 0: none)
+static int big_region_block(const ScoreCall &c, int32_t *list, int cap) {
+  int *blk = c.e->big_blk;                 // (lives in the handle: the copy needs no synchronisation)
+  for (int t = 0; t < 8; t++) blk[t] = 0;
+  blk[4] = cap;
+  memcpy(blk + 5, &list, sizeof list);
+  static_assert(sizeof list == 2 * sizeof(int), "the list's address takes two ints");
+  HIPCHK(hipMemcpyAsync(c.e->counter(kSlotBigRegion), blk, 8 * sizeof(int), hipMemcpyHostToDevice, c.s));
+  return WH_OK;
+}
+
+// ---- the big-region pass.  The resolver keeps the domains of a sampled trace (32), the significant clusters (64) and the
+// sampled segments (8 192) of a region in lists of fixed length: LDS and a small HBM block per wave, eight waves per CU.
+// hmmsearch has no such limit (a tandem repeat of 96 copies is ONE region of 96 domains per trace, 19 200 segments, 96
+// clusters).  A launch counts what such a region needs and lists the pair; this pass runs the listed pairs again with every
+// list in HBM, sized from the counts: few waves (one per workgroup) with large blocks.
+struct BigRegionPlan {
+  int dom_cap, seg_cap, clus_cap;     // entries per wave
+  size_t seg_ints;                    // 4-byte units of a wave's list block
+};
+// counts = (pairs, most domains of a trace, most segments, most significant clusters of a region) as a launch recorded them.
+// A count of 0 means that list was long enough.  A significant cluster holds segments of at least 25 % of the 200 traces,
+// so seg_cap / 50 clusters are enough whatever the (truncated) first clustering counted.
+static BigRegionPlan plan_big_regions(int Lc, int max_M, const int counts[4]) {
+  BigRegionPlan p;
+  p.dom_cap = std::max(resolve_dom_max(), (counts[1] + 63) & ~63);
+  p.seg_cap = std::max(resolve_seg_cap(), (counts[2] + 255) & ~255);
+  p.clus_cap = std::max(std::max(resolve_clus_max(), counts[3]), p.seg_cap / 50 + 1);
+  p.seg_ints = (resolve_big_seg_ints(Lc, max_M, p.dom_cap, p.seg_cap, p.clus_cap) + 3) & ~(size_t)3;
+  return p;
+}
+
+// <n_big> queue positions are listed in the first half of d_biglist; <counts> as read back with them.  The queue itself
+// (d_rrecs, <rext>) is the one of the launch that listed them.
+static int big_region_pass(const ScoreCall &c, const int counts_in[4], const int32_t *rext, int64_t rext_stride, int list_cap, int *rlaunches) {
+  wh_ehmm *e = c.e;
+  hipStream_t s = c.s;
+  const int Lc = c.Lc;
+  int counts[4] = {counts_in[0], counts_in[1], counts_in[2], counts_in[3]};
+  e->last_big[0] += std::min(counts[0], list_cap);
+  const size_t rlds = resolve_lds_bytes(Lc, e->max_M);
+  for (int again = 0; counts[0] > 0; again++) {
+    for (int t = 1; t < 4; t++) e->last_big[t] = std::max<int64_t>(e->last_big[t], counts[t]);
+    if (again == 2) { set_error("wh_score_dev: a region's lists (%d domains, %d segments, %d clusters) were too short twice", counts[1], counts[2], counts[3]); return WH_ERANGE; }
+    const int n_big = std::min(counts[0], list_cap);
+    ResolveArgs r = resolve_args(c, rext, rext_stride);
+    const BigRegionPlan p = plan_big_regions(Lc, e->max_M, counts);
+    r.dom_cap = p.dom_cap; r.seg_cap = p.seg_cap; r.clus_cap = p.clus_cap; r.seg_stride = p.seg_ints;
+    r.lds_tables = 0;
+    r.wave_lds_ints = (int)(rlds / 4);
+    const size_t lds_total = resolve_lds_header_bytes(0) + rlds;
+    // one segment of mixed models in the order of the list, one slot per workgroup
+    int blocks = std::min(n_big, e->cu_count);
+    const size_t per_block = r.mx_stride * sizeof(double) + r.seg_stride * sizeof(int32_t);
+    blocks = clamp_blocks(blocks, per_block, e->d_rmx, e->max_M, Lc, "big-region pass");
+    if (blocks < 0) return WH_ENOMEM;
+    if (e->d_rmx.ensure((size_t)blocks * r.mx_stride * sizeof(double)) || e->d_bigsegs.ensure((size_t)blocks * r.seg_stride * sizeof(int32_t))) {
+      set_error("big-region pass: %d workgroups x %zu bytes (lists of %d domains, %d segments, %d clusters) do not fit on the device", blocks, per_block, p.dom_cap, p.seg_cap, p.clus_cap);
+      return WH_ENOMEM;
+    }
+    r.mx = (double *)e->d_rmx.p; r.segs = (int32_t *)e->d_bigsegs.p;
+    std::vector<int32_t> plan((size_t)4 + blocks + 1, 0);
+    plan[1] = n_big; plan[2] = -1;
+    if (e->d_rchunks.ensure(sizeof(int32_t) * plan.size())) return WH_ENOMEM;
+    int32_t *d_chunks = (int32_t *)e->d_rchunks.p;
+    HIPCHK(hipMemcpyAsync(d_chunks, plan.data(), sizeof(int32_t) * plan.size(), hipMemcpyHostToDevice, s));
+    r.chunks = d_chunks; r.n_chunks = 1; r.slots = d_chunks + 4; r.n_slots = blocks; r.cursors = d_chunks + 4 + blocks;
+    int32_t *lists = (int32_t *)e->d_biglist.p;
+    r.order = lists + (size_t)(again & 1) * list_cap;
+    HIPCHK(hipMemsetAsync(r.counter, 0, sizeof(int), s));
+    if (int rc = big_region_block(c, lists + (size_t)((again + 1) & 1) * list_cap, list_cap)) return rc;
+    HIPCHK(hipStreamSynchronize(s));     // <plan> is a local
+    if (e->knobs.trace) fprintf(stderr, "[wh] big-region pass: %d pairs, lists of %d domains per trace, %d segments, %d clusters: %d workgroups of one wave, %zu KB of lists + %zu MB of matrix per wave\n",
+                                n_big, p.dom_cap, p.seg_cap, p.clus_cap, blocks, r.seg_stride * 4 >> 10, r.mx_stride * 8 >> 20);
+    const auto t0 = std::chrono::steady_clock::now();
+    hipError_t err = launch_resolve(r, blocks, 1, lds_total, s);
+    if (err != hipSuccess) { set_error("big-region resolve kernel launch failed: %s", hipGetErrorString(err)); return WH_EHIP; }
+    (*rlaunches)++;
+    HIPCHK(hipMemcpyAsync(counts, e->counter(kSlotBigRegion), sizeof counts, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int t = 1; t < 4; t++) e->last_big[t] = std::max<int64_t>(e->last_big[t], counts[t]);
+    if (e->knobs.trace) fprintf(stderr, "[wh] big-region pass: %.1f ms (host clock around launch + synchronize)%s\n",
+                                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), counts[0] > 0 ? "; lists still too short, once more" : "");
+  }
+  return WH_OK;
+}
+
+// one resolver launch (wh_resolve.hip, one wavefront per queued pair) over the first <n_multi> records of the queue;
+// <rext>: the long-list pass, whose records keep their regions in HBM.  Pairs with a region beyond the launch's lists are
+// counted in d_counter[kSlotBigRegion ..] and listed in d_biglist (unless WH_NO_BIG_REGION): the caller reads the count.
+static int resolve_queue(const ScoreCall &c, int n_multi, const int32_t *rext, int64_t rext_stride, int *rlaunches) {
+  wh_ehmm *e = c.e;
+  hipStream_t s = c.s;
+  const int Lc = c.Lc;
+  const size_t rlds = resolve_lds_bytes(Lc, e->max_M);
+  ResolveArgs r = resolve_args(c, rext, rext_stride);
+  if (!e->knobs.no_big_region && e->d_biglist.ensure(2 * sizeof(int32_t) * (size_t)n_multi)) return WH_ENOMEM;
+  if (int rc = big_region_block(c, e->knobs.no_big_region ? nullptr : (int32_t *)e->d_biglist.p, e->knobs.no_big_region ? 0 : n_multi)) return rc;
   if (int rc = stats_begin(c, 256, 16, &r.stats)) return rc;
   if (r.stats) HIPCHK(hipStreamSynchronize(s));
   // ---- launch geometry: ONE workgroup of up to eight waves per CU.  Models of up to 16 cells per lane get their
@@ -801,20 +900,28 @@ static int resolve_queue(const ScoreCall &c, int n_multi, const int32_t *rext, i
 // sequence of this length can have, then a resolver launch of its own that reads the regions from that list and sums
 // over all envelopes.  Costs one pass over the flags (a byte per pair) and one 4-byte read-back per call; the float64
 // kernels run only when a pair needs them.
-static int long_list_pass(const ScoreCall &c, int *rlaunches) {
+// <n_multi>: length of the main launch's queue, whose big-region counters come back with this pass's own count (ONE
+// 4-byte-sized read-back per call for both); <long_list> false: only that.
+static int long_list_pass(const ScoreCall &c, int n_multi, bool long_list, int *rlaunches) {
   wh_ehmm *e = c.e;
   hipStream_t s = c.s;
   const int Lc = c.Lc;
   int *d_tcount = e->counter(kSlotLongList);
   const int list_cap = (int)std::min<int64_t>(c.npairs_all, (int64_t)1 << 22);
-  if (e->d_tlist.ensure(sizeof(int64_t) * (size_t)list_cap)) return WH_ENOMEM;
   HIPCHK(hipMemsetAsync(d_tcount, 0, sizeof(int), s));
-  hipError_t terr = launch_trunc_list(c.d_flags, c.npairs_all, d_tcount, (int64_t *)e->d_tlist.p, list_cap, s);
-  if (terr != hipSuccess) { set_error("flag scan launch failed: %s", hipGetErrorString(terr)); return WH_EHIP; }
-  int n_trunc = 0;
-  HIPCHK(hipMemcpyAsync(&n_trunc, d_tcount, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (long_list) {
+    if (e->d_tlist.ensure(sizeof(int64_t) * (size_t)list_cap)) return WH_ENOMEM;
+    // (a pair the resolver could not finish is not flagged: it is in the big-region list, so what is flagged here has
+    // more regions than WH_MAX_ENVELOPES)
+    hipError_t terr = launch_trunc_list(c.d_flags, c.npairs_all, d_tcount, (int64_t *)e->d_tlist.p, list_cap, s);
+    if (terr != hipSuccess) { set_error("flag scan launch failed: %s", hipGetErrorString(terr)); return WH_EHIP; }
+  }
+  int back[5] = {0, 0, 0, 0, 0};                  // long-list count | big-region count and the three largest list lengths
+  HIPCHK(hipMemcpyAsync(back, d_tcount, (n_multi > 0 ? 5 : 1) * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  n_trunc = std::min(n_trunc, list_cap);          // (beyond four million such pairs in one call the rest stay flagged)
+  // the main launch's big regions first: its queue is still in place (the rounds below overwrite it)
+  if (back[1] > 0 && !e->knobs.no_big_region) if (int rc = big_region_pass(c, back + 1, nullptr, 0, n_multi, rlaunches)) return rc;
+  const int n_trunc = std::min(back[0], list_cap);          // (beyond four million such pairs in one call the rest stay flagged)
   if (n_trunc <= 0) return WH_OK;
   // a region is at least two rows long (the row that triggers it and a later one that ends it)
   const int ext_cap = Lc / 2 + 2;
@@ -846,6 +953,13 @@ static int long_list_pass(const ScoreCall &c, int *rlaunches) {
     HIPCHK(hipStreamSynchronize(s));
     if (int rc = resolve_queue(c, n_round, (const int32_t *)e->d_rext.p, rext_stride, rlaunches)) return rc;
     e->last_long_list += n_round;
+    if (!e->knobs.no_big_region) {
+      // (a pair with many regions can have a big one among them; this read-back is paid by calls that have such pairs only)
+      int big[4] = {0, 0, 0, 0};
+      HIPCHK(hipMemcpyAsync(big, e->counter(kSlotBigRegion), sizeof big, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      if (big[0] > 0) if (int rc = big_region_pass(c, big, (const int32_t *)e->d_rext.p, rext_stride, n_round, rlaunches)) return rc;
+    }
   }
   return WH_OK;
 }
@@ -876,7 +990,9 @@ static int resolver_stage(const ScoreCall &c, bool *overflow, int *rlaunches) {
   }
   if (n_multi > 0) if (int rc = resolve_queue(c, n_multi, nullptr, 0, rlaunches)) return rc;
   e->last_long_list = 0;
-  if (c.resolve && generic_lds_bytes(c.Lc) <= kLdsBudget && !e->knobs.no_long_list) return long_list_pass(c, rlaunches);
+  for (int64_t &v : e->last_big) v = 0;
+  const bool long_list = c.resolve && generic_lds_bytes(c.Lc) <= kLdsBudget && !e->knobs.no_long_list;
+  if (long_list || (n_multi > 0 && !e->knobs.no_big_region)) return long_list_pass(c, n_multi, long_list, rlaunches);
   return WH_OK;
 }
 
@@ -955,6 +1071,8 @@ extern "C" int wh_score_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t
   // pair that wants a slot; when the count exceeds the capacity, the queue is grown to the count and the scoring pass
   // runs once more (every pair is scored again, so the queue then holds exactly what the first pass counted).
   e->last_queue_reruns = 0;
+  e->last_long_list = 0;
+  for (int64_t &v : e->last_big) v = 0;
   e->rq_floor = 0;
   e->st_off = false;
   // (diagnostics only: a pair the kernels leave early - an empty query, one beyond the length cap - has a record of zeros)

@@ -163,8 +163,14 @@ struct ResolveArgs {
   int *err;                    // device counter: records dropped because their model is not the segment's (the host turns it into WH_EHIP)
   const int32_t *rext;         // long-list pass (wh_api.hip): record t's regions are NOT in the record but here, at rext + t * rext_stride:
   int64_t rext_stride;         // kRextInts ints per region (first row, last row, envsc bits, domcorr bits, multidomain), ResolveRec::nenv of them
+  // Regions whose lists do not fit the wave's blocks (wh_resolve.hip) are reported in eight ints kBigAfterErr behind <err>:
+  // [0] pairs that have one, [1..3] the most domains of a trace, segments and significant clusters such a region needs, [4]
+  // capacity of the list of their queue positions (0: none - the pair keeps WH_FLAG_TRUNC, WH_NO_BIG_REGION), [5..6] its address (8-byte aligned).
+  int dom_cap, clus_cap;       // > 0: the big-region pass (resolve_big_kernel) - every list of a region in the wave's HBM block, seg_cap segments,
+                               // seg_stride >= resolve_big_seg_ints(...)
 };
 constexpr int kRextInts = 5;
+constexpr int kBigAfterErr = 3;
 hipError_t launch_resolve(const ResolveArgs &a, int blocks, int waves, size_t lds, hipStream_t s);
 size_t resolve_lds_header_bytes(int Qt);
 // cost estimate of every queued pair (cells of its multidomain regions) for the longest-first order
@@ -174,6 +180,9 @@ size_t resolve_lds_bytes(int Lcap, int Mmax);
 int resolve_seg_cap();
 int resolve_waves_per_cu();
 size_t resolve_seg_ints(int Lcap, int Mmax);
+size_t resolve_big_seg_ints(int Lcap, int Mmax, int dom_cap, int seg_cap, int clus_cap);
+int resolve_dom_max();
+int resolve_clus_max();
 size_t resolve_dcache_doubles();
 size_t resolve_tail_row_doubles();
 

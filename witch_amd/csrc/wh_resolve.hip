@@ -22,6 +22,7 @@
 // -DWH_RESOLVE_DEBUG compiles the device printf dumps in (option WH_RDBG; tests/dbg/dbg_resolve.py):
 // off by default, device printf alone costs the kernel half of its register budget.
 #include <climits>
+#include <type_traits>
 #include <hip/hip_runtime.h>
 
 #include "wh_launch.h"
@@ -32,11 +33,12 @@ namespace wh {
 namespace {
 
 constexpr int kSamples = 200;
-constexpr int kDomMax = 32;          // domains per sampled trace kept (more: TRUNC)
-constexpr int kSegCap = 8192;         // sampled segments per region kept, in HBM (200 traces x up to kDomMax domains = 6 400: never short)
+constexpr int kDomMax = 32;          // domains per sampled trace the LDS list holds (more: counted, the pair goes to the big-region pass)
+constexpr int kSegCap = 8192;         // sampled segments per region a wave's HBM block holds in the main launch (more: counted, big-region pass)
 constexpr int kSegLds = 2048;         // ... of them, the clustering keeps its two vertex stacks in LDS up to this many (beyond: in HBM)
-constexpr int kClusMax = 64;          // significant clusters of ONE region kept (more: TRUNC)
+constexpr int kClusMax = 64;          // significant clusters of ONE region the LDS list holds (more: counted, big-region pass)
 constexpr int kHist = 64;            // decision fetches of a trace whose keys are remembered for the next trace
+constexpr int kBigMark = 0x100;      // internal bit of a pair's flags: a list of one of its regions was too short (never stored: the flags are a byte)
 constexpr int kEnvMax = 16;          // envelopes per pair kept internally (detail reports WH_MAX_ENVELOPES)
 enum { stM = 1, stD, stI, stN, stC, stJ, stE, stB, stS };
 
@@ -110,6 +112,14 @@ size_t resolve_lds_header_bytes(int Qt) { return 16 + (size_t)gNARR * Qt * 64 * 
 // halved the resident waves for 2 000-residue proteins
 size_t resolve_seg_ints(int Lcap, int Mmax) { return (size_t)7 * kSegCap + (size_t)(Lcap > Mmax ? Lcap : Mmax) + 8 + 2 * ((size_t)Lcap + 8); }
 int resolve_seg_cap() { return kSegCap; }
+// ... of the big-region pass: six segment arrays and two 32-bit vertex stacks of <seg_cap> entries, the histogram and the
+// per-residue arrays as above, <dom_cap> domains of a trace with their null2 vectors, <clus_cap> clusters (start, end,
+// posterior, a byte of the domination set)
+size_t resolve_big_seg_ints(int Lcap, int Mmax, int dom_cap, int seg_cap, int clus_cap) {
+  return (size_t)8 * seg_cap + (size_t)(Lcap > Mmax ? Lcap : Mmax) + 8 + 2 * ((size_t)Lcap + 8) + (size_t)(4 + 32) * dom_cap + (size_t)3 * clus_cap + ((size_t)clus_cap + 3) / 4 + 2;
+}
+int resolve_dom_max() { return kDomMax; }
+int resolve_clus_max() { return kClusMax; }
 // the walk's cache of threshold lines: 2^kDcBits lines of 64 x 16 bytes + their 8-byte tags, in doubles
 constexpr int kDcBits = 13;
 // doubles per sequence row behind the threshold-line cache: 65 of the E-state row cache + 6 compact special-state arrays
@@ -138,7 +148,16 @@ __device__ __forceinline__ unsigned line_check_bits(unsigned long long key, unsi
 // transition arrays are staged in LDS once for all waves (models of up to 16 cells per lane; a.lds_tables), which is
 // what the two Forward sweeps of a pair read from: they were 34-45 % of the kernel and bound by streaming those arrays
 // from L2 once per row and wave.
-__global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs a) {
+//
+// <BIG>: the big-region pass (wh_host_score.hip: big_region_pass).  The main launch keeps the domains of a trace (kDomMax),
+// their null2 vectors and the significant clusters of a region (kClusMax) in the wave's LDS block and kSegCap segments in
+// its HBM block; a region that needs more is COUNTED to the end (domains of a trace, segments, clusters), the largest
+// counts go to the handle's counters (one atomic max each) and the pair's queue position to the list named there.  The BIG instantiation runs
+// those pairs again with the same code and the lists in the wave's HBM block, sized from the counts (a.dom_cap,
+// a.seg_cap, a.clus_cap): what differs is where a list lives and how lane 0's stores reach the other lanes
+// (wave_barrier for LDS, wave_mem_sync for HBM), as the clustering's vertex stacks do it.
+template <bool BIG>
+__device__ __forceinline__ void resolve_body(const ResolveArgs a) {
   extern __shared__ __attribute__((aligned(16))) int lds_all[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwaves = blockDim.x >> 6;
@@ -148,28 +167,39 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
   const int Lp = (a.Lcap + 4) & ~1;
   uint8_t *seq = reinterpret_cast<uint8_t *>(lds_raw);
   int *uni = lds_raw + ((((a.Lcap + 8) / 4 + 2) + 1) & ~1);
-  int *dom = uni;                                                 // traces: kDomMax x (sqfrom, sqto, hmmfrom, hmmto)
-  float *dnull = reinterpret_cast<float *>(dom + 4 * kDomMax);   // kDomMax x 32
-  short *stk = reinterpret_cast<short *>(dnull + 32 * kDomMax);  // emitting state of each residue: +k match, -k insert
+  short *stk = reinterpret_cast<short *>(uni + (4 + 32) * kDomMax);  // emitting state of each residue: +k match, -k insert
   int *stk32 = reinterpret_cast<int *>(stk);                      // ... the same in 32 bits when a node index does not fit 16
   const bool wide_stk = resolve_stk32(a.Mmax);
   auto stk_get = [&](int p) -> int { return wide_stk ? stk32[p] : (int)stk[p]; };
   auto stk_set = [&](int p, int v) { if (wide_stk) stk32[p] = v; else stk[p] = (short)v; };
   const int SEGCAP = a.seg_cap;
+  const int DOMCAP = BIG ? a.dom_cap : kDomMax, CLCAP = BIG ? a.clus_cap : kClusMax;
+  // a list written by lane 0 is handed to the other lanes: LDS is ordered by its own pipeline, HBM by hand
+  auto list_sync = []() { if constexpr (BIG) wave_mem_sync(); else __builtin_amdgcn_wave_barrier(); };
   unsigned short *s_a = reinterpret_cast<unsigned short *>(uni); // clustering (after the traces): Easel's vertex stacks, same block
   unsigned short *s_b = s_a + kSegLds;
   double *bins = reinterpret_cast<double *>(uni + resolve_uni_ints(a.Lcap, a.Mmax));   // 64 float64 bins of the E-state row pass (8-byte aligned)
   int *misc = reinterpret_cast<int *>(bins + 64);                // 4 x kEnvMax + 3 x kClusMax ints: envelope list of the pair (detail), cluster list of a region
   unsigned long long *hprev = reinterpret_cast<unsigned long long *>(misc + 4 * kEnvMax + 3 * kClusMax + 16), *hcur = hprev + kHist;
+  // the big-region block of the handle's counters sits kBigAfterErr ints behind a.err (wh_host.h: kSlotBigRegion): pairs listed,
+  // the three largest counts, capacity of the list (0: none, WH_NO_BIG_REGION), the list's address.  Reached through a.err
+  // and read from memory where a pair needs it: as kernel arguments of their own these cost the main launch 16 bytes of scratch.
+  auto big_out = [&]() -> int * { return a.err + kBigAfterErr; };     // (formed where it is used: a pointer kept live costs the same)
+  int *pair_pos = misc + 4 * kEnvMax + 3 * kClusMax;             // queue position of the current pair (first of the 16 spare ints)
   (void)Lp;
   const size_t wslot = (size_t)blockIdx.x * nwaves + wave;        // this wave's slab / segment arrays
   int32_t *sg = a.segs + wslot * a.seg_stride;      // per wave in HBM: 6 arrays of SEGCAP ints, the vertex stacks of a large region, the histogram
   int32_t *s_idx = sg, *s_i = sg + SEGCAP, *s_j = sg + 2 * SEGCAP, *s_k = sg + 3 * SEGCAP, *s_m = sg + 4 * SEGCAP;
   int32_t *s_as = sg + 5 * SEGCAP;
   unsigned short *h_a = reinterpret_cast<unsigned short *>(sg + 6 * SEGCAP), *h_b = h_a + SEGCAP;   // vertex stacks of a region of more than kSegLds segments
-  int32_t *epc = sg + 7 * SEGCAP;                                // end-point histogram of one cluster
+  unsigned *w_a = reinterpret_cast<unsigned *>(sg + 6 * SEGCAP), *w_b = w_a + SEGCAP;               // ... BIG: 32 bits per vertex (more than 65 535 segments fit)
+  int32_t *epc = sg + (size_t)(BIG ? 8 : 7) * SEGCAP;            // end-point histogram of one cluster
   float *n2sc = reinterpret_cast<float *>(epc + (a.Lcap > a.Mmax ? a.Lcap : a.Mmax) + 8);   // per residue, HBM (read with L1 bypass)
   float *acc = n2sc + a.Lcap + 8;
+  // traces: DOMCAP x (sqfrom, sqto, hmmfrom, hmmto) and DOMCAP x 32 null2 values; a region's cluster list (start, end, posterior)
+  // and, BIG, a byte per cluster of the domination set - in LDS (head of <uni>, <misc>) or behind the accumulators in HBM
+  int *dom = BIG ? reinterpret_cast<int *>(acc + a.Lcap + 8) : uni;
+  float *dnull = reinterpret_cast<float *>(dom + 4 * DOMCAP);
   // sum of n2sc[lo..hi] in position order (float32, as HMMER adds them): 64 values per fetch, walked with v_readlane
   auto n2sum = [&](int lo, int hi) -> float {
     float sum = 0.f;
@@ -241,6 +271,7 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
     const unsigned long long r_pair0 = a.stats ? __builtin_amdgcn_s_memrealtime() : 0;
     const int ridx = a.order ? a.order[c_start + item] : c_start + item;
     const ResolveRec rec = a.recs[ridx];
+    if (lane == 0) *pair_pos = ridx;                   // (kept in LDS for the pair's end: needed only when a list of a region proves too short)
     // long-list pass: the pair's regions are in HBM (any number of them), the record carries the pair alone
     const int32_t *xl = a.rext ? a.rext + (size_t)ridx * (size_t)a.rext_stride : nullptr;
     if (c_h >= 0 && rec.h != c_h) {                    // never true for a well-formed segment list (the staged tables are c_h's):
@@ -317,7 +348,7 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
       for (int t = lane; t <= Lr; t += 64) ecache[(size_t)t * 65 + 64] = 0.0;
       const unsigned epoch = a.launch_id * 0x9E3779B1u + (++regions_done) * 0x85EBCA77u;     // (the threshold-line cache needs no clearing: see line_check_bits)
       wave_mem_sync();
-      int nseg = 0;
+      int nseg = 0, nseg_all = 0;          // segments kept, segments sampled
       Rng rng;
       rng.x = mix3(42u, 87654321u, 12345678u);
       if (rng.x == 0) rng.x = 42;
@@ -591,15 +622,20 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
             if (lane == 0) stk_set(i, k);
           } else if (s1 == stI) { if (lane == 0) stk_set(i, -k); }
           else if (s1 == stB) {
-            if (ndom < kDomMax) {
+            if (ndom < DOMCAP) {
               if (lane == 0) { dom[4 * ndom] = sqfrom; dom[4 * ndom + 1] = sqto; dom[4 * ndom + 2] = hmmfrom; dom[4 * ndom + 3] = hmmto; }
-              ndom++;
-            } else flags |= WH_FLAG_TRUNC;
+            }
+            ndom++;
           }
           if ((s1 == stN || s1 == stJ || s1 == stC) && s1 == s0) i--;
           s0 = s1;
         }
-        __builtin_amdgcn_wave_barrier();
+        nseg_all += ndom;
+        if (ndom > DOMCAP) {                 // (the walk and its random numbers do not depend on the list: the count is exact)
+          if (lane == 0) atomicMax(big_out() + 1, ndom);
+          flags |= kBigMark; ndom = DOMCAP;
+        }
+        list_sync();
         if (a.stats) { n_prev = jf < kHist ? jf : kHist; unsigned long long *tsw = hprev; hprev = hcur; hcur = tsw; }
         const long long tp0 = a.stats ? __builtin_readcyclecounter() : 0;
         // null2 by trace of every sampled domain (A.4b / p7_Null2_ByTrace): mean emission odds of the
@@ -696,21 +732,23 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
           }
           __builtin_amdgcn_wave_barrier();
           if (lane < a.K) dnull[32 * d + lane] = mine;
-          __builtin_amdgcn_wave_barrier();
+          list_sync();
           if (lane >= a.K && lane < a.Kp) {
             const uint32_t msk = a.degen[lane];
             float s = 0.f; int n = 0;
             for (int x = 0; x < a.K; x++) if (msk & (1u << x)) { s += dnull[32 * d + x]; n++; }
             dnull[32 * d + lane] = n > 0 ? s / (float)n : 1.0f;
           }
-          __builtin_amdgcn_wave_barrier();
+          list_sync();
         }
         // per-residue accumulators: +1 outside sampled domains AND at a domain's first residue (sic),
         // + null2[x] at the domain's other residues
         // (the accumulators live in the wave's HBM slab: eight positions per lane are requested at once)
         // (the domains' bounds once into a register, lane d holding domain d, read back as scalars: the inner loop was a chain of
         // dependent LDS reads - two bounds per domain and position)
-        const int dlo_v = lane < ndom ? dom[4 * lane] : 0, dhi_v = lane < ndom ? dom[4 * lane + 1] : -1;
+        // (BIG: 64 domains at a time; a trace's domains do not overlap, so at most one of them sets a position's value)
+        const int dchunks = BIG ? (ndom + 63) >> 6 : 1;
+        int dlo_v = lane < ndom ? dom[4 * lane] : 0, dhi_v = lane < ndom ? dom[4 * lane + 1] : -1;
         for (int p0 = 1 + lane; p0 <= Lr; p0 += 512) {
           float old[8];
           int rsv[8];
@@ -723,12 +761,16 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
           float add[8];
 #pragma unroll
           for (int u = 0; u < 8; u++) add[u] = 1.0f;
-          for (int d = 0; d < ndom; d++) {
-            const int lo = __builtin_amdgcn_readlane(dlo_v, d), hi = __builtin_amdgcn_readlane(dhi_v, d);
+          for (int dc = 0; dc < dchunks; dc++) {
+            const int d0 = BIG ? dc << 6 : 0, d1 = BIG ? min(ndom, d0 + 64) : ndom;
+            if constexpr (BIG) { dlo_v = d0 + lane < ndom ? dom[4 * (d0 + lane)] : 0; dhi_v = d0 + lane < ndom ? dom[4 * (d0 + lane) + 1] : -1; }
+            for (int d = d0; d < d1; d++) {
+              const int lo = __builtin_amdgcn_readlane(dlo_v, d - d0), hi = __builtin_amdgcn_readlane(dhi_v, d - d0);
 #pragma unroll
-            for (int u = 0; u < 8; u++) {
-              const int pos = p0 + 64 * u;
-              if (pos > lo && pos <= hi) add[u] = dnull[32 * d + rsv[u]];
+              for (int u = 0; u < 8; u++) {
+                const int pos = p0 + 64 * u;
+                if (pos > lo && pos <= hi) add[u] = dnull[32 * d + rsv[u]];
+              }
             }
           }
 #pragma unroll
@@ -744,7 +786,6 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
               const int z = nseg + (ndom - 1 - d);
               s_idx[z] = t; s_i[z] = dom[4 * d] + ireg - 1; s_j[z] = dom[4 * d + 1] + ireg - 1; s_k[z] = dom[4 * d + 2]; s_m[z] = dom[4 * d + 3];
             }
-        if (nseg + ndom > SEGCAP) flags |= WH_FLAG_TRUNC;
         nseg = min(SEGCAP, nseg + ndom);
         __builtin_amdgcn_wave_barrier();
         if (a.stats) c_post += __builtin_readcyclecounter() - tp0;
@@ -754,15 +795,17 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
         atomicAdd(a.stats + 20, (unsigned long long)n_pred); atomicAdd(a.stats + 21, (unsigned long long)n_resync); atomicAdd(a.stats + 23, (unsigned long long)c_load);
         atomicAdd(a.stats + 8, (unsigned long long)n_bm); atomicAdd(a.stats + 9, (unsigned long long)n_bd); atomicAdd(a.stats + 10, (unsigned long long)n_bf); atomicAdd(a.stats + 11, (unsigned long long)n_i); atomicAdd(a.stats + 12, (unsigned long long)n_hit);
       }
+      if (nseg_all > SEGCAP) { if (lane == 0) atomicMax(big_out() + 2, nseg_all); flags |= kBigMark; }
       RTICK(1);
       for (int pos = 1 + lane; pos <= Lr; pos += 64) n2sc[ireg + pos - 1] = logf(__builtin_nontemporal_load(acc + pos) / (float)kSamples);
       wave_mem_sync();
       // ---------------- single-linkage clustering in Easel's vertex order (esl_cluster_SingleLinkage)
       // (the two vertex stacks: in LDS, ordered by the LDS pipeline itself - or, for a region of more than kSegLds segments,
       // in the wave's HBM block with every hand-over between lanes ordered by hand; same code, <sync> is what differs)
-      auto single_linkage = [&](unsigned short *s_a, unsigned short *s_b, auto sync) -> int {
+      auto single_linkage = [&](auto *s_a, auto *s_b, auto sync) -> int {
+        using vtx_t = typename std::remove_reference<decltype(*s_a)>::type;
         int nc = 0;
-        for (int v = lane; v < nseg; v += 64) s_a[v] = (unsigned short)(nseg - v - 1);
+        for (int v = lane; v < nseg; v += 64) s_a[v] = (vtx_t)(nseg - v - 1);
         sync();
         int na = nseg;
         while (na > 0) {
@@ -770,7 +813,7 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
           na--;
           int nb = 1;
           sync();
-          if (lane == 0) s_b[0] = (unsigned short)v;
+          if (lane == 0) s_b[0] = (vtx_t)v;
           sync();
           while (nb > 0) {
             v = s_b[nb - 1];
@@ -799,7 +842,7 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
                 sync();
                 if (lane == 0) {
                   s_a[tp] = s_a[na - 1];
-                  s_b[nb] = (unsigned short)wv;
+                  s_b[nb] = (vtx_t)wv;
                 }
                 na--; nb++;
                 sync();
@@ -810,8 +853,10 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
         }
         return nc;
       };
-      const int nc = nseg <= kSegLds ? single_linkage(s_a, s_b, []() { __builtin_amdgcn_wave_barrier(); })
-                                     : single_linkage(h_a, h_b, []() { wave_mem_sync(); });
+      int nc;
+      if (nseg <= kSegLds) nc = single_linkage(s_a, s_b, []() { __builtin_amdgcn_wave_barrier(); });
+      else if constexpr (BIG) nc = single_linkage(w_a, w_b, []() { wave_mem_sync(); });
+      else nc = single_linkage(h_a, h_b, []() { wave_mem_sync(); });
       wave_mem_sync();
 #ifdef WH_RESOLVE_DEBUG
       if (a.dbg && lane == 0) {
@@ -822,8 +867,9 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
       RTICK(2);
       // ---------------- clusters -> envelopes (p7_spensemble_Cluster)
       int nsig = 0;
-      int *g_i = misc + 4 * kEnvMax, *g_j = g_i + kClusMax;
-      float *g_p = reinterpret_cast<float *>(g_j + kClusMax);
+      int *g_i = BIG ? reinterpret_cast<int *>(dnull + (size_t)32 * DOMCAP) : misc + 4 * kEnvMax, *g_j = g_i + CLCAP;
+      float *g_p = reinterpret_cast<float *>(g_j + CLCAP);
+      uint8_t *g_dom = reinterpret_cast<uint8_t *>(g_p + CLCAP);     // (BIG only)
       for (int c = 0; c < nc; c++) {
         // posterior of the cluster: traces that contribute (segments are in trace order)
         int ninc = 0;
@@ -890,25 +936,38 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
         if (a.dbg && lane == 0) printf("[resolve q=%lld h=%d region %d..%d] cluster %d: ninc %d thr %d i %d..%d j %d..%d k %d..%d m %d..%d best %d %d %d %d\n", (long long)rec.q, rec.h, ireg, jreg, c, ninc, thr, imin, imax, jmin, jmax, kmin, kmax, mmin, mmax, best[0], best[2], best[1], best[3]);
 #endif
         if (best[0] > best[2] || best[1] > best[3]) continue;
-        if (nsig < kClusMax) { g_i[nsig] = best[0]; g_j[nsig] = best[2]; g_p[nsig] = (float)ninc / (float)kSamples; nsig++; }
-        else flags |= WH_FLAG_TRUNC;
+        if (nsig < CLCAP && (!BIG || lane == 0)) { g_i[nsig] = best[0]; g_j[nsig] = best[2]; g_p[nsig] = (float)ninc / (float)kSamples; }
+        nsig++;
       }
+      if (nsig > CLCAP) { if (lane == 0) atomicMax(big_out() + 3, nsig); flags |= kBigMark; nsig = CLCAP; }
+      // (the main launch clustered a truncated segment list: what it counted is a lower bound, the full count is this one)
+      else if (BIG && nsig > kClusMax && lane == 0) atomicMax(big_out() + 3, nsig);
       RTICK(3);
       // order by start (stable), drop dominated clusters (region_trace_ensemble)
+      // (LDS: every lane writes the same values.  BIG: lane 0 sorts its own list in HBM, then hands it over)
+      if (!BIG || lane == 0)
       for (int d = 1; d < nsig; d++) {
         const int ti = g_i[d], tj = g_j[d]; const float tp = g_p[d];
         int d2 = d - 1;
         for (; d2 >= 0 && g_i[d2] > ti; d2--) { g_i[d2 + 1] = g_i[d2]; g_j[d2 + 1] = g_j[d2]; g_p[d2 + 1] = g_p[d2]; }
         g_i[d2 + 1] = ti; g_j[d2 + 1] = tj; g_p[d2 + 1] = tp;
       }
-      unsigned long long dominated = 0;
+      unsigned long long dominated = 0;     // the domination set: one word in the main launch, BIG a byte per cluster in HBM
+      if constexpr (BIG) {
+        for (int d = lane; d < nsig; d += 64) g_dom[d] = 0;
+        wave_mem_sync();
+      }
       for (int d = 0; d < nsig; d++)
         for (int d2 = d + 1; d2 < nsig; d2++) {
           const int nov = min(g_j[d], g_j[d2]) - max(g_i[d], g_i[d2]) + 1;
           if (nov == 0) break;
           const int nn = min(g_j[d] - g_i[d] + 1, g_j[d2] - g_i[d2] + 1);
-          if ((float)nov / (float)nn >= 0.8f) { if (g_p[d] > g_p[d2]) dominated |= 1ull << d2; else dominated |= 1ull << d; }
+          if ((float)nov / (float)nn >= 0.8f) {
+            const int loser = g_p[d] > g_p[d2] ? d2 : d;
+            if constexpr (BIG) { if (lane == 0) g_dom[loser] = 1; } else dominated |= 1ull << loser;
+          }
         }
+      if constexpr (BIG) wave_mem_sync();
       // ---------------- every surviving cluster is an envelope: unihit Forward score, trace-derived null2
       // HMMER sums n2sc over the whole sequence in position order; per region here (float32 either way)
       const float regsum = n2sum(ireg, jreg);
@@ -917,7 +976,7 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
       if (a.dbg && lane == 0) { printf("[resolve] region n2sc sum %.6f; n2sc:", regsum); for (int pos = ireg; pos <= jreg; pos++) printf(" %.3f", __builtin_nontemporal_load(n2sc + pos)); printf("\n"); }
 #endif
       for (int d = 0; d < nsig; d++) {
-        if (dominated & (1ull << d)) continue;
+        if (BIG ? g_dom[d] != 0 : (dominated & (1ull << d)) != 0) continue;
         const int i2 = g_i[d], j2 = g_j[d], Ld = j2 - i2 + 1;
         const double envsc = gforward_any<false>(m, seq + (i2 - 1), Ld, cu, mx, lane, use_tl ? (const ldbl *)tabL : nullptr);
         const float dc = n2sum(i2, j2);
@@ -956,6 +1015,16 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
       dp->nenv = nenv < WH_MAX_ENVELOPES ? nenv : WH_MAX_ENVELOPES;       // (the first ones; the score above is over all of them)
       for (int e = 0; e < dp->nenv; e++) { dp->env_i[e] = env_i[e]; dp->env_j[e] = env_j[e]; dp->envsc[e] = env_sc[e]; dp->domcorr[e] = env_dc[e]; }
     }
+    if (flags & kBigMark) {
+      // (a pair whose region LIST was too short, main launch only, is done again by the long-list pass anyway)
+      const int big_cap = __builtin_amdgcn_readfirstlane(__builtin_nontemporal_load(big_out() + 4));     // 0: no list (WH_NO_BIG_REGION)
+      if (big_cap <= 0) flags |= WH_FLAG_TRUNC;
+      else if ((a.rext || !(flags & WH_FLAG_TRUNC)) && lane == 0) {
+        int32_t *big_list = *reinterpret_cast<int32_t *const *>(big_out() + 5);
+        const int slot = atomicAdd(big_out(), 1);
+        if (slot < big_cap) big_list[slot] = *pair_pos;
+      }
+    }
     if (lane == 0) { a.decibits[out] = decibits; a.flags[out] = (uint8_t)flags; }
     if (a.stats && lane == 0) {      // shader cycles and 100 MHz ticks of this pair: their ratio is the clock the kernel ran at
       atomicAdd(a.stats + 14, (unsigned long long)(__builtin_readcyclecounter() - t_pair0));
@@ -968,6 +1037,10 @@ __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs 
     atomicAdd(a.stats + 17, life); atomicMax(a.stats + 18, life); atomicAdd(a.stats + 19, 1ull);
   }
 }
+
+__global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs a) { resolve_body<false>(a); }
+// the big-region pass: one wave per workgroup, every list of a region in the wave's HBM block
+__global__ __launch_bounds__(64 * kResMaxWaves) void resolve_big_kernel(ResolveArgs a) { resolve_body<true>(a); }
 
 // One thread per queued pair: the cells of its multidomain regions (region length x model length), the
 // quantity the Forward fill, the walk and the envelope rescoring all scale with; and its model.
@@ -994,9 +1067,14 @@ hipError_t launch_resolve_keys(const ResolveRec *recs, int n, const DevHMM *hmms
 
 hipError_t launch_resolve(const ResolveArgs &a, int blocks, int waves, size_t lds, hipStream_t s) {
   if (waves < 1 || waves > kResMaxWaves) return hipErrorInvalidValue;
-  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&resolve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const bool big = a.dom_cap > 0;
+  if (big && (a.dom_cap < kDomMax || a.seg_cap < kSegCap || a.clus_cap < kClusMax || a.seg_stride < resolve_big_seg_ints(a.Lcap, a.Mmax, a.dom_cap, a.seg_cap, a.clus_cap)))
+    return hipErrorInvalidValue;
+  const void *fn = big ? reinterpret_cast<const void *>(&resolve_big_kernel) : reinterpret_cast<const void *>(&resolve_kernel);
+  hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(resolve_kernel, dim3(blocks), dim3(64 * waves), lds, s, a);
+  if (big) hipLaunchKernelGGL(resolve_big_kernel, dim3(blocks), dim3(64 * waves), lds, s, a);
+  else hipLaunchKernelGGL(resolve_kernel, dim3(blocks), dim3(64 * waves), lds, s, a);
   return hipGetLastError();
 }
 

@@ -131,6 +131,14 @@ class EHMM:
         check(lib().wh_last_score_counters(self._h, c8.ctypes.data), "wh_last_score_counters")
         return int(c8[7])
 
+    def last_region_overflow(self):
+        """The big-region pass of the last score call: pairs it scored again because ONE multidomain region needed more
+        domains per sampled trace, segments or significant clusters than the resolver's fixed lists hold, and the largest
+        of each it met (all 0: no such region).  include/witch_hip.h: wh_last_region_overflow."""
+        o4 = np.zeros(4, dtype=np.int64)
+        check(lib().wh_last_region_overflow(self._h, o4.ctypes.data), "wh_last_region_overflow")
+        return {"pairs": int(o4[0]), "max_domains": int(o4[1]), "max_segments": int(o4[2]), "max_clusters": int(o4[3])}
+
     def set_path_buffer(self, paths_t):
         """Registers a CUDA uint8 tensor of nq x H bytes that later score calls fill with WH_PATH_* bits per pair
         (staged launches only; None switches it off).  The caller keeps the tensor alive (include/witch_hip.h)."""

@@ -61,6 +61,7 @@ class QueryAlignmentEngine:
         self.merged_minmax = None
         self.truncated_pairs = []     # (taxon, hmm label) with WH_FLAG_TRUNC
         self.long_list_pairs = 0      # pairs with more regions than a scoring kernel lists, scored in full by the long-list pass
+        self.big_region_pairs = 0     # pairs with a region beyond the resolver's fixed lists, scored in full by the big-region pass
         self.unaligned_pairs = []     # (taxon, hmm label) the alignment stage returned unaligned
         self.query_text = None        # uint8: the local queries' characters (upper-cased on read), concatenated like query_offsets
         self.device = 0
@@ -144,14 +145,16 @@ class QueryAlignmentEngine:
             t0 = time.time()
             deci, flags = e.score(cres, coffs)
             self.long_list_pairs += e.last_long_list_pairs()
+            self.big_region_pairs += e.last_region_overflow()["pairs"]
             if multidomain_policy == "drop":
                 drop = (flags & 2) != 0
                 flags = np.where(drop, flags & ~np.uint8(1), flags).astype(np.uint8)
             trunc = np.argwhere((flags & 8) != 0)
             if len(trunc):
-                # WH_FLAG_TRUNC: a list of the pair overflowed (include/witch_hip.h: since round 5 NOT the region list - pairs
-                # with more than WH_MAX_ENVELOPES regions are scored in full by the long-list pass - but more than 32 domains
-                # or 64 clusters inside ONE multidomain region); its score may differ from hmmsearch's.  Never silent.
+                # WH_FLAG_TRUNC (include/witch_hip.h): no list of a pair is too short any more - pairs with more than
+                # WH_MAX_ENVELOPES regions are scored in full by the long-list pass, regions with more domains, segments or
+                # clusters than the resolver's lists by the big-region pass - so this is a malformed queue record (an internal
+                # error) or a development knob; the pair's score may differ from hmmsearch's.  Never silent.
                 self.truncated_pairs += [(self.taxa[int(q) + c0 + self.row_lo], int(labels[int(h)])) for q, h in trunc]
             t1 = time.time()
             idx, w, nk, nu = e.topk(deci, flags, self.num_hmms)
@@ -204,8 +207,8 @@ class QueryAlignmentEngine:
         self.qpair_off[1:] = np.cumsum(self.n_used)
         self.pair_of = None
         if self.truncated_pairs:
-            warnings.warn("witch_amd: %d (query, HMM) pair(s) overflowed a list of the scoring kernels (WH_FLAG_TRUNC: more than 32 domains or 64 "
-                          "clusters in one multidomain region); their scores may differ from hmmsearch's (first: %s vs A_0_%d)"
+            warnings.warn("witch_amd: %d (query, HMM) pair(s) came back with WH_FLAG_TRUNC (a malformed resolver queue record, or a second pass "
+                          "switched off by a development knob); their scores may differ from hmmsearch's (first: %s vs A_0_%d)"
                           % ((len(self.truncated_pairs),) + self.truncated_pairs[0]), RuntimeWarning)
         if self.unaligned_pairs:
             warnings.warn("witch_amd: %d pair(s) on models of more than 3072 nodes could not be aligned and are left out "
