@@ -66,10 +66,16 @@ extern "C" {
  * count.  Nor is there a limit INSIDE a multidomain region: the resolver keeps 32 domains of a sampled trace, 8 192
  * sampled segments and 64 significant clusters of a region in fixed lists; a region that needs more (a tandem repeat of
  * more than 32 copies) is counted to the end, and its pair is scored again inside the same call by the big-region pass -
- * the same resolver with those lists in HBM, sized from the counts (wh_last_region_overflow).  What can still set
- * WH_FLAG_TRUNC: a malformed record in the resolver's queue (an internal error; a region outside its sequence), more
- * than four million pairs for the long-list pass in one call, or the development knobs WH_NO_LONG_LIST /
- * WH_NO_BIG_REGION / WH_NO_RESOLVE.  The value stays 8 for binary compatibility. */
+ * the same resolver with those lists in HBM, sized from the counts (wh_last_region_overflow).  Nor does the resolver limit
+ * the QUERY length: its per-wave LDS block holds the query and a state per residue, and a call whose longest query does
+ * not fit (beyond ~52 000 residues; ~31 000 with a model of more than 32 767 nodes) sizes its main launches for the
+ * lengths that keep their occupancy and resolves the pairs of longer queries in the long-query pass, the same resolver
+ * with those two arrays in HBM (wh_last_long_query_pairs).  The query-length limits that remain are the SCORING kernels'
+ * own, and they fail loudly (WH_ERANGE: "query length ... does not fit in LDS"; the float64 front end near 163 000
+ * residues).  What can still set WH_FLAG_TRUNC: a malformed record in the resolver's queue (an internal error; a region
+ * outside its sequence), more than four million pairs for the long-list pass in one call, or the development knobs
+ * WH_NO_LONG_LIST / WH_NO_BIG_REGION / WH_NO_RESOLVE (WH_NO_LONG_QUERY sets no flag: the call runs without the resolver,
+ * multidomain regions stay one envelope).  The value stays 8 for binary compatibility. */
 #define WH_MAX_ENVELOPES 16
 
 /* Which code path a pair took through the scoring kernels (optional per-pair byte, wh_set_path_buffer; written by
@@ -189,6 +195,10 @@ int wh_last_score_counters(wh_ehmm *e, int64_t *out8);
  * [2] = the most sampled segments and [3] = the most significant clusters of such a region (0 where that list was long
  * enough).  All 0: no pair went through the pass, which then cost nothing beyond four ints in the call's one read-back. */
 int wh_last_region_overflow(wh_ehmm *e, int64_t *out4);
+/* The long-query pass of the last scoring call: out[0] = pairs it resolved because their query is longer than the length
+ * cap of the resolver's main launches (only in a call whose longest query does not fit the resolver's LDS block), out[1] =
+ * the longest query among them.  Both 0: no pair went through the pass (two more ints in the call's one read-back). */
+int wh_last_long_query_pairs(wh_ehmm *e, int64_t out[2]);
 
 /* Optional per-PAIR record of the same: a device array of nq x H bytes that the scoring calls made after this one fill
  * with WH_PATH_* bits (NULL switches it off again).  Written by the staged launches only (WH_SCORE_KERNEL=10; pairs

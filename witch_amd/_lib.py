@@ -72,6 +72,7 @@ SYMBOLS = {
     "wh_set_path_buffer": (C.c_int, [_P, _P]),
     "wh_last_queue_reruns": (C.c_int, [_P]),
     "wh_last_region_overflow": (C.c_int, [_P, _P]),
+    "wh_last_long_query_pairs": (C.c_int, [_P, _P]),
     "wh_last_score_launches": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "wh_last_kernel_ms": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "wh_set_timing": (C.c_int, [_P, C.c_int]),

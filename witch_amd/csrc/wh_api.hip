@@ -54,7 +54,7 @@ int wh_digitize(int alphabet, const char *text, int64_t n, uint8_t *out) {
 
 void wh_ehmm_free(wh_ehmm *e) {
   if (!e) return;
-  for (DevBuf *b : {&e->d_tlist, &e->d_rext, &e->d_biglist, &e->d_bigsegs, &e->d_gtab, &e->d_rrecs, &e->d_rmx, &e->d_rsegs, &e->d_hmms, &e->d_tables, &e->d_nseq, &e->d_index, &e->d_lists, &e->d_counter, &e->d_scratch, &e->d_ascratch, &e->d_wscratch,
+  for (DevBuf *b : {&e->d_tlist, &e->d_rext, &e->d_biglist, &e->d_bigsegs, &e->d_longlist, &e->d_gtab, &e->d_rrecs, &e->d_rmx, &e->d_rsegs, &e->d_hmms, &e->d_tables, &e->d_nseq, &e->d_index, &e->d_lists, &e->d_counter, &e->d_scratch, &e->d_ascratch, &e->d_wscratch,
                     &e->s_res, &e->s_off, &e->s_deci, &e->s_flags, &e->s_fwd, &e->s_det, &e->s_idx, &e->s_w,
                     &e->s_nk, &e->s_nu, &e->s_pq, &e->s_ph, &e->s_co, &e->s_cols, &e->s_pos, &e->d_rkeys, &e->d_rorder, &e->d_rchunks, &e->d_qorder, &e->d_order, &e->d_items, &e->d_recs, &e->d_spec, &e->d_back, &e->d_cwj, &e->d_cwv, &e->d_cwn, &e->d_crow,
                     &e->c_buf[0], &e->c_buf[1], &e->c_buf[2], &e->c_buf[3], &e->c_buf[4], &e->c_buf[5], &e->c_buf[6],
@@ -242,6 +242,7 @@ int wh_set_option(wh_ehmm *e, const char *name, const char *value) {
   else if (!strcmp(name, "WH_NO_RESOLVE")) k.no_resolve = on;
   else if (!strcmp(name, "WH_NO_LONG_LIST")) k.no_long_list = on;
   else if (!strcmp(name, "WH_NO_BIG_REGION")) k.no_big_region = on;
+  else if (!strcmp(name, "WH_NO_LONG_QUERY")) k.no_long_query = on;
   else if (!strcmp(name, "WH_NO_WINDOW")) k.no_window = on;
   else if (!strcmp(name, "WH_NO_P2WIN")) k.no_p2win = on;
   else if (!strcmp(name, "WH_RQUEUE_CAP")) k.rqueue_cap = *v ? std::max(1, atoi(v)) : 0;
@@ -257,7 +258,7 @@ int wh_set_option(wh_ehmm *e, const char *name, const char *value) {
 }
 
 static void knobs_from_env(wh_ehmm *e) {
-  for (const char *name : {"WH_SCORE_KERNEL", "WH_ITEM_G", "WH_ST_UNITS", "WH_KEEP_LOG2", "WH_MAX_WAVES", "WH_FORCE_SPECG", "WH_NO_LOGSPACE", "WH_NO_RESOLVE", "WH_NO_LONG_LIST", "WH_NO_BIG_REGION", "WH_NO_WINDOW", "WH_NO_P2WIN", "WH_RQUEUE_CAP", "WH_NO_WIDE_ALIGN", "WH_STATS", "WH_TRACE", "WH_DBG", "WH_RDBG"})
+  for (const char *name : {"WH_SCORE_KERNEL", "WH_ITEM_G", "WH_ST_UNITS", "WH_KEEP_LOG2", "WH_MAX_WAVES", "WH_FORCE_SPECG", "WH_NO_LOGSPACE", "WH_NO_RESOLVE", "WH_NO_LONG_LIST", "WH_NO_BIG_REGION", "WH_NO_LONG_QUERY", "WH_NO_WINDOW", "WH_NO_P2WIN", "WH_RQUEUE_CAP", "WH_NO_WIDE_ALIGN", "WH_STATS", "WH_TRACE", "WH_DBG", "WH_RDBG"})
     if (const char *v = getenv(name)) (void)wh_set_option(e, name, v);
 }
 
@@ -314,6 +315,12 @@ int wh_set_path_buffer(wh_ehmm *e, uint8_t *d_paths) {
 int wh_last_region_overflow(wh_ehmm *e, int64_t *out4) {
   if (!e || !out4) { set_error("wh_last_region_overflow: bad argument"); return WH_EINVAL; }
   for (int t = 0; t < 4; t++) out4[t] = e->last_big[t];
+  return WH_OK;
+}
+
+int wh_last_long_query_pairs(wh_ehmm *e, int64_t out[2]) {
+  if (!e || !out) { set_error("wh_last_long_query_pairs: bad argument"); return WH_EINVAL; }
+  out[0] = e->last_long[0]; out[1] = e->last_long[1];
   return WH_OK;
 }
 

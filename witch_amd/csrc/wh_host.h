@@ -68,6 +68,7 @@ struct Knobs {
   bool no_p2win = false;     // the multihit Backward sweep runs full width only (A/B and debugging)
   bool no_long_list = false; // WH_NO_LONG_LIST: pairs with more than WH_MAX_ENVELOPES regions keep WH_FLAG_TRUNC (no second pass; tests)
   bool no_big_region = false; // WH_NO_BIG_REGION: a region with more domains, segments or clusters than the resolver's lists hold keeps WH_FLAG_TRUNC (no big-region pass; tests)
+  bool no_long_query = false; // WH_NO_LONG_QUERY: a call whose longest query exceeds the resolver's LDS cap runs without the resolver, as before the long-query pass (tests)
   bool no_resolve = false;   // multidomain regions stay ONE envelope (round-1 behaviour) instead of HMMER's stochastic resolver
   int rqueue_cap = 0;        // test hook: size the resolver's queue for this many pairs instead of the estimate (forces the overflow re-run)
   int item_g = 0;            // queries per wave in a work item of the phase-call kernels (0 = 32; A/B)
@@ -78,8 +79,8 @@ struct Knobs {
 };
 
 // ---- d_counter: 256 ints in HBM, zeroed at load.  Every owner of a slot or range, in one place: the kernels and the
-// wh_last_* getters depend on these numbers.  [60..62], [68..79], [89..95], [124..127], [144..145], [147], [157..159]
-// and [176..255] are free.
+// wh_last_* getters depend on these numbers.  [60..62], [68..79], [89..95], [124..127], [144..145], [147], [178..255]
+// are free.
 enum CounterSlot {
   kSlotLaunch0 = 0,         // [0..59] work-queue heads of the launches of ONE call, in launch order: the one-wave scoring
   kMaxLaunches = 60,        //   classes (wh_score_dev) or the alignment launches (wh_align_dev: both passes)
@@ -98,8 +99,10 @@ enum CounterSlot {
   kSlotResolveErr = 146,    // queue records the resolver found in a segment of another model (never, for a well-formed segment list)
   kSlotLongList = 148,      // pairs flagged WH_FLAG_TRUNC after the resolver (long-list pass)
   kSlotBigRegion = 149,     // [149..156] pairs with a region beyond the resolver's lists, the largest counts (read with 148), capacity and address of their list (wh_launch.h: kBigAfterErr)
+  kSlotLongQuery = 157,     // [157..159] pairs whose query is beyond a resolver launch's length cap, the longest such query (read with 148), capacity of their list (wh_launch.h: kLongAfterErr)
   kSlotWideScore = 160,     // [160..175] work-queue heads of the wide scoring launches, one per (cells per lane, waves) class
   kWideScoreClasses = 16,   //   (13 exist: 12 x 5..8, 16 x 7..8, 24 x 6..8, 48 x 5..8; WH_FORCE_WIDE adds smaller workgroups of one of them)
+  kSlotLongQueryList = 176, // [176..177] address of that list (wh_launch.h: kLongListAfterErr)
   kCounterInts = 256
 };
 static_assert(kSlotLaunch0 + kMaxLaunches <= kSlotConsensus && kSlotConsensus < kSlotResolveCount && kSlotResolveWork == kSlotResolveCount + 1 &&
@@ -107,7 +110,9 @@ static_assert(kSlotLaunch0 + kMaxLaunches <= kSlotConsensus && kSlotConsensus < 
 static_assert(kSlotWideAlign + kWideAlignClasses <= kSlotAlignStat && kSlotAlignCycles >= kSlotAlignStat && kSlotAlignCycles + 8 <= kSlotAlignStat + kAlignStatInts &&
               kSlotAlignCycles % 2 == 0 && kSlotAlignStat + kAlignStatInts <= kSlotScorePath && kSlotScorePath % 2 == 0, "d_counter slots overlap");
 static_assert(kSlotScorePath + kScorePathInts <= kSlotResolveErr && kSlotResolveErr < kSlotLongList && kSlotBigRegion == kSlotLongList + 1 && kSlotBigRegion + 8 <= kSlotWideScore && kSlotBigRegion == kSlotResolveErr + kBigAfterErr && (kSlotBigRegion + 5) % 2 == 0 &&
-              kSlotWideScore + kWideScoreClasses <= kCounterInts, "d_counter slots overlap or leave the buffer");
+              kSlotWideScore + kWideScoreClasses <= kSlotLongQueryList && kSlotLongQueryList + 2 <= kCounterInts, "d_counter slots overlap or leave the buffer");
+static_assert(kSlotLongQuery == kSlotBigRegion + 8 && kSlotLongQuery + 3 <= kSlotWideScore && kSlotLongQuery == kSlotResolveErr + kLongAfterErr &&
+              kSlotLongQueryList == kSlotResolveErr + kLongListAfterErr && kSlotLongQueryList % 2 == 0, "d_counter slots overlap");
 
 struct wh_ehmm {
   Knobs knobs;
@@ -131,8 +136,11 @@ struct wh_ehmm {
   int64_t last_long_list = 0;               // ... of them, pairs of the long-list pass (more than WH_MAX_ENVELOPES regions)
   DevBuf d_tlist, d_rext;                   // long-list pass: pair positions, their region lists
   int64_t last_big[4] = {0, 0, 0, 0};       // big-region pass of the last wh_score call: pairs redone, most domains of a trace, segments, clusters of a region
-  int big_blk[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // ... host copy of the counters' big-region block as uploaded in front of a resolver launch
+  int big_blk[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // ... host copy of the counters' big-region and long-query blocks as uploaded in front of a resolver launch
+  int32_t *long_blk = nullptr;              // ... and of the long-query list's address
   DevBuf d_biglist, d_bigsegs;              // ... queue positions of its pairs (two halves: read / written by a launch), its waves' list blocks
+  int64_t last_long[2] = {0, 0};            // long-query pass of the last wh_score call: pairs redone, the longest query among them
+  DevBuf d_longlist;                        // ... queue positions of its pairs
   int64_t rq_cap = 0;                       // records the queue of the current scoring call holds
   double rq_rate = 0.0;                     // largest share of queued pairs any call on this handle has seen (sizes the next queue)
   int64_t rq_floor = 0;                     // ... at least this many (set when a call overflowed its estimate; the call then runs again)

@@ -18,6 +18,7 @@ struct ScoreCall {
   const uint8_t *d_residues; const int64_t *d_offsets; int64_t nq, total_residues; int32_t max_len;
   int32_t *d_decibits; uint8_t *d_flags; float *d_fwd_bits; wh_pair_detail *d_detail;
   int Lc, H;
+  int Lmain;                     // length cap of the main resolver launches (= Lc unless the longest query exceeds the resolver's LDS block: long_query_pass)
   int64_t npairs_all;
   bool resolve;                  // multidomain regions go through the resolver's queue (else: one envelope per region)
   bool mixed;                    // query lengths differ enough for the length order to pay in the one-wave classes too
@@ -26,13 +27,30 @@ struct ScoreCall {
   int res_waves;                 // WH_RES_WAVES (experiments: waves per resolver workgroup), 0 = not set
 };
 
+// the longest query of which the main resolver launch keeps all its waves per CU (no staged tables): the length cap of the
+// main launches of a call that has a query beyond the resolver's LDS block
+static int resolve_main_cap(int max_M) {
+  const size_t per_wave = (kLdsBudget - resolve_lds_header_bytes(0)) / (size_t)resolve_waves_per_cu();
+  int lo = 1, hi = 1 << 20;              // (resolve_lds_bytes grows with the length; the cap is a few thousand residues)
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (resolve_lds_bytes(mid, max_M) <= per_wave) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 static ScoreCall score_call(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues, int32_t max_len,
                             int32_t *d_decibits, uint8_t *d_flags, float *d_fwd_bits, wh_pair_detail *d_detail, void *stream) {
   ScoreCall c = {e, (hipStream_t)stream, d_residues, d_offsets, nq, total_residues, max_len, d_decibits, d_flags, d_fwd_bits, d_detail};
   c.Lc = std::max(max_len, 1);
   c.H = (int)e->hmms.size();
   c.npairs_all = nq * (int64_t)c.H;
-  c.resolve = !e->knobs.no_resolve && resolve_lds_bytes(c.Lc, e->max_M) <= kLdsBudget && c.npairs_all < 0x7FFFFFFF;
+  // The resolver's LDS block holds the query and a state per residue.  A call whose longest query does not fit keeps the
+  // resolver all the same: its main launches are sized for the lengths that keep their occupancy, longer queries' pairs go
+  // through the long-query pass (WH_NO_LONG_QUERY: no resolver for the whole call, as it was).
+  const bool fits = resolve_lds_bytes(c.Lc, e->max_M) <= kLdsBudget;
+  c.Lmain = fits || e->knobs.no_long_query ? c.Lc : resolve_main_cap(e->max_M);
+  c.resolve = !e->knobs.no_resolve && (fits || !e->knobs.no_long_query) && c.npairs_all < 0x7FFFFFFF;
   c.mixed = nq > 0 && total_residues > 0 && (double)max_len > 1.25 * (double)total_residues / (double)nq;
   c.wide_dense = getenv("WH_WIDE_DENSE"); c.wide_no_em_lds = getenv("WH_WIDE_NO_EM_LDS"); c.p2win_force = getenv("WH_P2WIN_FORCE");
   c.res_null2_gather = getenv("WH_RES_NULL2_GATHER"); c.res_no_lds_tables = getenv("WH_RES_NO_LDS_TABLES");
@@ -693,9 +711,10 @@ static int print_resolver_stats(const ScoreCall &c, const ResolveArgs &r, int n_
 }
 
 // what every resolver launch of a call shares: tables, queue, outputs, the layout of a wave's matrix slab
-static ResolveArgs resolve_args(const ScoreCall &c, const int32_t *rext, int64_t rext_stride) {
+// <Lc>: the launch's length cap (a pair of a longer query is listed for the long-query pass)
+static ResolveArgs resolve_args(const ScoreCall &c, const int32_t *rext, int64_t rext_stride, int Lc) {
   wh_ehmm *e = c.e;
-  const int Lc = c.Lc, Qmax = e->max_Q;
+  const int Qmax = e->max_Q;
   ResolveArgs r;
   memset(&r, 0, sizeof r);
   r.rext = rext; r.rext_stride = rext_stride;
@@ -721,14 +740,19 @@ static ResolveArgs resolve_args(const ScoreCall &c, const int32_t *rext, int64_t
 }
 
 // the big-region block of the counters (wh_launch.h: kBigAfterErr) in front of a resolver launch: counts zeroed, the list
-// the launch appends to (<cap> 0: none)
-static int big_region_block(const ScoreCall &c, int32_t *list, int cap) {
+// the launch appends to (<cap> 0: none); behind it the long-query block (kLongAfterErr): count and longest length zeroed,
+// capacity of <long_list> (0: none - the launch's length cap is the call's longest query)
+static int big_region_block(const ScoreCall &c, int32_t *list, int cap, int32_t *long_list = nullptr, int long_cap = 0) {
   int *blk = c.e->big_blk;                 // (lives in the handle: the copy needs no synchronisation)
-  for (int t = 0; t < 8; t++) blk[t] = 0;
+  for (int t = 0; t < 11; t++) blk[t] = 0;
   blk[4] = cap;
   memcpy(blk + 5, &list, sizeof list);
   static_assert(sizeof list == 2 * sizeof(int), "the list's address takes two ints");
-  HIPCHK(hipMemcpyAsync(c.e->counter(kSlotBigRegion), blk, 8 * sizeof(int), hipMemcpyHostToDevice, c.s));
+  blk[10] = long_cap;
+  c.e->long_blk = long_list;
+  static_assert(kSlotLongQuery == kSlotBigRegion + 8, "one copy for both blocks");
+  HIPCHK(hipMemcpyAsync(c.e->counter(kSlotBigRegion), blk, 11 * sizeof(int), hipMemcpyHostToDevice, c.s));
+  HIPCHK(hipMemcpyAsync(c.e->counter(kSlotLongQueryList), &c.e->long_blk, sizeof c.e->long_blk, hipMemcpyHostToDevice, c.s));
   return WH_OK;
 }
 
@@ -755,30 +779,49 @@ static BigRegionPlan plan_big_regions(int Lc, int max_M, const int counts[4]) {
 
 // <n_big> queue positions are listed in the first half of d_biglist; <counts> as read back with them.  The queue itself
 // (d_rrecs, <rext>) is the one of the launch that listed them.
-static int big_region_pass(const ScoreCall &c, const int counts_in[4], const int32_t *rext, int64_t rext_stride, int list_cap, int *rlaunches) {
+// <long_q>: the long-query pass.  The same loop with resolve_long_kernel: <counts_in> = (pairs, 0, 0, 0), the pairs listed in
+// d_longlist, the first launch with lists of the default sizes (a long pair with a big region is counted and listed there
+// like any other, and done again with longer lists); the length cap is the call's longest query, which a wave's LDS block
+// does not hold in this pass, so a workgroup runs several waves where the device has room for their slabs.
+static int big_region_pass(const ScoreCall &c, const int counts_in[4], const int32_t *rext, int64_t rext_stride, int list_cap, int *rlaunches, bool long_q = false) {
   wh_ehmm *e = c.e;
   hipStream_t s = c.s;
-  const int Lc = c.Lc;
+  const int Lc = long_q ? c.Lc : c.Lmain;
+  const char *what = long_q ? "long-query pass" : "big-region pass";
   int counts[4] = {counts_in[0], counts_in[1], counts_in[2], counts_in[3]};
-  e->last_big[0] += std::min(counts[0], list_cap);
-  const size_t rlds = resolve_lds_bytes(Lc, e->max_M);
+  if (!long_q) e->last_big[0] += std::min(counts[0], list_cap);
+  const bool relist = !e->knobs.no_big_region;      // (the long-query pass under WH_NO_BIG_REGION: such a pair keeps WH_FLAG_TRUNC)
+  if (long_q && relist && e->d_biglist.ensure(2 * sizeof(int32_t) * (size_t)list_cap)) return WH_ENOMEM;
+  const size_t rlds = long_q ? resolve_long_lds_bytes(e->max_M) : resolve_lds_bytes(Lc, e->max_M);
+  const int first_big = long_q ? 1 : 0;             // the first launch whose pairs are there for a region's lists
   for (int again = 0; counts[0] > 0; again++) {
     for (int t = 1; t < 4; t++) e->last_big[t] = std::max<int64_t>(e->last_big[t], counts[t]);
-    if (again == 2) { set_error("wh_score_dev: a region's lists (%d domains, %d segments, %d clusters) were too short twice", counts[1], counts[2], counts[3]); return WH_ERANGE; }
+    if (again == first_big + 2) { set_error("wh_score_dev: a region's lists (%d domains, %d segments, %d clusters) were too short twice", counts[1], counts[2], counts[3]); return WH_ERANGE; }
     const int n_big = std::min(counts[0], list_cap);
-    ResolveArgs r = resolve_args(c, rext, rext_stride);
-    const BigRegionPlan p = plan_big_regions(Lc, e->max_M, counts);
+    if (long_q && again == 1) e->last_big[0] += n_big;
+    ResolveArgs r = resolve_args(c, rext, rext_stride, Lc);
+    BigRegionPlan p = plan_big_regions(Lc, e->max_M, counts);
+    if (long_q) { p.seg_ints = resolve_long_seg_ints(Lc, e->max_M, p.dom_cap, p.seg_cap, p.clus_cap); r.long_query = 1; }
     r.dom_cap = p.dom_cap; r.seg_cap = p.seg_cap; r.clus_cap = p.clus_cap; r.seg_stride = p.seg_ints;
     r.lds_tables = 0;
     r.wave_lds_ints = (int)(rlds / 4);
-    const size_t lds_total = resolve_lds_header_bytes(0) + rlds;
     // one segment of mixed models in the order of the list, one slot per workgroup
-    int blocks = std::min(n_big, e->cu_count);
-    const size_t per_block = r.mx_stride * sizeof(double) + r.seg_stride * sizeof(int32_t);
-    blocks = clamp_blocks(blocks, per_block, e->d_rmx, e->max_M, Lc, "big-region pass");
+    const size_t per_wave = r.mx_stride * sizeof(double) + r.seg_stride * sizeof(int32_t);
+    int waves = 1;
+    if (long_q) {
+      waves = std::max(1, std::min(std::min(resolve_waves_per_cu(), (int)((kLdsBudget - resolve_lds_header_bytes(0)) / rlds)), n_big / e->cu_count));
+      if (c.res_waves > 0) waves = std::min(waves, c.res_waves);
+      size_t free_b = 0, total_b = 0;
+      if (waves > 1 && hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        while (waves > 1 && (double)waves * (double)per_wave > 0.7 * (double)(free_b + e->d_rmx.cap)) waves--;
+    }
+    const size_t lds_total = resolve_lds_header_bytes(0) + (size_t)waves * rlds;
+    int blocks = std::min((n_big + waves - 1) / waves, e->cu_count);
+    const size_t per_block = (size_t)waves * per_wave;
+    blocks = clamp_blocks(blocks, per_block, e->d_rmx, e->max_M, Lc, what);
     if (blocks < 0) return WH_ENOMEM;
-    if (e->d_rmx.ensure((size_t)blocks * r.mx_stride * sizeof(double)) || e->d_bigsegs.ensure((size_t)blocks * r.seg_stride * sizeof(int32_t))) {
-      set_error("big-region pass: %d workgroups x %zu bytes (lists of %d domains, %d segments, %d clusters) do not fit on the device", blocks, per_block, p.dom_cap, p.seg_cap, p.clus_cap);
+    if (e->d_rmx.ensure((size_t)blocks * waves * r.mx_stride * sizeof(double)) || e->d_bigsegs.ensure((size_t)blocks * waves * r.seg_stride * sizeof(int32_t))) {
+      set_error("%s: %d workgroups x %zu bytes (queries of up to %d residues, lists of %d domains, %d segments, %d clusters) do not fit on the device", what, blocks, per_block, Lc, p.dom_cap, p.seg_cap, p.clus_cap);
       return WH_ENOMEM;
     }
     r.mx = (double *)e->d_rmx.p; r.segs = (int32_t *)e->d_bigsegs.p;
@@ -788,24 +831,36 @@ static int big_region_pass(const ScoreCall &c, const int counts_in[4], const int
     int32_t *d_chunks = (int32_t *)e->d_rchunks.p;
     HIPCHK(hipMemcpyAsync(d_chunks, plan.data(), sizeof(int32_t) * plan.size(), hipMemcpyHostToDevice, s));
     r.chunks = d_chunks; r.n_chunks = 1; r.slots = d_chunks + 4; r.n_slots = blocks; r.cursors = d_chunks + 4 + blocks;
+    // the list this launch reads and the one it appends to: the halves of d_biglist in turn (the long-query pass starts from its own list)
     int32_t *lists = (int32_t *)e->d_biglist.p;
-    r.order = lists + (size_t)(again & 1) * list_cap;
+    r.order = long_q && again == 0 ? (const int32_t *)e->d_longlist.p : lists + (size_t)((again - first_big) & 1) * list_cap;
     HIPCHK(hipMemsetAsync(r.counter, 0, sizeof(int), s));
-    if (int rc = big_region_block(c, lists + (size_t)((again + 1) & 1) * list_cap, list_cap)) return rc;
+    if (int rc = big_region_block(c, relist ? lists + (size_t)((again - first_big + 1) & 1) * list_cap : nullptr, relist ? list_cap : 0)) return rc;
     HIPCHK(hipStreamSynchronize(s));     // <plan> is a local
-    if (e->knobs.trace) fprintf(stderr, "[wh] big-region pass: %d pairs, lists of %d domains per trace, %d segments, %d clusters: %d workgroups of one wave, %zu KB of lists + %zu MB of matrix per wave\n",
-                                n_big, p.dom_cap, p.seg_cap, p.clus_cap, blocks, r.seg_stride * 4 >> 10, r.mx_stride * 8 >> 20);
+    if (e->knobs.trace) fprintf(stderr, "[wh] %s: %d pairs, queries of up to %d residues, lists of %d domains per trace, %d segments, %d clusters: %d workgroups of %d wave(s), lds %zu, %zu KB of lists + %zu MB of matrix per wave\n",
+                                what, n_big, Lc, p.dom_cap, p.seg_cap, p.clus_cap, blocks, waves, lds_total, r.seg_stride * 4 >> 10, r.mx_stride * 8 >> 20);
     const auto t0 = std::chrono::steady_clock::now();
-    hipError_t err = launch_resolve(r, blocks, 1, lds_total, s);
-    if (err != hipSuccess) { set_error("big-region resolve kernel launch failed: %s", hipGetErrorString(err)); return WH_EHIP; }
+    hipError_t err = launch_resolve(r, blocks, waves, lds_total, s);
+    if (err != hipSuccess) { set_error("%s: resolve kernel launch failed: %s", what, hipGetErrorString(err)); return WH_EHIP; }
     (*rlaunches)++;
     HIPCHK(hipMemcpyAsync(counts, e->counter(kSlotBigRegion), sizeof counts, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     for (int t = 1; t < 4; t++) e->last_big[t] = std::max<int64_t>(e->last_big[t], counts[t]);
-    if (e->knobs.trace) fprintf(stderr, "[wh] big-region pass: %.1f ms (host clock around launch + synchronize)%s\n",
-                                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), counts[0] > 0 ? "; lists still too short, once more" : "");
+    if (e->knobs.trace) fprintf(stderr, "[wh] %s: %.1f ms (host clock around launch + synchronize)%s\n", what,
+                                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), counts[0] > 0 ? "; lists too short, once more" : "");
   }
   return WH_OK;
+}
+
+// ---- the long-query pass.  The main resolver launches of a call are sized for the length cap c.Lmain; a launch lists the
+// pairs of longer queries (<n_long> of them in d_longlist, the longest <longest> residues) instead of resolving them, and
+// this pass runs them with the call's longest query as the cap and the per-residue arrays in HBM (big_region_pass above).
+static int long_query_pass(const ScoreCall &c, int n_long, int longest, const int32_t *rext, int64_t rext_stride, int list_cap, int *rlaunches) {
+  wh_ehmm *e = c.e;
+  const int counts[4] = {std::min(n_long, list_cap), 0, 0, 0};
+  e->last_long[0] += counts[0];
+  e->last_long[1] = std::max<int64_t>(e->last_long[1], longest);
+  return big_region_pass(c, counts, rext, rext_stride, list_cap, rlaunches, true);
 }
 
 // one resolver launch (wh_resolve.hip, one wavefront per queued pair) over the first <n_multi> records of the queue;
@@ -814,11 +869,14 @@ static int big_region_pass(const ScoreCall &c, const int counts_in[4], const int
 static int resolve_queue(const ScoreCall &c, int n_multi, const int32_t *rext, int64_t rext_stride, int *rlaunches) {
   wh_ehmm *e = c.e;
   hipStream_t s = c.s;
-  const int Lc = c.Lc;
+  const int Lc = c.Lmain;
   const size_t rlds = resolve_lds_bytes(Lc, e->max_M);
-  ResolveArgs r = resolve_args(c, rext, rext_stride);
+  ResolveArgs r = resolve_args(c, rext, rext_stride, Lc);
+  const bool long_q = c.Lmain < c.Lc;      // pairs of queries beyond the cap are listed in d_longlist (long_query_pass)
   if (!e->knobs.no_big_region && e->d_biglist.ensure(2 * sizeof(int32_t) * (size_t)n_multi)) return WH_ENOMEM;
-  if (int rc = big_region_block(c, e->knobs.no_big_region ? nullptr : (int32_t *)e->d_biglist.p, e->knobs.no_big_region ? 0 : n_multi)) return rc;
+  if (long_q && e->d_longlist.ensure(sizeof(int32_t) * (size_t)n_multi)) return WH_ENOMEM;
+  if (int rc = big_region_block(c, e->knobs.no_big_region ? nullptr : (int32_t *)e->d_biglist.p, e->knobs.no_big_region ? 0 : n_multi,
+                                long_q ? (int32_t *)e->d_longlist.p : nullptr, long_q ? n_multi : 0)) return rc;
   if (int rc = stats_begin(c, 256, 16, &r.stats)) return rc;
   if (r.stats) HIPCHK(hipStreamSynchronize(s));
   // ---- launch geometry: ONE workgroup of up to eight waves per CU.  Models of up to 16 cells per lane get their
@@ -916,11 +974,14 @@ static int long_list_pass(const ScoreCall &c, int n_multi, bool long_list, int *
     hipError_t terr = launch_trunc_list(c.d_flags, c.npairs_all, d_tcount, (int64_t *)e->d_tlist.p, list_cap, s);
     if (terr != hipSuccess) { set_error("flag scan launch failed: %s", hipGetErrorString(terr)); return WH_EHIP; }
   }
-  int back[5] = {0, 0, 0, 0, 0};                  // long-list count | big-region count and the three largest list lengths
-  HIPCHK(hipMemcpyAsync(back, d_tcount, (n_multi > 0 ? 5 : 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+  // long-list count | big-region count and the three largest list lengths (then the list's capacity and address) | long-query count, longest query
+  int back[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  static_assert(kSlotBigRegion == kSlotLongList + 1 && kSlotLongQuery == kSlotLongList + 9, "one read-back for the three");
+  HIPCHK(hipMemcpyAsync(back, d_tcount, (n_multi > 0 ? 11 : 1) * sizeof(int), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  // the main launch's big regions first: its queue is still in place (the rounds below overwrite it)
+  // the main launch's big regions and long queries first: its queue is still in place (the rounds below overwrite it)
   if (back[1] > 0 && !e->knobs.no_big_region) if (int rc = big_region_pass(c, back + 1, nullptr, 0, n_multi, rlaunches)) return rc;
+  if (back[9] > 0) if (int rc = long_query_pass(c, back[9], back[10], nullptr, 0, n_multi, rlaunches)) return rc;
   const int n_trunc = std::min(back[0], list_cap);          // (beyond four million such pairs in one call the rest stay flagged)
   if (n_trunc <= 0) return WH_OK;
   // a region is at least two rows long (the row that triggers it and a later one that ends it)
@@ -953,12 +1014,14 @@ static int long_list_pass(const ScoreCall &c, int n_multi, bool long_list, int *
     HIPCHK(hipStreamSynchronize(s));
     if (int rc = resolve_queue(c, n_round, (const int32_t *)e->d_rext.p, rext_stride, rlaunches)) return rc;
     e->last_long_list += n_round;
-    if (!e->knobs.no_big_region) {
-      // (a pair with many regions can have a big one among them; this read-back is paid by calls that have such pairs only)
-      int big[4] = {0, 0, 0, 0};
+    if (!e->knobs.no_big_region || c.Lmain < c.Lc) {
+      // (a pair with many regions can have a big one among them, or a query beyond the main launch's cap; this read-back is
+      // paid by calls that have such pairs only)
+      int big[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       HIPCHK(hipMemcpyAsync(big, e->counter(kSlotBigRegion), sizeof big, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
-      if (big[0] > 0) if (int rc = big_region_pass(c, big, (const int32_t *)e->d_rext.p, rext_stride, n_round, rlaunches)) return rc;
+      if (big[0] > 0 && !e->knobs.no_big_region) if (int rc = big_region_pass(c, big, (const int32_t *)e->d_rext.p, rext_stride, n_round, rlaunches)) return rc;
+      if (big[8] > 0) if (int rc = long_query_pass(c, big[8], big[9], (const int32_t *)e->d_rext.p, rext_stride, n_round, rlaunches)) return rc;
     }
   }
   return WH_OK;
@@ -991,8 +1054,9 @@ static int resolver_stage(const ScoreCall &c, bool *overflow, int *rlaunches) {
   if (n_multi > 0) if (int rc = resolve_queue(c, n_multi, nullptr, 0, rlaunches)) return rc;
   e->last_long_list = 0;
   for (int64_t &v : e->last_big) v = 0;
+  e->last_long[0] = e->last_long[1] = 0;
   const bool long_list = c.resolve && generic_lds_bytes(c.Lc) <= kLdsBudget && !e->knobs.no_long_list;
-  if (long_list || (n_multi > 0 && !e->knobs.no_big_region)) return long_list_pass(c, n_multi, long_list, rlaunches);
+  if (long_list || (n_multi > 0 && (!e->knobs.no_big_region || c.Lmain < c.Lc))) return long_list_pass(c, n_multi, long_list, rlaunches);
   return WH_OK;
 }
 
@@ -1073,6 +1137,7 @@ extern "C" int wh_score_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t
   e->last_queue_reruns = 0;
   e->last_long_list = 0;
   for (int64_t &v : e->last_big) v = 0;
+  e->last_long[0] = e->last_long[1] = 0;
   e->rq_floor = 0;
   e->st_off = false;
   // (diagnostics only: a pair the kernels leave early - an empty query, one beyond the length cap - has a record of zeros)

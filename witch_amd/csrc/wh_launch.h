@@ -168,9 +168,16 @@ struct ResolveArgs {
   // capacity of the list of their queue positions (0: none - the pair keeps WH_FLAG_TRUNC, WH_NO_BIG_REGION), [5..6] its address (8-byte aligned).
   int dom_cap, clus_cap;       // > 0: the big-region pass (resolve_big_kernel) - every list of a region in the wave's HBM block, seg_cap segments,
                                // seg_stride >= resolve_big_seg_ints(...)
+  // A pair whose query is longer than <Lcap> is reported in three ints kLongAfterErr behind <err>: [0] such pairs, [1] the longest
+  // query among them, [2] capacity of the list of their queue positions (0: none - the pair keeps WH_FLAG_TRUNC); the list's
+  // address (8-byte aligned) sits kLongListAfterErr behind <err>.
+  int long_query;              // 1 (with dom_cap > 0): the long-query pass (resolve_long_kernel) - residues and emitting states in the wave's HBM
+                               // block as well, seg_stride >= resolve_long_seg_ints(...), wave_lds_ints = resolve_long_lds_bytes(Mmax) / 4
 };
 constexpr int kRextInts = 5;
 constexpr int kBigAfterErr = 3;
+constexpr int kLongAfterErr = 11;
+constexpr int kLongListAfterErr = 30;
 hipError_t launch_resolve(const ResolveArgs &a, int blocks, int waves, size_t lds, hipStream_t s);
 size_t resolve_lds_header_bytes(int Qt);
 // cost estimate of every queued pair (cells of its multidomain regions) for the longest-first order
@@ -181,6 +188,8 @@ int resolve_seg_cap();
 int resolve_waves_per_cu();
 size_t resolve_seg_ints(int Lcap, int Mmax);
 size_t resolve_big_seg_ints(int Lcap, int Mmax, int dom_cap, int seg_cap, int clus_cap);
+size_t resolve_long_seg_ints(int Lcap, int Mmax, int dom_cap, int seg_cap, int clus_cap);
+size_t resolve_long_lds_bytes(int Mmax);
 int resolve_dom_max();
 int resolve_clus_max();
 size_t resolve_dcache_doubles();

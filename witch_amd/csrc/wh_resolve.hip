@@ -115,9 +115,20 @@ int resolve_seg_cap() { return kSegCap; }
 // ... of the big-region pass: six segment arrays and two 32-bit vertex stacks of <seg_cap> entries, the histogram and the
 // per-residue arrays as above, <dom_cap> domains of a trace with their null2 vectors, <clus_cap> clusters (start, end,
 // posterior, a byte of the domination set)
-size_t resolve_big_seg_ints(int Lcap, int Mmax, int dom_cap, int seg_cap, int clus_cap) {
+__host__ __device__ inline size_t big_seg_ints(int Lcap, int Mmax, int dom_cap, int seg_cap, int clus_cap) {
   return (size_t)8 * seg_cap + (size_t)(Lcap > Mmax ? Lcap : Mmax) + 8 + 2 * ((size_t)Lcap + 8) + (size_t)(4 + 32) * dom_cap + (size_t)3 * clus_cap + ((size_t)clus_cap + 3) / 4 + 2;
 }
+// ... of the long-query pass (a query beyond the length cap of the main launches): the big-region block, then the query's
+// residues (a byte each) and the emitting state of every residue (16 or 32 bits) - what the other launches keep in LDS
+__host__ __device__ inline size_t resolve_long_seq_ints(int Lcap) { return (((size_t)Lcap + 8 + 3) / 4 + 3) & ~(size_t)3; }
+size_t resolve_long_seg_ints(int Lcap, int Mmax, int dom_cap, int seg_cap, int clus_cap) {
+  const size_t Lp = (size_t)((Lcap + 4) & ~1);
+  const size_t n = ((big_seg_ints(Lcap, Mmax, dom_cap, seg_cap, clus_cap) + 3) & ~(size_t)3) + resolve_long_seq_ints(Lcap) + (resolve_stk32(Mmax) ? Lp : Lp / 2) + 2;
+  return (n + 3) & ~(size_t)3;
+}
+// LDS per wave of that pass: the block of a launch without residues and states (it does not depend on the query length)
+size_t resolve_long_lds_bytes(int Mmax) { return resolve_lds_ints(0, Mmax) * 4; }
+size_t resolve_big_seg_ints(int Lcap, int Mmax, int dom_cap, int seg_cap, int clus_cap) { return big_seg_ints(Lcap, Mmax, dom_cap, seg_cap, clus_cap); }
 int resolve_dom_max() { return kDomMax; }
 int resolve_clus_max() { return kClusMax; }
 // the walk's cache of threshold lines: 2^kDcBits lines of 64 x 16 bytes + their 8-byte tags, in doubles
@@ -156,29 +167,31 @@ __device__ __forceinline__ unsigned line_check_bits(unsigned long long key, unsi
 // those pairs again with the same code and the lists in the wave's HBM block, sized from the counts (a.dom_cap,
 // a.seg_cap, a.clus_cap): what differs is where a list lives and how lane 0's stores reach the other lanes
 // (wave_barrier for LDS, wave_mem_sync for HBM), as the clustering's vertex stacks do it.
-template <bool BIG>
+//
+// <LONGQ> (with BIG): the long-query pass (wh_host_score.hip: long_query_pass).  The main launches are sized for a length cap
+// (a.Lcap) that keeps their occupancy; a longer query's pair is listed (the counters' long-query block) and done again here,
+// where the two per-residue arrays of the LDS block - the residues and their emitting states - live in the wave's HBM block
+// too, behind the big-region lists: lane 0 (the leading lanes of a run) writes with ordinary stores, every lane reads after
+// wave_mem_sync.  The LDS block of this instantiation does not depend on the query length.
+template <bool BIG, bool LONGQ = false>
 __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
+  static_assert(BIG || !LONGQ, "the long-query pass keeps every list in HBM");
   extern __shared__ __attribute__((aligned(16))) int lds_all[];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwaves = blockDim.x >> 6;
   volatile int *s_hdr = lds_all;                                  // [0] chunk of the workgroup, [1] cursor inside it
   double *tabL = reinterpret_cast<double *>(lds_all + 4);         // staged transition arrays (a.lds_tables > 0)
   int *lds_raw = lds_all + 4 + (a.lds_tables > 0 ? gNARR * a.lds_tables * 64 * 2 : 0) + (size_t)wave * a.wave_lds_ints;
-  const int Lp = (a.Lcap + 4) & ~1;
-  uint8_t *seq = reinterpret_cast<uint8_t *>(lds_raw);
-  int *uni = lds_raw + ((((a.Lcap + 8) / 4 + 2) + 1) & ~1);
-  short *stk = reinterpret_cast<short *>(uni + (4 + 32) * kDomMax);  // emitting state of each residue: +k match, -k insert
-  int *stk32 = reinterpret_cast<int *>(stk);                      // ... the same in 32 bits when a node index does not fit 16
-  const bool wide_stk = resolve_stk32(a.Mmax);
-  auto stk_get = [&](int p) -> int { return wide_stk ? stk32[p] : (int)stk[p]; };
-  auto stk_set = [&](int p, int v) { if (wide_stk) stk32[p] = v; else stk[p] = (short)v; };
+  const int Llds = LONGQ ? 0 : a.Lcap;                            // query length the LDS block is laid out for
+  const int Lp = (Llds + 4) & ~1;
+  int *uni = lds_raw + ((((Llds + 8) / 4 + 2) + 1) & ~1);
   const int SEGCAP = a.seg_cap;
   const int DOMCAP = BIG ? a.dom_cap : kDomMax, CLCAP = BIG ? a.clus_cap : kClusMax;
   // a list written by lane 0 is handed to the other lanes: LDS is ordered by its own pipeline, HBM by hand
   auto list_sync = []() { if constexpr (BIG) wave_mem_sync(); else __builtin_amdgcn_wave_barrier(); };
   unsigned short *s_a = reinterpret_cast<unsigned short *>(uni); // clustering (after the traces): Easel's vertex stacks, same block
   unsigned short *s_b = s_a + kSegLds;
-  double *bins = reinterpret_cast<double *>(uni + resolve_uni_ints(a.Lcap, a.Mmax));   // 64 float64 bins of the E-state row pass (8-byte aligned)
+  double *bins = reinterpret_cast<double *>(uni + resolve_uni_ints(Llds, a.Mmax));   // 64 float64 bins of the E-state row pass (8-byte aligned)
   int *misc = reinterpret_cast<int *>(bins + 64);                // 4 x kEnvMax + 3 x kClusMax ints: envelope list of the pair (detail), cluster list of a region
   unsigned long long *hprev = reinterpret_cast<unsigned long long *>(misc + 4 * kEnvMax + 3 * kClusMax + 16), *hcur = hprev + kHist;
   // the big-region block of the handle's counters sits kBigAfterErr ints behind a.err (wh_host.h: kSlotBigRegion): pairs listed,
@@ -188,7 +201,16 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
   int *pair_pos = misc + 4 * kEnvMax + 3 * kClusMax;             // queue position of the current pair (first of the 16 spare ints)
   (void)Lp;
   const size_t wslot = (size_t)blockIdx.x * nwaves + wave;        // this wave's slab / segment arrays
-  int32_t *sg = a.segs + wslot * a.seg_stride;      // per wave in HBM: 6 arrays of SEGCAP ints, the vertex stacks of a large region, the histogram
+  int32_t *sg = a.segs + wslot * a.seg_stride;
+  // residues of the pair and the emitting state of each residue (+k match, -k insert; 32 bits when a node index does not fit 16):
+  // in LDS, or (LONGQ) at the end of the wave's HBM block
+  int32_t *lq = LONGQ ? sg + ((big_seg_ints(a.Lcap, a.Mmax, a.dom_cap, a.seg_cap, a.clus_cap) + 3) & ~(size_t)3) : nullptr;
+  uint8_t *seq = LONGQ ? reinterpret_cast<uint8_t *>(lq) : reinterpret_cast<uint8_t *>(lds_raw);
+  short *stk = LONGQ ? reinterpret_cast<short *>(lq + resolve_long_seq_ints(a.Lcap)) : reinterpret_cast<short *>(uni + (4 + 32) * kDomMax);
+  int *stk32 = reinterpret_cast<int *>(stk);
+  const bool wide_stk = resolve_stk32(a.Mmax);
+  auto stk_get = [&](int p) -> int { return wide_stk ? stk32[p] : (int)stk[p]; };
+  auto stk_set = [&](int p, int v) { if (wide_stk) stk32[p] = v; else stk[p] = (short)v; };      // per wave in HBM: 6 arrays of SEGCAP ints, the vertex stacks of a large region, the histogram
   int32_t *s_idx = sg, *s_i = sg + SEGCAP, *s_j = sg + 2 * SEGCAP, *s_k = sg + 3 * SEGCAP, *s_m = sg + 4 * SEGCAP;
   int32_t *s_as = sg + 5 * SEGCAP;
   unsigned short *h_a = reinterpret_cast<unsigned short *>(sg + 6 * SEGCAP), *h_b = h_a + SEGCAP;   // vertex stacks of a region of more than kSegLds segments
@@ -289,9 +311,27 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
     const int64_t off = a.offsets[rec.q];
     const int L = (int)(a.offsets[rec.q + 1] - off);
     const size_t out = (size_t)rec.q * a.H + rec.h;
+    if (L > a.Lcap) {
+      // a query beyond this launch's length cap: nothing of it fits the wave's blocks.  Its queue position goes to the list of
+      // the long-query pass (the counters' long-query block, kLongAfterErr ints behind a.err: pairs, longest query, capacity;
+      // the list's address kLongListAfterErr behind it).  Without a list, or when the long-list pass scores the pair again
+      // anyway (its region list was too short: main launch only), the pair is flagged.
+      if (lane == 0) {
+        int *lq_out = a.err + kLongAfterErr;
+        const int fl = rec.flags | (rec.multi_mask ? WH_FLAG_MULTI : 0);
+        const int lq_cap = __builtin_nontemporal_load(lq_out + 2);
+        if (lq_cap > 0 && (a.rext || !(fl & WH_FLAG_TRUNC))) {
+          int32_t *lq_list = *reinterpret_cast<int32_t *const *>(a.err + kLongListAfterErr);
+          const int slot = atomicAdd(lq_out, 1);
+          if (slot < lq_cap) lq_list[slot] = ridx;
+          atomicMax(lq_out + 1, L);
+        } else a.flags[out] = (uint8_t)(fl | WH_FLAG_TRUNC);
+      }
+      continue;
+    }
     for (int t = lane; t < L; t += 64) { const int r = a.residues[off + t]; seq[t] = (uint8_t)(r < a.Kp ? r : a.Kp - 1); }
     for (int t = lane; t <= L + 1; t += 64) n2sc[t] = 0.f;
-    __builtin_amdgcn_wave_barrier();
+    if constexpr (LONGQ) wave_mem_sync(); else __builtin_amdgcn_wave_barrier();
     const GLen cm = glen_config(L, true), cu = glen_config(L, false);
     int flags = rec.flags | (rec.multi_mask ? WH_FLAG_MULTI : 0);     // (the any-size front end queues every pair with a region)
     // envelope list of the pair
@@ -315,7 +355,7 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
       // (values that steer the wave-uniform walk are made provably uniform: the walk then compiles to SALU code)
       const int ireg = __builtin_amdgcn_readfirstlane(xl ? xl[kRextInts * e] : rec.ri[e]);
       const int jreg = __builtin_amdgcn_readfirstlane(xl ? xl[kRextInts * e + 1] : rec.rj[e]), Lr = jreg - ireg + 1;
-      if (ireg < 1 || jreg > L || Lr < 1 || L > a.Lcap) { flags |= WH_FLAG_TRUNC; continue; }     // never true for a well-formed record
+      if (ireg < 1 || jreg > L || Lr < 1) { flags |= WH_FLAG_TRUNC; continue; }     // never true for a well-formed record
       const bool multi_reg = xl ? __builtin_amdgcn_readfirstlane(xl[kRextInts * e + 4]) != 0 : ((rec.multi_mask >> (e & 31)) & 1) != 0;
       if (!multi_reg) {
         // single-domain region: envelope = region, scored by the scoring kernel (A.5)
@@ -1041,6 +1081,8 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
 __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_kernel(ResolveArgs a) { resolve_body<false>(a); }
 // the big-region pass: one wave per workgroup, every list of a region in the wave's HBM block
 __global__ __launch_bounds__(64 * kResMaxWaves) void resolve_big_kernel(ResolveArgs a) { resolve_body<true>(a); }
+// the long-query pass: as the big-region pass, the residues and their emitting states in the wave's HBM block too
+__global__ __launch_bounds__(64 * kResMaxWaves) void resolve_long_kernel(ResolveArgs a) { resolve_body<true, true>(a); }
 
 // One thread per queued pair: the cells of its multidomain regions (region length x model length), the
 // quantity the Forward fill, the walk and the envelope rescoring all scale with; and its model.
@@ -1067,13 +1109,18 @@ hipError_t launch_resolve_keys(const ResolveRec *recs, int n, const DevHMM *hmms
 
 hipError_t launch_resolve(const ResolveArgs &a, int blocks, int waves, size_t lds, hipStream_t s) {
   if (waves < 1 || waves > kResMaxWaves) return hipErrorInvalidValue;
-  const bool big = a.dom_cap > 0;
-  if (big && (a.dom_cap < kDomMax || a.seg_cap < kSegCap || a.clus_cap < kClusMax || a.seg_stride < resolve_big_seg_ints(a.Lcap, a.Mmax, a.dom_cap, a.seg_cap, a.clus_cap)))
+  const bool big = a.dom_cap > 0, longq = a.long_query != 0;
+  if (longq && !big) return hipErrorInvalidValue;
+  if (big && (a.dom_cap < kDomMax || a.seg_cap < kSegCap || a.clus_cap < kClusMax ||
+              a.seg_stride < (longq ? resolve_long_seg_ints(a.Lcap, a.Mmax, a.dom_cap, a.seg_cap, a.clus_cap) : resolve_big_seg_ints(a.Lcap, a.Mmax, a.dom_cap, a.seg_cap, a.clus_cap))))
     return hipErrorInvalidValue;
-  const void *fn = big ? reinterpret_cast<const void *>(&resolve_big_kernel) : reinterpret_cast<const void *>(&resolve_kernel);
+  // (the LDS block must be the one the instantiation lays out: the long-query pass's does not hold the query)
+  if ((size_t)a.wave_lds_ints * 4 != (longq ? resolve_long_lds_bytes(a.Mmax) : resolve_lds_bytes(a.Lcap, a.Mmax))) return hipErrorInvalidValue;
+  const void *fn = longq ? reinterpret_cast<const void *>(&resolve_long_kernel) : big ? reinterpret_cast<const void *>(&resolve_big_kernel) : reinterpret_cast<const void *>(&resolve_kernel);
   hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
-  if (big) hipLaunchKernelGGL(resolve_big_kernel, dim3(blocks), dim3(64 * waves), lds, s, a);
+  if (longq) hipLaunchKernelGGL(resolve_long_kernel, dim3(blocks), dim3(64 * waves), lds, s, a);
+  else if (big) hipLaunchKernelGGL(resolve_big_kernel, dim3(blocks), dim3(64 * waves), lds, s, a);
   else hipLaunchKernelGGL(resolve_kernel, dim3(blocks), dim3(64 * waves), lds, s, a);
   return hipGetLastError();
 }

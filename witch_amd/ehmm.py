@@ -139,6 +139,14 @@ class EHMM:
         check(lib().wh_last_region_overflow(self._h, o4.ctypes.data), "wh_last_region_overflow")
         return {"pairs": int(o4[0]), "max_domains": int(o4[1]), "max_segments": int(o4[2]), "max_clusters": int(o4[3])}
 
+    def last_long_queries(self):
+        """The long-query pass of the last score call: (pairs it scored again because their query is longer than the length
+        cap of the resolver's main launches, the longest query among them); (0, 0) when every query of the call fitted
+        the resolver's LDS block.  include/witch_hip.h: wh_last_long_query_pairs."""
+        o2 = np.zeros(2, dtype=np.int64)
+        check(lib().wh_last_long_query_pairs(self._h, o2.ctypes.data), "wh_last_long_query_pairs")
+        return int(o2[0]), int(o2[1])
+
     def set_path_buffer(self, paths_t):
         """Registers a CUDA uint8 tensor of nq x H bytes that later score calls fill with WH_PATH_* bits per pair
         (staged launches only; None switches it off).  The caller keeps the tensor alive (include/witch_hip.h)."""

@@ -62,6 +62,7 @@ class QueryAlignmentEngine:
         self.truncated_pairs = []     # (taxon, hmm label) with WH_FLAG_TRUNC
         self.long_list_pairs = 0      # pairs with more regions than a scoring kernel lists, scored in full by the long-list pass
         self.big_region_pairs = 0     # pairs with a region beyond the resolver's fixed lists, scored in full by the big-region pass
+        self.long_query_pairs = 0     # pairs of queries beyond the resolver's LDS block, resolved by the long-query pass
         self.unaligned_pairs = []     # (taxon, hmm label) the alignment stage returned unaligned
         self.query_text = None        # uint8: the local queries' characters (upper-cased on read), concatenated like query_offsets
         self.device = 0
@@ -146,6 +147,7 @@ class QueryAlignmentEngine:
             deci, flags = e.score(cres, coffs)
             self.long_list_pairs += e.last_long_list_pairs()
             self.big_region_pairs += e.last_region_overflow()["pairs"]
+            self.long_query_pairs += e.last_long_queries()[0]
             if multidomain_policy == "drop":
                 drop = (flags & 2) != 0
                 flags = np.where(drop, flags & ~np.uint8(1), flags).astype(np.uint8)
