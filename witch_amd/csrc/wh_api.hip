@@ -1,6 +1,6 @@
 // C ABI of libwitch_hip.so (declared in include/witch_hip.h): handle management, options, getters of the last call's
-// figures, the host-pointer entry points, top-k, consensus and the final merge.  wh_score_dev is in wh_host_score.hip,
-// wh_align_dev in wh_host_align.hip; what the three share is in wh_host.h.
+// figures, the host-pointer entry points, top-k, consensus and the final merge.  wh_score_dev is in wh_host_score.hip
+// (its resolver stage in wh_host_resolve.hip), wh_align_dev in wh_host_align.hip; what they share is in wh_host.h.
 #include <atomic>
 #include <chrono>
 #include <memory>

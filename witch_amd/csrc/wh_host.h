@@ -1,5 +1,6 @@
 // Internal header of the host side of libwitch_hip.so: what wh_api.hip (handles, options, getters, host-pointer entry
-// points), wh_host_score.hip (wh_score_dev) and wh_host_align.hip (wh_align_dev) share.  No kernel file includes it.
+// points), wh_host_score.hip (wh_score_dev), wh_host_resolve.hip (its resolver stage) and wh_host_align.hip (wh_align_dev)
+// share.  No kernel file includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -79,7 +80,7 @@ struct Knobs {
 };
 
 // ---- d_counter: 256 ints in HBM, zeroed at load.  Every owner of a slot or range, in one place: the kernels and the
-// wh_last_* getters depend on these numbers.  [60..62], [68..79], [89..95], [124..127], [144..145], [147], [178..255]
+// wh_last_* getters depend on these numbers.  [60..62], [68..79], [89..95], [124..127], [144..159], [176..177], [192..255]
 // are free.
 enum CounterSlot {
   kSlotLaunch0 = 0,         // [0..59] work-queue heads of the launches of ONE call, in launch order: the one-wave scoring
@@ -96,23 +97,20 @@ enum CounterSlot {
   kSlotAlignCycles = 100,   //   [100..107] four 64-bit cycle counters (AlignArgs::wcyc)
   kSlotScorePath = 128,     // [128..143] eight 64-bit counters of the last scoring call: six paths (wh_last_score_paths),
   kScorePathInts = 16,      //   bytes of Forward rows stored, spare (wh_last_score_counters)
-  kSlotResolveErr = 146,    // queue records the resolver found in a segment of another model (never, for a well-formed segment list)
-  kSlotLongList = 148,      // pairs flagged WH_FLAG_TRUNC after the resolver (long-list pass)
-  kSlotBigRegion = 149,     // [149..156] pairs with a region beyond the resolver's lists, the largest counts (read with 148), capacity and address of their list (wh_launch.h: kBigAfterErr)
-  kSlotLongQuery = 157,     // [157..159] pairs whose query is beyond a resolver launch's length cap, the longest such query (read with 148), capacity of their list (wh_launch.h: kLongAfterErr)
   kSlotWideScore = 160,     // [160..175] work-queue heads of the wide scoring launches, one per (cells per lane, waves) class
   kWideScoreClasses = 16,   //   (13 exist: 12 x 5..8, 16 x 7..8, 24 x 6..8, 48 x 5..8; WH_FORCE_WIDE adds smaller workgroups of one of them)
-  kSlotLongQueryList = 176, // [176..177] address of that list (wh_launch.h: kLongListAfterErr)
+  kSlotResolveFeedback = 178, // [178..191] what the resolver launches report and the lists they append to (wh_launch.h: ResolveFeedback)
+  kResolveFeedbackInts = 14,
   kCounterInts = 256
 };
 static_assert(kSlotLaunch0 + kMaxLaunches <= kSlotConsensus && kSlotConsensus < kSlotResolveCount && kSlotResolveWork == kSlotResolveCount + 1 &&
               kSlotResolveWork < kSlotGenericFront && kSlotGenericFront < kSlotGenericAlign && kSlotGenericAlign < kSlotWideAlign, "d_counter slots overlap");
 static_assert(kSlotWideAlign + kWideAlignClasses <= kSlotAlignStat && kSlotAlignCycles >= kSlotAlignStat && kSlotAlignCycles + 8 <= kSlotAlignStat + kAlignStatInts &&
               kSlotAlignCycles % 2 == 0 && kSlotAlignStat + kAlignStatInts <= kSlotScorePath && kSlotScorePath % 2 == 0, "d_counter slots overlap");
-static_assert(kSlotScorePath + kScorePathInts <= kSlotResolveErr && kSlotResolveErr < kSlotLongList && kSlotBigRegion == kSlotLongList + 1 && kSlotBigRegion + 8 <= kSlotWideScore && kSlotBigRegion == kSlotResolveErr + kBigAfterErr && (kSlotBigRegion + 5) % 2 == 0 &&
-              kSlotWideScore + kWideScoreClasses <= kSlotLongQueryList && kSlotLongQueryList + 2 <= kCounterInts, "d_counter slots overlap or leave the buffer");
-static_assert(kSlotLongQuery == kSlotBigRegion + 8 && kSlotLongQuery + 3 <= kSlotWideScore && kSlotLongQuery == kSlotResolveErr + kLongAfterErr &&
-              kSlotLongQueryList == kSlotResolveErr + kLongListAfterErr && kSlotLongQueryList % 2 == 0, "d_counter slots overlap");
+static_assert(kSlotScorePath + kScorePathInts <= kSlotWideScore && kSlotWideScore + kWideScoreClasses <= kSlotResolveFeedback &&
+              kSlotResolveFeedback + kResolveFeedbackInts <= kCounterInts && kResolveFeedbackInts * sizeof(int) == sizeof(ResolveFeedback) &&
+              (kSlotResolveFeedback * sizeof(int) + offsetof(ResolveFeedback, big_list)) % 8 == 0 && (kSlotResolveFeedback * sizeof(int) + offsetof(ResolveFeedback, long_list)) % 8 == 0,
+              "d_counter slots overlap or leave the buffer, the resolver's feedback does not fill its range, or a list's address is not 8-byte aligned");
 
 struct wh_ehmm {
   Knobs knobs;
@@ -136,8 +134,7 @@ struct wh_ehmm {
   int64_t last_long_list = 0;               // ... of them, pairs of the long-list pass (more than WH_MAX_ENVELOPES regions)
   DevBuf d_tlist, d_rext;                   // long-list pass: pair positions, their region lists
   int64_t last_big[4] = {0, 0, 0, 0};       // big-region pass of the last wh_score call: pairs redone, most domains of a trace, segments, clusters of a region
-  int big_blk[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // ... host copy of the counters' big-region and long-query blocks as uploaded in front of a resolver launch
-  int32_t *long_blk = nullptr;              // ... and of the long-query list's address
+  ResolveFeedback feedback = {};            // host copy of the resolver's feedback as uploaded in front of a launch (here: the async copy needs no synchronisation)
   DevBuf d_biglist, d_bigsegs;              // ... queue positions of its pairs (two halves: read / written by a launch), its waves' list blocks
   int64_t last_long[2] = {0, 0};            // long-query pass of the last wh_score call: pairs redone, the longest query among them
   DevBuf d_longlist;                        // ... queue positions of its pairs
@@ -172,6 +169,7 @@ struct wh_ehmm {
   std::vector<int> cls_q, cls_kind;
   int cls_n = 0;
   int *counter(int slot) const { return (int *)d_counter.p + slot; }      // a slot of the table above
+  ResolveFeedback *d_feedback() const { return (ResolveFeedback *)counter(kSlotResolveFeedback); }
 };
 
 // one event per scoring launch (timing mode only); events are created once and reused
@@ -248,4 +246,81 @@ static inline int clamp_blocks(int blocks, size_t per_block, const DevBuf &have,
   const size_t budget = (size_t)((double)(free_b + have.cap) * 0.7);
   const size_t fit = budget / per_block;
   return (int)std::max<size_t>(1, std::min<size_t>((size_t)blocks, fit));
+}
+
+// ---- wh_score_dev: what wh_host_score.hip and wh_host_resolve.hip share
+// One scoring call: what the stages of a pass share.  The environment switches are per CALL, not per handle (tests flip
+// them between two calls on one handle), and read once, so that the admission check and the launches cannot disagree.
+struct ScoreCall {
+  wh_ehmm *e;
+  hipStream_t s;
+  const uint8_t *d_residues; const int64_t *d_offsets; int64_t nq, total_residues; int32_t max_len;
+  int32_t *d_decibits; uint8_t *d_flags; float *d_fwd_bits; wh_pair_detail *d_detail;
+  int Lc, H;
+  int Lmain;                     // length cap of the main resolver launches (= Lc unless the longest query exceeds the resolver's LDS block: long_query_pass)
+  int64_t npairs_all;
+  bool resolve;                  // multidomain regions go through the resolver's queue (else: one envelope per region)
+  bool mixed;                    // query lengths differ enough for the length order to pay in the one-wave classes too
+  const int32_t *d_qorder;       // queries in descending length order, when the pass formed it
+  bool wide_dense, wide_no_em_lds, p2win_force, res_null2_gather, res_no_lds_tables;   // WH_WIDE_DENSE ... WH_RES_NO_LDS_TABLES
+  int res_waves;                 // WH_RES_WAVES (experiments: waves per resolver workgroup), 0 = not set
+};
+
+// multidomain regions: HMMER's stochastic resolver over the queue the scoring launches filled, then its follow-up passes
+// (wh_host_resolve.hip).  <overflow>: the queue was too small, the caller repeats the scoring pass
+int resolver_stage(const ScoreCall &c, bool *overflow, int *rlaunches);
+// the follow-up passes' counters of the last call: reset when a call starts and when a pass starts over
+static inline void reset_resolver_counts(wh_ehmm *e) {
+  e->last_long_list = 0;
+  for (int64_t &v : e->last_big) v = 0;
+  e->last_long[0] = e->last_long[1] = 0;
+}
+
+// the fields ScoreArgs, WideArgs and GenericArgs have in common: models, queries, outputs, alphabet, resolver queue
+template <class Args> static void fill_common(Args &a, const ScoreCall &c) {
+  const wh_ehmm *e = c.e;
+  memset(&a, 0, sizeof a);
+  a.hmms = (const DevHMM *)e->d_hmms.p;
+  a.residues = c.d_residues; a.offsets = c.d_offsets; a.nq = c.nq;
+  a.Lcap = c.Lc;
+  a.decibits = c.d_decibits; a.flags = c.d_flags; a.fwd_bits = c.d_fwd_bits; a.detail = c.d_detail;
+  a.H = c.H; a.K = e->K; a.Kp = e->Kp;
+  memcpy(a.degen, e->degen, sizeof a.degen);
+  if (c.resolve) { a.rrecs = (ResolveRec *)e->d_rrecs.p; a.rcount = e->counter(kSlotResolveCount); a.rcap = (int)e->rq_cap; }
+}
+
+// WH_STATS: a kernel's counter block (in d_recs), zeroed before its launch; <min_slot>: a 64-bit slot that starts at ~0
+static inline int stats_begin(const ScoreCall &c, size_t bytes, int min_slot, unsigned long long **stats) {
+  if (!c.e->knobs.stats) return WH_OK;
+  if (c.e->d_recs.ensure(bytes)) return WH_ENOMEM;
+  HIPCHK(hipMemsetAsync(c.e->d_recs.p, 0, bytes, c.s));
+  if (min_slot >= 0) { unsigned long long bigv = ~0ull; HIPCHK(hipMemcpyAsync((char *)c.e->d_recs.p + min_slot * 8, &bigv, 8, hipMemcpyHostToDevice, c.s)); }
+  *stats = (unsigned long long *)c.e->d_recs.p;
+  return WH_OK;
+}
+template <int N> static int stats_read(const ScoreCall &c, const unsigned long long *stats, unsigned long long (&st)[N]) {
+  HIPCHK(hipMemcpyAsync(st, stats, sizeof st, hipMemcpyDeviceToHost, c.s));
+  HIPCHK(hipStreamSynchronize(c.s));
+  return WH_OK;
+}
+
+// The float64 front end (wh_generic.hip), one wavefront per pair: its arguments but for the work list (models of the
+// main launch, pairs of the long-list pass), and the wavefronts of a launch over <n_items> with their slabs in d_rmx.
+static inline GenericArgs front_args(const ScoreCall &c) {
+  GenericArgs g;
+  fill_common(g, c);
+  g.gtab = (const double *)c.e->d_gtab.p;
+  g.counter = c.e->counter(kSlotGenericFront);
+  g.Qmax = c.e->max_Q;
+  g.slab_stride = (generic_front_doubles(c.Lc, c.e->max_Q) + 1) & ~(size_t)1;
+  return g;
+}
+static inline int front_blocks(const ScoreCall &c, GenericArgs &g, int64_t n_items, const char *what, int *blocks) {
+  wh_ehmm *e = c.e;
+  *blocks = (int)std::min<int64_t>(n_items, (int64_t)e->cu_count * std::min<size_t>(12, kLdsBudget / generic_lds_bytes(c.Lc)));
+  *blocks = clamp_blocks(*blocks, g.slab_stride * sizeof(double), e->d_rmx, e->max_M, c.Lc, what);
+  if (*blocks < 0) return WH_ENOMEM;
+  if (e->d_rmx.ensure((size_t)*blocks * g.slab_stride * sizeof(double))) return WH_ENOMEM;
+  g.slab = (double *)e->d_rmx.p;
+  return WH_OK;
 }

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "wh_common.h"
 
 namespace wh {
@@ -126,6 +128,22 @@ hipError_t launch_score7q(int Q, const ScoreArgs &a, int blocks, int threads, si
 hipError_t launch_score9(int Q, const ScoreArgs &a, int blocks, int threads, size_t lds, hipStream_t s);
 int score9_block_floats(int SP, int Lcap);
 
+// What the resolver kernels report back to the host and what the host tells a launch about its lists: one block of the
+// handle's counters (wh_host.h: kSlotResolveFeedback), reached through ResolveArgs::fb.
+struct ResolveFeedback {
+  int wrong_model;             // queue records found in a segment of another model (never, for a well-formed segment list): NOT reset by an upload
+  int long_list_pairs;         // pairs flagged WH_FLAG_TRUNC after the resolver (trunc_list_kernel)
+  // ---- from here on the host uploads the block in front of every launch: counts zeroed, the launch's lists
+  // Regions whose lists do not fit the wave's blocks (wh_resolve.hip):
+  int big_pairs, big_doms, big_segs, big_clus;   // pairs that have one; the most domains of a trace, segments and significant clusters such a region needs (0: that list was long enough)
+  // Pairs whose query is longer than ResolveArgs::Lcap:
+  int long_pairs, longest_query;
+  int big_cap;                 // capacity of the list of the big-region pairs' queue positions (0: none - the pair keeps WH_FLAG_TRUNC, WH_NO_BIG_REGION)
+  int long_cap;                // ... of the long-query pairs' (0: none - the pair keeps WH_FLAG_TRUNC)
+  int32_t *big_list, *long_list;
+};
+constexpr size_t kFeedbackUploadFrom = offsetof(ResolveFeedback, big_pairs);
+
 struct ResolveArgs {
   const DevHMM *hmms;
   const double *gtab;          // float64 tables of every model (DevHMM::gfw_off / gem_off)
@@ -160,24 +178,16 @@ struct ResolveArgs {
   uint32_t degen[32];
   unsigned long long *stats;   // WH_STATS: wave cycles per phase [0] region Forward [1] traces [2] clustering [3] cluster statistics [4] envelope Forward
   int dbg;                     // WH_RDBG > 0: print the first <dbg> sampled segments and the cluster statistics of every region
-  int *err;                    // device counter: records dropped because their model is not the segment's (the host turns it into WH_EHIP)
+  ResolveFeedback *fb;         // device: what the launch reports (wrong_model: the host turns it into WH_EHIP) and the lists it appends to.  ONE
+                               // pointer, read from memory where a pair needs it: as kernel arguments of their own the fields cost the main launch scratch
   const int32_t *rext;         // long-list pass (wh_api.hip): record t's regions are NOT in the record but here, at rext + t * rext_stride:
   int64_t rext_stride;         // kRextInts ints per region (first row, last row, envsc bits, domcorr bits, multidomain), ResolveRec::nenv of them
-  // Regions whose lists do not fit the wave's blocks (wh_resolve.hip) are reported in eight ints kBigAfterErr behind <err>:
-  // [0] pairs that have one, [1..3] the most domains of a trace, segments and significant clusters such a region needs, [4]
-  // capacity of the list of their queue positions (0: none - the pair keeps WH_FLAG_TRUNC, WH_NO_BIG_REGION), [5..6] its address (8-byte aligned).
   int dom_cap, clus_cap;       // > 0: the big-region pass (resolve_big_kernel) - every list of a region in the wave's HBM block, seg_cap segments,
                                // seg_stride >= resolve_big_seg_ints(...)
-  // A pair whose query is longer than <Lcap> is reported in three ints kLongAfterErr behind <err>: [0] such pairs, [1] the longest
-  // query among them, [2] capacity of the list of their queue positions (0: none - the pair keeps WH_FLAG_TRUNC); the list's
-  // address (8-byte aligned) sits kLongListAfterErr behind <err>.
   int long_query;              // 1 (with dom_cap > 0): the long-query pass (resolve_long_kernel) - residues and emitting states in the wave's HBM
                                // block as well, seg_stride >= resolve_long_seg_ints(...), wave_lds_ints = resolve_long_lds_bytes(Mmax) / 4
 };
 constexpr int kRextInts = 5;
-constexpr int kBigAfterErr = 3;
-constexpr int kLongAfterErr = 11;
-constexpr int kLongListAfterErr = 30;
 hipError_t launch_resolve(const ResolveArgs &a, int blocks, int waves, size_t lds, hipStream_t s);
 size_t resolve_lds_header_bytes(int Qt);
 // cost estimate of every queued pair (cells of its multidomain regions) for the longest-first order

@@ -160,7 +160,7 @@ __device__ __forceinline__ unsigned line_check_bits(unsigned long long key, unsi
 // what the two Forward sweeps of a pair read from: they were 34-45 % of the kernel and bound by streaming those arrays
 // from L2 once per row and wave.
 //
-// <BIG>: the big-region pass (wh_host_score.hip: big_region_pass).  The main launch keeps the domains of a trace (kDomMax),
+// <BIG>: the big-region pass (wh_host_resolve.hip: big_region_pass).  The main launch keeps the domains of a trace (kDomMax),
 // their null2 vectors and the significant clusters of a region (kClusMax) in the wave's LDS block and kSegCap segments in
 // its HBM block; a region that needs more is COUNTED to the end (domains of a trace, segments, clusters), the largest
 // counts go to the handle's counters (one atomic max each) and the pair's queue position to the list named there.  The BIG instantiation runs
@@ -168,7 +168,7 @@ __device__ __forceinline__ unsigned line_check_bits(unsigned long long key, unsi
 // a.seg_cap, a.clus_cap): what differs is where a list lives and how lane 0's stores reach the other lanes
 // (wave_barrier for LDS, wave_mem_sync for HBM), as the clustering's vertex stacks do it.
 //
-// <LONGQ> (with BIG): the long-query pass (wh_host_score.hip: long_query_pass).  The main launches are sized for a length cap
+// <LONGQ> (with BIG): the long-query pass (wh_host_resolve.hip: long_query_pass).  The main launches are sized for a length cap
 // (a.Lcap) that keeps their occupancy; a longer query's pair is listed (the counters' long-query block) and done again here,
 // where the two per-residue arrays of the LDS block - the residues and their emitting states - live in the wave's HBM block
 // too, behind the big-region lists: lane 0 (the leading lanes of a run) writes with ordinary stores, every lane reads after
@@ -194,10 +194,8 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
   double *bins = reinterpret_cast<double *>(uni + resolve_uni_ints(Llds, a.Mmax));   // 64 float64 bins of the E-state row pass (8-byte aligned)
   int *misc = reinterpret_cast<int *>(bins + 64);                // 4 x kEnvMax + 3 x kClusMax ints: envelope list of the pair (detail), cluster list of a region
   unsigned long long *hprev = reinterpret_cast<unsigned long long *>(misc + 4 * kEnvMax + 3 * kClusMax + 16), *hcur = hprev + kHist;
-  // the big-region block of the handle's counters sits kBigAfterErr ints behind a.err (wh_host.h: kSlotBigRegion): pairs listed,
-  // the three largest counts, capacity of the list (0: none, WH_NO_BIG_REGION), the list's address.  Reached through a.err
-  // and read from memory where a pair needs it: as kernel arguments of their own these cost the main launch 16 bytes of scratch.
-  auto big_out = [&]() -> int * { return a.err + kBigAfterErr; };     // (formed where it is used: a pointer kept live costs the same)
+  // a.fb (wh_launch.h: ResolveFeedback) is read from memory where a pair needs it: as kernel arguments of their own its
+  // fields cost the main launch 16 bytes of scratch, and a pointer to one of them kept live costs the same.
   int *pair_pos = misc + 4 * kEnvMax + 3 * kClusMax;             // queue position of the current pair (first of the 16 spare ints)
   (void)Lp;
   const size_t wslot = (size_t)blockIdx.x * nwaves + wave;        // this wave's slab / segment arrays
@@ -297,7 +295,7 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
     // long-list pass: the pair's regions are in HBM (any number of them), the record carries the pair alone
     const int32_t *xl = a.rext ? a.rext + (size_t)ridx * (size_t)a.rext_stride : nullptr;
     if (c_h >= 0 && rec.h != c_h) {                    // never true for a well-formed segment list (the staged tables are c_h's):
-      if (lane == 0 && a.err) atomicAdd(a.err, 1);     // counted, and the next scoring call on the handle fails with WH_EHIP
+      if (lane == 0 && a.fb) atomicAdd(&a.fb->wrong_model, 1);    // counted, and the next scoring call on the handle fails with WH_EHIP
       continue;
     }
     const DevHMM hm = a.hmms[rec.h];
@@ -313,18 +311,16 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
     const size_t out = (size_t)rec.q * a.H + rec.h;
     if (L > a.Lcap) {
       // a query beyond this launch's length cap: nothing of it fits the wave's blocks.  Its queue position goes to the list of
-      // the long-query pass (the counters' long-query block, kLongAfterErr ints behind a.err: pairs, longest query, capacity;
-      // the list's address kLongListAfterErr behind it).  Without a list, or when the long-list pass scores the pair again
-      // anyway (its region list was too short: main launch only), the pair is flagged.
+      // the long-query pass (a.fb->long_list).  Without a list, or when the long-list pass scores the pair again anyway (its
+      // region list was too short: main launch only), the pair is flagged.
       if (lane == 0) {
-        int *lq_out = a.err + kLongAfterErr;
         const int fl = rec.flags | (rec.multi_mask ? WH_FLAG_MULTI : 0);
-        const int lq_cap = __builtin_nontemporal_load(lq_out + 2);
+        const int lq_cap = __builtin_nontemporal_load(&a.fb->long_cap);
         if (lq_cap > 0 && (a.rext || !(fl & WH_FLAG_TRUNC))) {
-          int32_t *lq_list = *reinterpret_cast<int32_t *const *>(a.err + kLongListAfterErr);
-          const int slot = atomicAdd(lq_out, 1);
+          int32_t *lq_list = a.fb->long_list;
+          const int slot = atomicAdd(&a.fb->long_pairs, 1);
           if (slot < lq_cap) lq_list[slot] = ridx;
-          atomicMax(lq_out + 1, L);
+          atomicMax(&a.fb->longest_query, L);
         } else a.flags[out] = (uint8_t)(fl | WH_FLAG_TRUNC);
       }
       continue;
@@ -672,7 +668,7 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
         }
         nseg_all += ndom;
         if (ndom > DOMCAP) {                 // (the walk and its random numbers do not depend on the list: the count is exact)
-          if (lane == 0) atomicMax(big_out() + 1, ndom);
+          if (lane == 0) atomicMax(&a.fb->big_doms, ndom);
           flags |= kBigMark; ndom = DOMCAP;
         }
         list_sync();
@@ -835,7 +831,7 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
         atomicAdd(a.stats + 20, (unsigned long long)n_pred); atomicAdd(a.stats + 21, (unsigned long long)n_resync); atomicAdd(a.stats + 23, (unsigned long long)c_load);
         atomicAdd(a.stats + 8, (unsigned long long)n_bm); atomicAdd(a.stats + 9, (unsigned long long)n_bd); atomicAdd(a.stats + 10, (unsigned long long)n_bf); atomicAdd(a.stats + 11, (unsigned long long)n_i); atomicAdd(a.stats + 12, (unsigned long long)n_hit);
       }
-      if (nseg_all > SEGCAP) { if (lane == 0) atomicMax(big_out() + 2, nseg_all); flags |= kBigMark; }
+      if (nseg_all > SEGCAP) { if (lane == 0) atomicMax(&a.fb->big_segs, nseg_all); flags |= kBigMark; }
       RTICK(1);
       for (int pos = 1 + lane; pos <= Lr; pos += 64) n2sc[ireg + pos - 1] = logf(__builtin_nontemporal_load(acc + pos) / (float)kSamples);
       wave_mem_sync();
@@ -979,9 +975,9 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
         if (nsig < CLCAP && (!BIG || lane == 0)) { g_i[nsig] = best[0]; g_j[nsig] = best[2]; g_p[nsig] = (float)ninc / (float)kSamples; }
         nsig++;
       }
-      if (nsig > CLCAP) { if (lane == 0) atomicMax(big_out() + 3, nsig); flags |= kBigMark; nsig = CLCAP; }
+      if (nsig > CLCAP) { if (lane == 0) atomicMax(&a.fb->big_clus, nsig); flags |= kBigMark; nsig = CLCAP; }
       // (the main launch clustered a truncated segment list: what it counted is a lower bound, the full count is this one)
-      else if (BIG && nsig > kClusMax && lane == 0) atomicMax(big_out() + 3, nsig);
+      else if (BIG && nsig > kClusMax && lane == 0) atomicMax(&a.fb->big_clus, nsig);
       RTICK(3);
       // order by start (stable), drop dominated clusters (region_trace_ensemble)
       // (LDS: every lane writes the same values.  BIG: lane 0 sorts its own list in HBM, then hands it over)
@@ -1057,11 +1053,11 @@ __device__ __forceinline__ void resolve_body(const ResolveArgs a) {
     }
     if (flags & kBigMark) {
       // (a pair whose region LIST was too short, main launch only, is done again by the long-list pass anyway)
-      const int big_cap = __builtin_amdgcn_readfirstlane(__builtin_nontemporal_load(big_out() + 4));     // 0: no list (WH_NO_BIG_REGION)
+      const int big_cap = __builtin_amdgcn_readfirstlane(__builtin_nontemporal_load(&a.fb->big_cap));     // 0: no list (WH_NO_BIG_REGION)
       if (big_cap <= 0) flags |= WH_FLAG_TRUNC;
       else if ((a.rext || !(flags & WH_FLAG_TRUNC)) && lane == 0) {
-        int32_t *big_list = *reinterpret_cast<int32_t *const *>(big_out() + 5);
-        const int slot = atomicAdd(big_out(), 1);
+        int32_t *big_list = a.fb->big_list;
+        const int slot = atomicAdd(&a.fb->big_pairs, 1);
         if (slot < big_cap) big_list[slot] = *pair_pos;
       }
     }
