@@ -45,7 +45,8 @@ extern "C" {
 #define WH_EIO        -2   /* cannot open / parse an HMM file                */
 #define WH_ENODEV     -3   /* no usable HIP device                           */
 #define WH_EHIP       -4   /* a HIP runtime call failed                      */
-#define WH_ERANGE     -5   /* query longer than this build supports, or too many pairs in one call (models: any length) */
+#define WH_ERANGE     -5   /* too many pairs in one call (2^31 or more; models and queries: any length.  A query too long for a
+                              kernel's LDS plan only under the development knobs WH_NO_LONG_SCORE / WH_NO_RESOLVE)          */
 #define WH_ENOMEM     -6   /* device memory: also a call whose workspace for ONE workgroup does not fit (wh_last_error: the figures) */
 
 #define WH_ALPH_DNA    0
@@ -70,9 +71,13 @@ extern "C" {
  * the QUERY length: its per-wave LDS block holds the query and a state per residue, and a call whose longest query does
  * not fit (beyond ~52 000 residues; ~31 000 with a model of more than 32 767 nodes) sizes its main launches for the
  * lengths that keep their occupancy and resolves the pairs of longer queries in the long-query pass, the same resolver
- * with those two arrays in HBM (wh_last_long_query_pairs).  The query-length limits that remain are the SCORING kernels'
- * own, and they fail loudly (WH_ERANGE: "query length ... does not fit in LDS"; the float64 front end near 163 000
- * residues).  What can still set WH_FLAG_TRUNC: a malformed record in the resolver's queue (an internal error; a region
+ * with those two arrays in HBM (wh_last_long_query_pairs).  Nor do the SCORING and ALIGNMENT kernels: their launches keep the
+ * query in LDS, and a call whose longest query a size class cannot plan (wh_ehmm_max_query_len: 15 788 - 142 368 residues
+ * by model class) sizes them for the lengths every class accepts and hands the pairs of longer queries to the long-query
+ * scoring / alignment pass - the any-size float64 kernels, one wavefront per pair, with the residues in HBM beyond ~163 000
+ * residues (wh_last_long_score_pairs, wh_last_long_align_pairs).  What remains is the device's memory: one wave's float64 slab
+ * grows with query length x model length, and a call whose slab does not fit is refused with WH_ENOMEM before anything is
+ * launched.  What can still set WH_FLAG_TRUNC: a malformed record in the resolver's queue (an internal error; a region
  * outside its sequence), more than four million pairs for the long-list pass in one call, or the development knobs
  * WH_NO_LONG_LIST / WH_NO_BIG_REGION / WH_NO_RESOLVE (WH_NO_LONG_QUERY sets no flag: the call runs without the resolver,
  * multidomain regions stay one envelope).  The value stays 8 for binary compatibility. */
@@ -127,7 +132,13 @@ int      wh_ehmm_alphabet(const wh_ehmm *e);
 int      wh_ehmm_info(const wh_ehmm *e, int32_t *M, int32_t *nseq, int32_t *hmm_index);
 /* MAP annotation of model h: alignment column (1-based) of match state k=1..M, 0 if absent. */
 int      wh_ehmm_map(const wh_ehmm *e, int h, int32_t *map_cols);
+/* The length up to which the queries of a call stay on the float32 kernels, in scoring and in alignment: the largest
+ * length every launch of the handle's size classes can plan (phase-call, pass-synchronous and several-waves-per-pair
+ * kernels alike).  A call with a longer query is served all the same - the pairs of the longer queries by the long-query
+ * passes (float64, one wavefront per pair: correct, not fast) - so this is a performance figure, not a limit.
+ * wh_query_len_cap gives the same figure (default knobs) from the node counts alone, without a handle or a device. */
 int      wh_ehmm_max_query_len(const wh_ehmm *e);
+int      wh_query_len_cap(int alphabet, const int32_t *model_nodes, int n);
 
 /* All-vs-all scoring: nq queries (digital residues, CSR offsets[nq+1]) x H models.  One call serves fewer than 2^31
  * pairs (WH_ERANGE beyond: feed the queries in chunks, as the reference feeds hmmsearch 20 000 sequences at a time,
@@ -199,6 +210,13 @@ int wh_last_region_overflow(wh_ehmm *e, int64_t *out4);
  * cap of the resolver's main launches (only in a call whose longest query does not fit the resolver's LDS block), out[1] =
  * the longest query among them.  Both 0: no pair went through the pass (two more ints in the call's one read-back). */
 int wh_last_long_query_pairs(wh_ehmm *e, int64_t out[2]);
+/* The long-query scoring pass of the last scoring call: out[0] = pairs it scored because their query is longer than the
+ * length cap of the call's scoring launches (every model of every such query; only in a call whose longest query a size
+ * class cannot plan, or under the development knob WH_SCORE_LMAIN), out[1] = the longest query among them.  Both 0: no
+ * pair went through the pass, and the call made no launch and no read-back for it.  wh_last_long_align_pairs: the same
+ * for the last wh_align call (pairs on models of up to 3 072 nodes handed to the any-size float64 alignment kernel). */
+int wh_last_long_score_pairs(wh_ehmm *e, int64_t out[2]);
+int wh_last_long_align_pairs(wh_ehmm *e, int64_t out[2]);
 
 /* Optional per-PAIR record of the same: a device array of nq x H bytes that the scoring calls made after this one fill
  * with WH_PATH_* bits (NULL switches it off again).  Written by the staged launches only (WH_SCORE_KERNEL=10; pairs
@@ -246,7 +264,9 @@ int wh_last_score_launches(wh_ehmm *e, int32_t *cells_per_lane, int32_t *kind, d
 /* When enabled, every kernel launch is bracketed by HIP events (bench/roofline use). */
 int wh_set_timing(wh_ehmm *e, int enabled);
 /* Development knobs (WH_SCORE_KERNEL, WH_KEEP_LOG2, WH_MAX_WAVES, WH_FORCE_SPECG,
- * WH_NO_LOGSPACE, WH_STATS, WH_TRACE, WH_DBG).  The environment is read ONCE, in wh_ehmm_load; this call
+ * WH_NO_LOGSPACE, WH_STATS, WH_TRACE, WH_DBG; WH_SCORE_LMAIN=<n> caps the main length of scoring and alignment calls at n
+ * residues, WH_NO_LONG_SCORE switches the long-query scoring / alignment passes off, WH_LONGQ_FORCE runs them with the
+ * residues in HBM whatever the length).  The environment is read ONCE, in wh_ehmm_load; this call
  * changes a knob on a live handle (A/B harness tools/ab_score.py).  Production needs none of them. */
 int wh_set_option(wh_ehmm *e, const char *name, const char *value);
 

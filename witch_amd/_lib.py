@@ -57,6 +57,7 @@ SYMBOLS = {
     "wh_ehmm_info": (C.c_int, [_P, _P, _P, _P]),
     "wh_ehmm_map": (C.c_int, [_P, C.c_int, _P]),
     "wh_ehmm_max_query_len": (C.c_int, [_P]),
+    "wh_query_len_cap": (C.c_int, [C.c_int, _P, C.c_int]),
     "wh_score": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "wh_score_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
     "wh_topk": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P]),
@@ -73,6 +74,8 @@ SYMBOLS = {
     "wh_last_queue_reruns": (C.c_int, [_P]),
     "wh_last_region_overflow": (C.c_int, [_P, _P]),
     "wh_last_long_query_pairs": (C.c_int, [_P, _P]),
+    "wh_last_long_score_pairs": (C.c_int, [_P, _P]),
+    "wh_last_long_align_pairs": (C.c_int, [_P, _P]),
     "wh_last_score_launches": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "wh_last_kernel_ms": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "wh_set_timing": (C.c_int, [_P, C.c_int]),

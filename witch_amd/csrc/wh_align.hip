@@ -883,12 +883,14 @@ static hipError_t launch_align_q(int Q, const AlignArgs &a, int blocks, int thre
 }
 
 // protein models of 20/24 cells per lane do not fit both orientations beside 20 emission rows:
-// they run the pass-synchronous variant too
+// they run the pass-synchronous variant too (16 cells per lane: with a query that leaves no wave beside the tables)
 static hipError_t launch_align_swap_mid(int Q, const AlignArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
   if (a.logsp) {
+    if (Q == 16) return launch_one<16, false, true, true, true>(a, blocks, threads, lds, s);
     if (Q == 20) return launch_one<20, false, true, true, true>(a, blocks, threads, lds, s);
     if (Q == 24) return launch_one<24, false, true, true, true>(a, blocks, threads, lds, s);
   } else {
+    if (Q == 16) return launch_one<16, false, true, true>(a, blocks, threads, lds, s);
     if (Q == 20) return launch_one<20, false, true, true>(a, blocks, threads, lds, s);
     if (Q == 24) return launch_one<24, false, true, true>(a, blocks, threads, lds, s);
   }

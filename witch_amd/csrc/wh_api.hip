@@ -54,7 +54,7 @@ int wh_digitize(int alphabet, const char *text, int64_t n, uint8_t *out) {
 
 void wh_ehmm_free(wh_ehmm *e) {
   if (!e) return;
-  for (DevBuf *b : {&e->d_tlist, &e->d_rext, &e->d_biglist, &e->d_bigsegs, &e->d_longlist, &e->d_gtab, &e->d_rrecs, &e->d_rmx, &e->d_rsegs, &e->d_hmms, &e->d_tables, &e->d_nseq, &e->d_index, &e->d_lists, &e->d_counter, &e->d_scratch, &e->d_ascratch, &e->d_wscratch,
+  for (DevBuf *b : {&e->d_tlist, &e->d_rext, &e->d_biglist, &e->d_bigsegs, &e->d_longlist, &e->d_lqlist, &e->d_gtab, &e->d_rrecs, &e->d_rmx, &e->d_rsegs, &e->d_hmms, &e->d_tables, &e->d_nseq, &e->d_index, &e->d_lists, &e->d_counter, &e->d_scratch, &e->d_ascratch, &e->d_wscratch,
                     &e->s_res, &e->s_off, &e->s_deci, &e->s_flags, &e->s_fwd, &e->s_det, &e->s_idx, &e->s_w,
                     &e->s_nk, &e->s_nu, &e->s_pq, &e->s_ph, &e->s_co, &e->s_cols, &e->s_pos, &e->d_rkeys, &e->d_rorder, &e->d_rchunks, &e->d_qorder, &e->d_order, &e->d_items, &e->d_recs, &e->d_spec, &e->d_back, &e->d_cwj, &e->d_cwv, &e->d_cwn, &e->d_crow,
                     &e->c_buf[0], &e->c_buf[1], &e->c_buf[2], &e->c_buf[3], &e->c_buf[4], &e->c_buf[5], &e->c_buf[6],
@@ -243,6 +243,9 @@ int wh_set_option(wh_ehmm *e, const char *name, const char *value) {
   else if (!strcmp(name, "WH_NO_LONG_LIST")) k.no_long_list = on;
   else if (!strcmp(name, "WH_NO_BIG_REGION")) k.no_big_region = on;
   else if (!strcmp(name, "WH_NO_LONG_QUERY")) k.no_long_query = on;
+  else if (!strcmp(name, "WH_SCORE_LMAIN")) k.score_lmain = *v ? std::max(0, atoi(v)) : 0;
+  else if (!strcmp(name, "WH_NO_LONG_SCORE")) k.no_long_score = on;
+  else if (!strcmp(name, "WH_LONGQ_FORCE")) k.longq_force = on;
   else if (!strcmp(name, "WH_NO_WINDOW")) k.no_window = on;
   else if (!strcmp(name, "WH_NO_P2WIN")) k.no_p2win = on;
   else if (!strcmp(name, "WH_RQUEUE_CAP")) k.rqueue_cap = *v ? std::max(1, atoi(v)) : 0;
@@ -258,7 +261,7 @@ int wh_set_option(wh_ehmm *e, const char *name, const char *value) {
 }
 
 static void knobs_from_env(wh_ehmm *e) {
-  for (const char *name : {"WH_SCORE_KERNEL", "WH_ITEM_G", "WH_ST_UNITS", "WH_KEEP_LOG2", "WH_MAX_WAVES", "WH_FORCE_SPECG", "WH_NO_LOGSPACE", "WH_NO_RESOLVE", "WH_NO_LONG_LIST", "WH_NO_BIG_REGION", "WH_NO_LONG_QUERY", "WH_NO_WINDOW", "WH_NO_P2WIN", "WH_RQUEUE_CAP", "WH_NO_WIDE_ALIGN", "WH_STATS", "WH_TRACE", "WH_DBG", "WH_RDBG"})
+  for (const char *name : {"WH_SCORE_KERNEL", "WH_ITEM_G", "WH_ST_UNITS", "WH_KEEP_LOG2", "WH_MAX_WAVES", "WH_FORCE_SPECG", "WH_NO_LOGSPACE", "WH_NO_RESOLVE", "WH_NO_LONG_LIST", "WH_NO_BIG_REGION", "WH_NO_LONG_QUERY", "WH_SCORE_LMAIN", "WH_NO_LONG_SCORE", "WH_LONGQ_FORCE", "WH_NO_WINDOW", "WH_NO_P2WIN", "WH_RQUEUE_CAP", "WH_NO_WIDE_ALIGN", "WH_STATS", "WH_TRACE", "WH_DBG", "WH_RDBG"})
     if (const char *v = getenv(name)) (void)wh_set_option(e, name, v);
 }
 
@@ -321,6 +324,18 @@ int wh_last_region_overflow(wh_ehmm *e, int64_t *out4) {
 int wh_last_long_query_pairs(wh_ehmm *e, int64_t out[2]) {
   if (!e || !out) { set_error("wh_last_long_query_pairs: bad argument"); return WH_EINVAL; }
   out[0] = e->last_long[0]; out[1] = e->last_long[1];
+  return WH_OK;
+}
+
+int wh_last_long_score_pairs(wh_ehmm *e, int64_t out[2]) {
+  if (!e || !out) { set_error("wh_last_long_score_pairs: bad argument"); return WH_EINVAL; }
+  out[0] = e->last_long_score[0]; out[1] = e->last_long_score[1];
+  return WH_OK;
+}
+
+int wh_last_long_align_pairs(wh_ehmm *e, int64_t out[2]) {
+  if (!e || !out) { set_error("wh_last_long_align_pairs: bad argument"); return WH_EINVAL; }
+  out[0] = e->last_long_align[0]; out[1] = e->last_long_align[1];
   return WH_OK;
 }
 
@@ -634,18 +649,29 @@ int wh_consensus(wh_ehmm *e, const int64_t *offsets, int64_t nq, const int64_t *
   return WH_OK;
 }
 
+// The length up to which queries stay on the float32 kernels, from the planner's own functions (wh_plan.h): the largest
+// length every scoring launch (one-wave classes whichever kernel family they take, the wide kernel, the float64 front end
+// of the models beyond them) and every alignment class of the handle can plan.  Longer queries are served by the long-query
+// passes.
 int wh_ehmm_max_query_len(const wh_ehmm *e) {
   if (!e) return WH_EINVAL;
-  // Long queries keep their special-state rows in HBM; what remains in LDS per wave is the
-  // residue buffer, so the bound is one wave's residues beside the largest model's tables
-  // (the HBM workspace grows with L x M and may still fail with WH_ENOMEM).
-  int best = 1 << 20;
-  for (auto &kv : e->by_q) {
-    const size_t table = (size_t)(e->K + 2 * FW_NARR) * kv.first * kWave * sizeof(float);
-    const size_t left = kLdsBudget - kLdsHeader - table - (32 + kRegsInts + 8) * sizeof(float);
-    best = std::min(best, (int)std::min<size_t>(left, 1u << 20));
+  return query_len_cap(plan_knobs(e), plan_classes(e));
+}
+
+int wh_query_len_cap(int alphabet, const int32_t *model_nodes, int n) {
+  int K, Kp;
+  if (alphabet_sizes(alphabet, &K, &Kp) != 0 || !model_nodes || n <= 0) { set_error("wh_query_len_cap: bad argument"); return WH_EINVAL; }
+  PlanClasses cl;
+  cl.K = K;
+  for (int i = 0; i < n; i++) {
+    if (model_nodes[i] < 1) { set_error("wh_query_len_cap: model %d has %d nodes", i, model_nodes[i]); return WH_EINVAL; }
+    const int Q = choose_Q(model_nodes[i]);
+    if (Q > kMaxQ) {
+      // (as wh_ehmm_load: wide tables up to 8 waves of 48 cells per lane, the float64 front end beyond)
+      if ((model_nodes[i] + kWave * kWideQBig - 1) / (kWave * kWideQBig) <= kWideWavesMax) cl.wide = true; else cl.front = true;
+    } else if (std::find(cl.score_q.begin(), cl.score_q.end(), Q) == cl.score_q.end()) { cl.score_q.push_back(Q); cl.align_q.push_back(Q); }
   }
-  return best;
+  return query_len_cap(PlanKnobs(), cl);
 }
 
 }  // extern "C"

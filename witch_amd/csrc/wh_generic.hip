@@ -20,6 +20,22 @@
 #include "wh_launch.h"
 #include "wh_f64.h"
 
+// This file is compiled twice (Makefile).  wh_generic.o: the kernels as they always were, the query in the wave's LDS block.
+// wh_generic_long.o (WH_GENERIC_LONGQ=1): generic_front_long_kernel and generic_align_long_kernel alone - the same code with
+// the residues (clamped to the alphabet like the LDS copy) in the last generic_seq_doubles(Lcap) doubles of the wave's HBM
+// slab, so that the LDS block no longer depends on the query length: queries beyond generic_lds_bytes (~163 000 residues).
+// An object of its own keeps the inlining decisions, and so the instructions, of the first object what they were.
+#ifndef WH_GENERIC_LONGQ
+#define WH_GENERIC_LONGQ 0
+#endif
+#if WH_GENERIC_LONGQ
+#define WH_GENERIC_FRONT generic_front_long_kernel
+#define WH_GENERIC_ALIGN generic_align_long_kernel
+#else
+#define WH_GENERIC_FRONT generic_front_kernel
+#define WH_GENERIC_ALIGN generic_align_kernel
+#endif
+
 namespace wh {
 
 namespace {
@@ -359,17 +375,24 @@ __host__ __device__ inline size_t generic_rowlen(int Q) { return (size_t)3 * Q *
 
 constexpr double kRt1 = 0.25, kRt2 = 0.10, kRt3 = 0.20;
 
+constexpr bool LONGQ = WH_GENERIC_LONGQ != 0;
+// a wave's residue copy at the end of its slab (the long kernels): an even number of doubles
+__host__ __device__ inline size_t seq_doubles(int Lcap) { return (((size_t)Lcap + 16 + 15) / 16) * 2; }
+
 }  // namespace
 
+#if !WH_GENERIC_LONGQ
 size_t generic_front_doubles(int Lcap, int Qmax) {
   return (size_t)(Lcap + 4) * generic_rowlen(Qmax) + 2 * (size_t)(Lcap + 2) * xNSPEC + 5 * (size_t)(Lcap + 4) + 2 * (size_t)Qmax * 64 + 8;
 }
 size_t generic_align_doubles(int Lcap, int Qmax) {
   return (size_t)(Lcap + 4) * generic_rowlen(Qmax) + 2 * (size_t)(Lcap + 2) * xNSPEC + 8;
 }
+size_t generic_seq_doubles(int Lcap) { return seq_doubles(Lcap); }
 size_t generic_lds_bytes(int Lcap) { return (size_t)(Lcap + 16) + 64 * 4 + kRextInts * WH_MAX_ENVELOPES * 4 + 64; }
+#endif
 
-__global__ __launch_bounds__(64, 3) void generic_front_kernel(GenericArgs a) {
+__global__ __launch_bounds__(64, 3) void WH_GENERIC_FRONT(GenericArgs a) {
   extern __shared__ __attribute__((aligned(16))) int lds_raw[];
   const int lane = threadIdx.x;
   float *null2 = reinterpret_cast<float *>(lds_raw);                 // 32 floats (+ 32 spare)
@@ -384,6 +407,7 @@ __global__ __launch_bounds__(64, 3) void generic_front_kernel(GenericArgs a) {
   const int64_t n_work = listed ? a.n_pairs : a.nq * (int64_t)a.n_list;
   const double LOG2 = 0.69314718055994529;
   double *slab = a.slab + (size_t)blockIdx.x * a.slab_stride;
+  if constexpr (LONGQ) seq = reinterpret_cast<uint8_t *>(slab + (a.slab_stride - seq_doubles(a.Lcap)));
   for (;;) {
     int item = 0;
     if (lane == 0) item = atomicAdd(a.counter, 1);
@@ -418,7 +442,7 @@ __global__ __launch_bounds__(64, 3) void generic_front_kernel(GenericArgs a) {
     int nreg_rec = 0, nenv_rec = 0;
     if (L > 0 && L <= a.Lcap) {
       for (int t = lane; t < L; t += 64) { const int r = a.residues[off + t]; seq[t] = (uint8_t)(r < a.Kp ? r : a.Kp - 1); }
-      __builtin_amdgcn_wave_barrier();
+      if constexpr (LONGQ) wave_mem_sync(); else __builtin_amdgcn_wave_barrier();
       // ---------------- A.2 multihit Forward and Backward of the whole sequence, special states only
       const GLen cm = glen_config(L, true), cu = glen_config(L, false);
       const double fwd = gforward<false>(m, seq, L, cm, mx, lane, xsF);
@@ -577,11 +601,12 @@ __device__ __forceinline__ float gatef(double t, float v) { return t > 0.0 ? v :
 __device__ __forceinline__ float ldf(const double *p) { return (float)__builtin_nontemporal_load(p); }
 }  // namespace
 
-__global__ __launch_bounds__(64, 3) void generic_align_kernel(GenericAlignArgs a) {
+__global__ __launch_bounds__(64, 3) void WH_GENERIC_ALIGN(GenericAlignArgs a) {
   extern __shared__ __attribute__((aligned(16))) int lds_raw[];
   const int lane = threadIdx.x;
   uint8_t *seq = reinterpret_cast<uint8_t *>(lds_raw);
   double *slab = a.slab + (size_t)blockIdx.x * a.slab_stride;
+  if constexpr (LONGQ) seq = reinterpret_cast<uint8_t *>(slab + (a.slab_stride - seq_doubles(a.Lcap)));
   enum { oN = 0, oB, oE, oJ, oC };
   for (;;) {
     int item = 0;
@@ -608,7 +633,7 @@ __global__ __launch_bounds__(64, 3) void generic_align_kernel(GenericAlignArgs a
     for (int t = lane; t < L; t += 64) cols[t] = -1;
     if (L <= 0 || L > a.Lcap) continue;
     for (int t = lane; t < L; t += 64) { const int r = a.residues[off + t]; seq[t] = (uint8_t)(r < a.Kp ? r : a.Kp - 1); }
-    __builtin_amdgcn_wave_barrier();
+    if constexpr (LONGQ) wave_mem_sync(); else __builtin_amdgcn_wave_barrier();
     const GLen c = glen_config(L, false);
     const double fwd = gforward<true>(m, seq, L, c, mx, lane);
     if (!isfinite(fwd)) { if (lane == 0 && a.status) a.status[p] = 1; continue; }
@@ -806,10 +831,73 @@ __global__ __launch_bounds__(64, 3) void generic_align_kernel(GenericAlignArgs a
   }
 }
 
-hipError_t launch_generic_front(const GenericArgs &a, int blocks, size_t lds, hipStream_t s) {
+#if WH_GENERIC_LONGQ
+hipError_t launch_generic_front_long(const GenericArgs &a, int blocks, size_t lds, hipStream_t s) {
+  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&generic_front_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(generic_front_long_kernel, dim3(blocks), dim3(64), lds, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_generic_align_long(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s) {
+  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&generic_align_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(generic_align_long_kernel, dim3(blocks), dim3(64), lds, s, a);
+  return hipGetLastError();
+}
+#else
+hipError_t launch_generic_front_long(const GenericArgs &a, int blocks, size_t lds, hipStream_t s);
+hipError_t launch_generic_align_long(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s);
+
+// <longq>: the instantiation that keeps the residues in the wave's slab, behind what the kernel lays out in it
+hipError_t launch_generic_front(const GenericArgs &a, int blocks, size_t lds, hipStream_t s, bool longq) {
+  if (longq ? a.slab_stride < generic_front_doubles(a.Lcap, a.Qmax) + generic_seq_doubles(a.Lcap) || lds < generic_lds_bytes(0) : lds < generic_lds_bytes(a.Lcap)) return hipErrorInvalidValue;
+  if (longq) return launch_generic_front_long(a, blocks, lds, s);
   hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&generic_front_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(generic_front_kernel, dim3(blocks), dim3(64), lds, s, a);
+  return hipGetLastError();
+}
+
+// ---- the long-query scoring pass (wh_host_score.hip): the queries longer than <Lmain>, counted and listed (in no particular
+// order; <count2>: their number and the longest), then their pairs on every model, model by model
+__global__ void long_queries_kernel(const int64_t *offsets, int64_t nq, int Lmain, int *count2, int64_t *qlist) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  const int64_t L = offsets[q + 1] - offsets[q];
+  if (L <= (int64_t)Lmain) return;
+  const int t = atomicAdd(count2, 1);
+  qlist[t] = q;                         // (the list holds nq entries)
+  atomicMax(count2 + 1, (int)L);
+}
+__global__ void long_pairs_kernel(const int64_t *qlist, int n_long, int H, int64_t *pair_list) {
+  const int64_t n = (int64_t)n_long * H;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+    pair_list[t] = qlist[t % n_long] * H + t / n_long;
+}
+// The front end's pair-list mode leaves the Forward log-odds of a pair to the kernel that scored it first; the pairs of the
+// long-query scoring pass have no other: taken from their records.
+__global__ void long_fwd_bits_kernel(const ResolveRec *recs, int n, int H, float *fwd_bits, wh_pair_detail *detail) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const size_t out = (size_t)recs[t].q * H + recs[t].h;
+  const float v = recs[t].fwd_bits;
+  if (fwd_bits) fwd_bits[out] = v;
+  if (detail) detail[out].fwd_bits = v;
+}
+hipError_t launch_long_queries(const int64_t *offsets, int64_t nq, int Lmain, int *count2, int64_t *qlist, hipStream_t s) {
+  if (nq < 1) return hipSuccess;
+  hipLaunchKernelGGL(long_queries_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, offsets, nq, Lmain, count2, qlist);
+  return hipGetLastError();
+}
+hipError_t launch_long_pairs(const int64_t *qlist, int n_long, int H, int64_t *pair_list, hipStream_t s) {
+  const int64_t n = (int64_t)n_long * H;
+  if (n < 1) return hipSuccess;
+  hipLaunchKernelGGL(long_pairs_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 8192)), dim3(256), 0, s, qlist, n_long, H, pair_list);
+  return hipGetLastError();
+}
+hipError_t launch_long_fwd_bits(const ResolveRec *recs, int n, int H, float *fwd_bits, wh_pair_detail *detail, hipStream_t s) {
+  if (n < 1 || (!fwd_bits && !detail)) return hipSuccess;
+  hipLaunchKernelGGL(long_fwd_bits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, recs, n, H, fwd_bits, detail);
   return hipGetLastError();
 }
 
@@ -831,11 +919,14 @@ hipError_t launch_trunc_list(const uint8_t *flags, int64_t npairs, int *count, i
   return hipGetLastError();
 }
 
-hipError_t launch_generic_align(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s) {
+hipError_t launch_generic_align(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s, bool longq) {
+  if (longq ? a.slab_stride < generic_align_doubles(a.Lcap, a.Qmax) + generic_seq_doubles(a.Lcap) : lds < (size_t)a.Lcap) return hipErrorInvalidValue;
+  if (longq) return launch_generic_align_long(a, blocks, lds, s);
   hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&generic_align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
   hipLaunchKernelGGL(generic_align_kernel, dim3(blocks), dim3(64), lds, s, a);
   return hipGetLastError();
 }
+#endif
 
 }  // namespace wh

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "wh_launch.h"
+#include "wh_plan.h"
 
 namespace wh {
 const char *last_error();
@@ -71,6 +72,9 @@ struct Knobs {
   bool no_big_region = false; // WH_NO_BIG_REGION: a region with more domains, segments or clusters than the resolver's lists hold keeps WH_FLAG_TRUNC (no big-region pass; tests)
   bool no_long_query = false; // WH_NO_LONG_QUERY: a call whose longest query exceeds the resolver's LDS cap runs without the resolver, as before the long-query pass (tests)
   bool no_resolve = false;   // multidomain regions stay ONE envelope (round-1 behaviour) instead of HMMER's stochastic resolver
+  int score_lmain = 0;       // WH_SCORE_LMAIN=<n>: the main length cap of scoring and alignment calls is at most n (tests: reaches the long-query scoring and alignment passes with short queries)
+  bool no_long_score = false; // WH_NO_LONG_SCORE: no long-query scoring / alignment pass - a call with a query beyond a class's LDS plan is refused (WH_ERANGE), as before the pass
+  bool longq_force = false;  // WH_LONGQ_FORCE: the passes run the float64 kernels' residues-in-HBM instantiations whatever the length (tests)
   int rqueue_cap = 0;        // test hook: size the resolver's queue for this many pairs instead of the estimate (forces the overflow re-run)
   int item_g = 0;            // queries per wave in a work item of the phase-call kernels (0 = 32; A/B)
   int st_units = 0;          // staged launches: envelope units (Forward slabs) per batch (0 = sized from the free HBM)
@@ -80,7 +84,7 @@ struct Knobs {
 };
 
 // ---- d_counter: 256 ints in HBM, zeroed at load.  Every owner of a slot or range, in one place: the kernels and the
-// wh_last_* getters depend on these numbers.  [60..62], [68..79], [89..95], [124..127], [144..159], [176..177], [192..255]
+// wh_last_* getters depend on these numbers.  [60..62], [68..79], [89..95], [124..127], [144..159], [192..255]
 // are free.
 enum CounterSlot {
   kSlotLaunch0 = 0,         // [0..59] work-queue heads of the launches of ONE call, in launch order: the one-wave scoring
@@ -99,6 +103,7 @@ enum CounterSlot {
   kScorePathInts = 16,      //   bytes of Forward rows stored, spare (wh_last_score_counters)
   kSlotWideScore = 160,     // [160..175] work-queue heads of the wide scoring launches, one per (cells per lane, waves) class
   kWideScoreClasses = 16,   //   (13 exist: 12 x 5..8, 16 x 7..8, 24 x 6..8, 48 x 5..8; WH_FORCE_WIDE adds smaller workgroups of one of them)
+  kSlotLongScore = 176,     // [176..177] long-query scoring pass: queries beyond the main length cap, the longest of them (long_queries_kernel)
   kSlotResolveFeedback = 178, // [178..191] what the resolver launches report and the lists they append to (wh_launch.h: ResolveFeedback)
   kResolveFeedbackInts = 14,
   kCounterInts = 256
@@ -107,7 +112,7 @@ static_assert(kSlotLaunch0 + kMaxLaunches <= kSlotConsensus && kSlotConsensus < 
               kSlotResolveWork < kSlotGenericFront && kSlotGenericFront < kSlotGenericAlign && kSlotGenericAlign < kSlotWideAlign, "d_counter slots overlap");
 static_assert(kSlotWideAlign + kWideAlignClasses <= kSlotAlignStat && kSlotAlignCycles >= kSlotAlignStat && kSlotAlignCycles + 8 <= kSlotAlignStat + kAlignStatInts &&
               kSlotAlignCycles % 2 == 0 && kSlotAlignStat + kAlignStatInts <= kSlotScorePath && kSlotScorePath % 2 == 0, "d_counter slots overlap");
-static_assert(kSlotScorePath + kScorePathInts <= kSlotWideScore && kSlotWideScore + kWideScoreClasses <= kSlotResolveFeedback &&
+static_assert(kSlotScorePath + kScorePathInts <= kSlotWideScore && kSlotWideScore + kWideScoreClasses <= kSlotLongScore && kSlotLongScore + 2 <= kSlotResolveFeedback &&
               kSlotResolveFeedback + kResolveFeedbackInts <= kCounterInts && kResolveFeedbackInts * sizeof(int) == sizeof(ResolveFeedback) &&
               (kSlotResolveFeedback * sizeof(int) + offsetof(ResolveFeedback, big_list)) % 8 == 0 && (kSlotResolveFeedback * sizeof(int) + offsetof(ResolveFeedback, long_list)) % 8 == 0,
               "d_counter slots overlap or leave the buffer, the resolver's feedback does not fill its range, or a list's address is not 8-byte aligned");
@@ -138,6 +143,9 @@ struct wh_ehmm {
   DevBuf d_biglist, d_bigsegs;              // ... queue positions of its pairs (two halves: read / written by a launch), its waves' list blocks
   int64_t last_long[2] = {0, 0};            // long-query pass of the last wh_score call: pairs redone, the longest query among them
   DevBuf d_longlist;                        // ... queue positions of its pairs
+  int64_t last_long_score[2] = {0, 0};      // long-query scoring pass of the last wh_score call: pairs scored by it, the longest query among them
+  int64_t last_long_align[2] = {0, 0};      // ... and the same of the last wh_align call's long-query alignment pass
+  DevBuf d_lqlist;                          // long-query scoring pass: the queries beyond the main length cap (their pairs: d_tlist)
   int64_t rq_cap = 0;                       // records the queue of the current scoring call holds
   double rq_rate = 0.0;                     // largest share of queued pairs any call on this handle has seen (sizes the next queue)
   int64_t rq_floor = 0;                     // ... at least this many (set when a call overflowed its estimate; the call then runs again)
@@ -199,26 +207,7 @@ static inline int timer_end(wh_ehmm *e, int which, hipStream_t s, int launches) 
   return WH_OK;
 }
 
-static const size_t kLdsBudget = 160 * 1024 - 512;
-static const size_t kLdsHeader = 16;   // work-item slot in front of the tables (keeps them 16-byte aligned)
-static inline int row_stride(int Lc) { return (Lc + 1 + 3) / 4 * 4; }        // floats of one per-row array: rows 0..Lc, 16-byte multiple
-static inline int residue_words(int Lc) { return (Lc + 3) / 4 + 4; }         // words of a wave's residue buffer
-// LDS of a workgroup: <header> bytes, the model's tables, <w> wave blocks of <wave_words> words; and the most waves (from
-// <w> down, 0 = none) of which <per_cu> such workgroups fit a CU.  (The alignment planner tests without the header.)
-static inline size_t lds_bytes(size_t header, size_t table, int w, int wave_words) { return header + table + (size_t)w * wave_words * sizeof(float); }
-static inline int fit_waves(size_t header, size_t table, int w, int wave_words, int per_cu = 1) {
-  while (w >= 1 && per_cu * lds_bytes(header, table, w, wave_words) > kLdsBudget) w--;
-  return w;
-}
-// Long models (pass-synchronous scoring and alignment): ONE orientation resident, four waves - one per SIMD, the kernel
-// uses the whole register file; the emission rows beside it where they fit (Klds = K), else read from L2 (Klds = 0).
-static inline bool plan_long_model(int Q, int K, int wave_words, int *Klds, size_t *lds) {
-  *Klds = K;
-  size_t table = (size_t)(K + 8) * Q * kWave * sizeof(float);
-  if (lds_bytes(kLdsHeader, table, 4, wave_words) > kLdsBudget) { *Klds = 0; table = (size_t)8 * Q * kWave * sizeof(float); }
-  *lds = lds_bytes(kLdsHeader, table, 4, wave_words);
-  return *lds <= kLdsBudget;
-}
+static_assert(kAlignSpecRows == kAlignSpecArrays, "wh_plan.h sizes the alignment kernel's special-state rows");
 
 // Resident workgroups are capped so that <per_block> bytes of per-wave workspace each fit in
 // about 70 % of the free HBM (the work-item counter loops tolerate fewer workgroups than CUs).
@@ -257,6 +246,7 @@ struct ScoreCall {
   const uint8_t *d_residues; const int64_t *d_offsets; int64_t nq, total_residues; int32_t max_len;
   int32_t *d_decibits; uint8_t *d_flags; float *d_fwd_bits; wh_pair_detail *d_detail;
   int Lc, H;
+  int Ls;                        // length cap of the scoring launches (= Lc unless a class cannot plan the call's longest query: long_score_pass scores the longer queries' pairs)
   int Lmain;                     // length cap of the main resolver launches (= Lc unless the longest query exceeds the resolver's LDS block: long_query_pass)
   int64_t npairs_all;
   bool resolve;                  // multidomain regions go through the resolver's queue (else: one envelope per region)
@@ -274,6 +264,34 @@ static inline void reset_resolver_counts(wh_ehmm *e) {
   e->last_long_list = 0;
   for (int64_t &v : e->last_big) v = 0;
   e->last_long[0] = e->last_long[1] = 0;
+  e->last_long_score[0] = e->last_long_score[1] = 0;
+}
+
+// what of the handle decides the LDS plans (wh_plan.h)
+static inline PlanKnobs plan_knobs(const wh_ehmm *e, bool p2win_force = false) {
+  const Knobs &k = e->knobs;
+  PlanKnobs pk;
+  pk.kernel = k.kernel; pk.max_waves = k.max_waves; pk.force_specg = k.force_specg; pk.no_window = k.no_window; pk.no_p2win = k.no_p2win; pk.p2win_force = p2win_force;
+  return pk;
+}
+static inline PlanClasses plan_classes(const wh_ehmm *e) {
+  PlanClasses cl;
+  cl.K = e->K;
+  for (auto &kv : e->by_q) {
+    cl.align_q.push_back(kv.first);
+    if (!(e->force_wide && e->dev[(size_t)kv.second[0]].wideW > 0)) cl.score_q.push_back(kv.first);   // (test hook: these models go through the wide kernel)
+  }
+  cl.wide = !e->wide_by_w.empty(); cl.force_wide = e->force_wide; cl.front = !e->generic_front.empty();
+  return cl;
+}
+// the main length cap of a scoring (alignment) call with the longest query <Lc>; <can_pass>: the call has what the long-query
+// pass needs, else - and under WH_NO_LONG_SCORE - the cap is Lc and the planner refuses what does not fit
+static inline int main_length_cap(const wh_ehmm *e, int Lc, bool align, bool can_pass, bool p2win_force = false) {
+  if (!can_pass || e->knobs.no_long_score) return Lc;
+  const PlanKnobs pk = plan_knobs(e, p2win_force);
+  const PlanClasses cl = plan_classes(e);
+  const int cap = align ? align_main_cap(pk, cl, Lc) : score_main_cap(pk, cl, Lc);
+  return e->knobs.score_lmain > 0 ? std::max(1, std::min(cap, e->knobs.score_lmain)) : cap;
 }
 
 // the fields ScoreArgs, WideArgs and GenericArgs have in common: models, queries, outputs, alphabet, resolver queue
@@ -282,7 +300,7 @@ template <class Args> static void fill_common(Args &a, const ScoreCall &c) {
   memset(&a, 0, sizeof a);
   a.hmms = (const DevHMM *)e->d_hmms.p;
   a.residues = c.d_residues; a.offsets = c.d_offsets; a.nq = c.nq;
-  a.Lcap = c.Lc;
+  a.Lcap = c.Ls;
   a.decibits = c.d_decibits; a.flags = c.d_flags; a.fwd_bits = c.d_fwd_bits; a.detail = c.d_detail;
   a.H = c.H; a.K = e->K; a.Kp = e->Kp;
   memcpy(a.degen, e->degen, sizeof a.degen);
@@ -306,19 +324,23 @@ template <int N> static int stats_read(const ScoreCall &c, const unsigned long l
 
 // The float64 front end (wh_generic.hip), one wavefront per pair: its arguments but for the work list (models of the
 // main launch, pairs of the long-list pass), and the wavefronts of a launch over <n_items> with their slabs in d_rmx.
-static inline GenericArgs front_args(const ScoreCall &c) {
+// <Lcap>: the launch's length cap, which sizes the slab; <longq>: the residues behind it (generic_front_long_kernel)
+static inline bool front_longq(const wh_ehmm *e, int Lcap) { return e->knobs.longq_force || generic_lds_bytes(Lcap) > kLdsBudget; }
+static inline GenericArgs front_args(const ScoreCall &c, int Lcap, bool longq = false) {
   GenericArgs g;
   fill_common(g, c);
+  g.Lcap = Lcap;
   g.gtab = (const double *)c.e->d_gtab.p;
   g.counter = c.e->counter(kSlotGenericFront);
   g.Qmax = c.e->max_Q;
-  g.slab_stride = (generic_front_doubles(c.Lc, c.e->max_Q) + 1) & ~(size_t)1;
+  g.slab_stride = (generic_front_doubles(Lcap, c.e->max_Q) + 1) & ~(size_t)1;
+  if (longq) g.slab_stride += generic_seq_doubles(Lcap);
   return g;
 }
 static inline int front_blocks(const ScoreCall &c, GenericArgs &g, int64_t n_items, const char *what, int *blocks) {
   wh_ehmm *e = c.e;
-  *blocks = (int)std::min<int64_t>(n_items, (int64_t)e->cu_count * std::min<size_t>(12, kLdsBudget / generic_lds_bytes(c.Lc)));
-  *blocks = clamp_blocks(*blocks, g.slab_stride * sizeof(double), e->d_rmx, e->max_M, c.Lc, what);
+  *blocks = (int)std::min<int64_t>(n_items, (int64_t)e->cu_count * std::min<size_t>(12, kLdsBudget / std::min(generic_lds_bytes(g.Lcap), kLdsBudget)));
+  *blocks = clamp_blocks(*blocks, g.slab_stride * sizeof(double), e->d_rmx, e->max_M, g.Lcap, what);
   if (*blocks < 0) return WH_ENOMEM;
   if (e->d_rmx.ensure((size_t)*blocks * g.slab_stride * sizeof(double))) return WH_ENOMEM;
   g.slab = (double *)e->d_rmx.p;

@@ -9,6 +9,8 @@ struct AlignCall {
   const uint8_t *d_residues; const int64_t *d_offsets; const int64_t *d_pair_q; const int32_t *d_pair_h; int64_t npairs;
   const int64_t *d_col_offsets; int32_t *d_cols;
   int32_t max_len; int Lc;
+  int Lm;                        // length cap of the class launches (= Lc unless a class cannot plan the call's longest query: the longer queries' pairs go to the float64 kernel)
+  int64_t n_long;                // such pairs of this call
   bool want_redo;                // pairs whose Backward sweep leaves float32 range are queued on the device and redone in log space
   int *d_redo_count; int32_t *d_redo_list;
   int launches;                  // of this call so far
@@ -34,31 +36,14 @@ static void group_by_model(const int32_t *pairs, int64_t n, const std::vector<in
   for (int64_t t = 0; t < n; t++) { const int32_t p = pairs ? pairs[t] : (int32_t)t; order[(size_t)cursor[(size_t)ph[(size_t)p]]++] = p; }
 }
 
-// LDS plan of the alignment kernel for one size class (waves, block, tables); workgroups and workspace come later
+// LDS plan of the alignment kernel for one size class (wh_plan.h: plan_align_lds); workgroups and workspace come later
 static int plan_align_class(const AlignCall &c, int Q, AlignClassPlan *out) {
-  const wh_ehmm *e = c.e;
-  const int Lc = c.Lc, K = e->K;
-  const size_t table = (size_t)(K + 2 * FW_NARR) * Q * kWave * sizeof(float);
+  AlignLds l;
+  const int why = plan_align_lds(c.e->knobs.force_specg, c.e->K, Q, c.Lm, &l);
+  if (why == 1) { set_error("query length %d with model class Q=%d does not fit in LDS", c.max_len, Q); return WH_ERANGE; }
+  if (why != 0) { set_error("model class Q=%d does not fit in LDS", Q); return WH_ERANGE; }
   AlignClassPlan p = {};
-  p.Q = Q; p.Klds = K; p.SP = row_stride(Lc);
-  if (Q <= kMaxQFast) {      // special states in LDS, up to eight waves
-    p.wave_lds = kAlignSpecArrays * p.SP + residue_words(Lc);
-    p.waves = std::max(0, fit_waves(0, table, 8, p.wave_lds));
-    p.lds = lds_bytes(kLdsHeader, table, p.waves, p.wave_lds);
-  }
-  p.swap = Q > kMaxQFast;
-  // 20/24-cell models whose emission rows (protein: 20) do not fit beside BOTH orientations even
-  // with the special states in HBM: pass-synchronous variant
-  if (!p.swap && Q >= 20 && (p.waves < 4 || e->knobs.force_specg) && lds_bytes(kLdsHeader, table, 4, residue_words(Lc)) > kLdsBudget) p.swap = true;
-  if (p.swap) {   // long models: one orientation resident, 4 waves, special states in HBM
-    p.spec_in_hbm = true; p.wave_lds = residue_words(Lc); p.waves = 4;
-    if (!plan_long_model(Q, K, p.wave_lds, &p.Klds, &p.lds)) { set_error("query length %d with model class Q=%d does not fit in LDS", c.max_len, Q); return WH_ERANGE; }
-  } else if (p.waves < 4 || e->knobs.force_specg) {   // long queries: special-state rows in HBM
-    p.spec_in_hbm = true; p.wave_lds = residue_words(Lc);
-    p.waves = fit_waves(kLdsHeader, table, 8, p.wave_lds);
-    if (p.waves < 1) { set_error("model class Q=%d does not fit in LDS", Q); return WH_ERANGE; }
-    p.lds = lds_bytes(kLdsHeader, table, p.waves, p.wave_lds);
-  }
+  p.Q = Q; p.waves = l.waves; p.SP = l.SP; p.wave_lds = l.wave_lds; p.Klds = l.Klds; p.lds = l.lds; p.spec_in_hbm = l.spec_in_hbm; p.swap = l.swap;
   *out = p;
   return WH_OK;
 }
@@ -90,9 +75,9 @@ static int align_pass(AlignCall &c, const std::vector<int32_t> &order, const std
   if (c.launches + (int)plans.size() > kMaxLaunches) { set_error("wh_align_dev: too many launches in one call"); return WH_ERANGE; }
   size_t need_scratch = 0, need_spec = 0;
   for (AlignClassPlan &p : plans) {
-    p.scratch_stride = (size_t)(c.Lc + 1) * 5 * p.Q * kWave;
+    p.scratch_stride = (size_t)(c.Lm + 1) * 5 * p.Q * kWave;
     p.spec_stride = p.spec_in_hbm ? (size_t)kAlignSpecArrays * p.SP : 0;
-    p.blocks = clamp_blocks(std::min(p.n_items, e->cu_count * std::max(1, 8 / p.waves)), (size_t)p.waves * (p.scratch_stride + p.spec_stride) * sizeof(float), e->d_ascratch, e->max_M, c.Lc, "alignment");
+    p.blocks = clamp_blocks(std::min(p.n_items, e->cu_count * std::max(1, 8 / p.waves)), (size_t)p.waves * (p.scratch_stride + p.spec_stride) * sizeof(float), e->d_ascratch, e->max_M, c.Lm, "alignment");
     if (p.blocks < 0) return WH_ENOMEM;
     need_scratch = std::max(need_scratch, (size_t)p.blocks * p.waves * p.scratch_stride * sizeof(float));
     need_spec = std::max(need_spec, (size_t)p.blocks * p.waves * p.spec_stride * sizeof(float));
@@ -110,7 +95,7 @@ static int align_pass(AlignCall &c, const std::vector<int32_t> &order, const std
     a.n_items = p.n_items;
     a.col_offsets = c.d_col_offsets; a.cols = c.d_cols;
     a.counter = e->counter(kSlotLaunch0 + c.launches);
-    a.Lcap = c.Lc; a.SP = p.SP; a.wave_lds = p.wave_lds;
+    a.Lcap = c.Lm; a.SP = p.SP; a.wave_lds = p.wave_lds;
     a.K = e->K; a.Kp = e->Kp; a.Klds = p.Klds; a.swap = p.swap ? 1 : 0;
     a.logsp = logsp ? 1 : 0;
     a.no_window = e->knobs.no_window ? 1 : 0;
@@ -223,6 +208,14 @@ static int align_wide(AlignCall &c, const std::map<int, std::vector<int32_t>> &w
 
 // pairs on models of more than 3072 nodes that the wide kernel does not serve: the any-size float64 alignment kernel
 // (wh_generic.hip), one wavefront per pair
+// doubles of one wave's slab of the any-size kernel for this call.  <longq>: a query beyond the LDS block (or, with pairs of
+// the long-query pass, WH_LONGQ_FORCE) - the residues behind the wave's slab
+static size_t align_float64_stride(const AlignCall &c, bool *longq) {
+  const wh_ehmm *e = c.e;
+  *longq = (size_t)c.Lc + 64 > kLdsBudget ? !e->knobs.no_long_score : e->knobs.longq_force && c.n_long > 0;
+  return ((generic_align_doubles(c.Lc, e->max_Q) + 1) & ~(size_t)1) + (*longq ? generic_seq_doubles(c.Lc) : 0);
+}
+
 static int align_float64(AlignCall &c, const std::vector<int32_t> &gitems) {
   wh_ehmm *e = c.e;
   hipStream_t s = c.s;
@@ -239,8 +232,9 @@ static int align_float64(AlignCall &c, const std::vector<int32_t> &gitems) {
   g.status = (int32_t *)e->d_recs.p;
   g.counter = e->counter(kSlotGenericAlign);
   g.Lcap = Lc; g.Qmax = e->max_Q; g.Kp = e->Kp;
-  g.slab_stride = (generic_align_doubles(Lc, e->max_Q) + 1) & ~(size_t)1;
-  const size_t glds = (size_t)Lc + 64;
+  bool longq = false;
+  g.slab_stride = align_float64_stride(c, &longq);
+  const size_t glds = longq ? 64 : (size_t)Lc + 64;
   if (glds > kLdsBudget) { set_error("query length %d does not fit the any-size kernel's LDS", c.max_len); return WH_ERANGE; }
   int blocks = (int)std::min<size_t>(gitems.size(), (size_t)e->cu_count * std::min<size_t>(12, kLdsBudget / glds));
   blocks = clamp_blocks(blocks, g.slab_stride * sizeof(double), e->d_rmx, e->max_M, Lc, "any-size alignment");
@@ -248,8 +242,8 @@ static int align_float64(AlignCall &c, const std::vector<int32_t> &gitems) {
   if (e->d_rmx.ensure((size_t)blocks * g.slab_stride * sizeof(double))) return WH_ENOMEM;
   g.slab = (double *)e->d_rmx.p;
   HIPCHK(hipMemsetAsync(g.counter, 0, sizeof(int), s));
-  if (e->knobs.trace) fprintf(stderr, "[wh] any-size alignment: %zu pairs, %d wavefronts, slab %zu MB per wave\n", gitems.size(), blocks, g.slab_stride * 8 >> 20);
-  hipError_t gerr = launch_generic_align(g, blocks, glds, s);
+  if (e->knobs.trace) fprintf(stderr, "[wh] any-size alignment: %zu pairs (%lld of queries beyond %d residues), %d wavefronts, slab %zu MB per wave%s\n", gitems.size(), (long long)c.n_long, c.Lm, blocks, g.slab_stride * 8 >> 20, longq ? ", residues in HBM" : "");
+  hipError_t gerr = launch_generic_align(g, blocks, glds, s, longq);
   if (gerr != hipSuccess) { set_error("any-size alignment kernel launch failed: %s", hipGetErrorString(gerr)); return WH_EHIP; }
   c.launches++;
   std::vector<int32_t> st((size_t)c.npairs);
@@ -286,12 +280,36 @@ extern "C" int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t
   const int H = (int)e->hmms.size();
   for (int64_t p = 0; p < npairs; p++)
     if (ph[(size_t)p] < 0 || ph[(size_t)p] >= H) { set_error("pair %lld: model position %d out of range", (long long)p, ph[(size_t)p]); return WH_EINVAL; }
-  group_by_model(nullptr, npairs, ph, H, order, cnt);
-  // a pair on a model beyond the register kernels may end on the float64 kernel: refuse the call before anything is
-  // launched when not even one wave's slab of that kernel fits on the device
+  // The class launches keep the query in LDS.  A call whose longest query a size class cannot plan sizes them for the lengths
+  // every class accepts (wh_plan.h); the pairs of longer queries on those classes' models are aligned by the any-size float64
+  // kernel, which serves models beyond 3 072 nodes from a pair list already.  Every other pair keeps its class launch.
+  c.Lm = main_length_cap(e, c.Lc, true, true);
+  c.n_long = 0;
+  e->last_long_align[0] = e->last_long_align[1] = 0;
+  std::vector<int32_t> short_pairs, long_pairs;
+  if (c.Lm < c.Lc) {
+    std::vector<int64_t> offs((size_t)nq + 1), pq((size_t)npairs);
+    HIPCHK(hipMemcpyAsync(offs.data(), d_offsets, sizeof(int64_t) * offs.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pq.data(), d_pair_q, sizeof(int64_t) * pq.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int64_t p = 0; p < npairs; p++) {
+      const int64_t q = pq[(size_t)p];
+      if (q < 0 || q >= nq) { set_error("pair %lld: query %lld out of range", (long long)p, (long long)q); return WH_EINVAL; }
+      const int64_t L = offs[(size_t)q + 1] - offs[(size_t)q];
+      if (L > c.Lm && e->dev[(size_t)ph[(size_t)p]].Q <= kMaxQ) { long_pairs.push_back((int32_t)p); e->last_long_align[1] = std::max<int64_t>(e->last_long_align[1], L); }
+      else short_pairs.push_back((int32_t)p);
+    }
+    c.n_long = (int64_t)long_pairs.size();
+    e->last_long_align[0] = c.n_long;
+  }
+  if (c.n_long > 0) group_by_model(short_pairs.data(), (int64_t)short_pairs.size(), ph, H, order, cnt);
+  else group_by_model(nullptr, npairs, ph, H, order, cnt);
+  // a pair on a model beyond the register kernels may end on the float64 kernel, a pair of the long-query pass does: refuse
+  // the call before anything is launched when not even one wave's slab of that kernel fits on the device
   for (int h = 0; h < H; h++)
-    if (cnt[(size_t)h + 1] > cnt[(size_t)h] && e->dev[(size_t)h].Q > kMaxQ) {
-      if (!one_block_fits(((generic_align_doubles(c.Lc, e->max_Q) + 1) & ~(size_t)1) * sizeof(double), e->d_rmx, e->max_M, c.Lc, "any-size alignment"))
+    if (c.n_long > 0 || (cnt[(size_t)h + 1] > cnt[(size_t)h] && e->dev[(size_t)h].Q > kMaxQ)) {
+      bool longq = false;
+      if (!one_block_fits(align_float64_stride(c, &longq) * sizeof(double), e->d_rmx, e->max_M, c.Lc, "any-size alignment"))
         return WH_ENOMEM;
       break;
     }
@@ -303,25 +321,31 @@ extern "C" int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t
   HIPCHK(hipMemsetAsync(c.d_redo_count, 0, sizeof(int), s));
   HIPCHK(hipMemsetAsync(e->counter(kSlotAlignStat), 0, kAlignStatInts * sizeof(int), s));
   if (timer_begin(e, 2, s)) return WH_EHIP;
-  if (int rc = align_pass(c, order, cnt, false)) return rc;
   int n_redo = 0;
-  if (int rc = align_logspace_pass(c, ph, &n_redo)) return rc;
+  if (!order.empty()) {          // (empty: every pair of the call is the long-query pass's)
+    if (int rc = align_pass(c, order, cnt, false)) return rc;
+    if (int rc = align_logspace_pass(c, ph, &n_redo)) return rc;
+  }
   if (int rc = read_align_stats(c)) return rc;
   e->last_align_redo = n_redo;
   e->last_align_unaligned = 0;
   e->last_unaligned_pairs.clear();
-  if (!e->generic.empty() || e->force_wide) {
+  if (!e->generic.empty() || e->force_wide || c.n_long > 0) {
     // models of 3 073 - 12 288 nodes go to the wide kernel; pairs that leave float32 range there, longer queries and
     // larger models (the 48-cell scoring class included) to the float64 kernel
     const bool use_wide = wide_align_lds_bytes(c.Lc) <= kLdsBudget && !e->wide_by_w.empty() && !e->knobs.no_wide_align;
-    std::vector<int32_t> gitems;
+    std::vector<int32_t> gitems(long_pairs);
     std::map<int, std::vector<int32_t>> witems;
+    std::vector<char> is_long(c.n_long > 0 ? (size_t)npairs : 0, 0);
+    for (int32_t p : long_pairs) is_long[(size_t)p] = 1;
     for (int64_t p = 0; p < npairs; p++) {
       const DevHMM &dm = e->dev[(size_t)ph[(size_t)p]];
+      if (c.n_long > 0 && is_long[(size_t)p]) continue;
       if (use_wide && dm.wideW > 0 && dm.wideQ != kWideQBig && (dm.Q > kMaxQ || e->force_wide)) witems[dm.wideQ * 16 + dm.wideW].push_back((int32_t)p);
       else if (dm.Q > kMaxQ) gitems.push_back((int32_t)p);
     }
     if (!witems.empty()) if (int rc = align_wide(c, witems, gitems)) return rc;
+    std::sort(gitems.begin(), gitems.end());
     if (!gitems.empty()) if (int rc = align_float64(c, gitems)) return rc;
   }
   if (timer_end(e, 2, s, c.launches)) return WH_EHIP;

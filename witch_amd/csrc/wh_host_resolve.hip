@@ -328,18 +328,68 @@ static int resolve_queue(const ScoreCall &c, int n_multi, const int32_t *rext, i
   return r.stats ? print_resolver_stats(c, r, n_multi, blocks, waves) : WH_OK;
 }
 
+// Rounds of the float64 front end in its pair-list mode (wh_generic.hip) over the <n> pairs of <d_pairs>, each followed by a
+// resolver launch of its own over the round's records, which reads the regions from the round's list in HBM and sums over
+// all envelopes, and by that launch's follow-up passes.  <Lcap>: the longest query among the pairs - it sizes the slabs and
+// the region lists, which hold every region a sequence of that length can have.  <first>: no kernel has scored the pairs
+// (long-query scoring pass): their Forward log-odds are written too, and the residues-in-HBM instantiation serves a cap
+// beyond the LDS block.  The main launch's queue is overwritten.
+static int front_rounds(const ScoreCall &c, const int64_t *d_pairs, int n, int Lcap, bool first, const char *what, int *rlaunches, int64_t *done) {
+  wh_ehmm *e = c.e;
+  hipStream_t s = c.s;
+  const bool longq = first && front_longq(e, Lcap);
+  // a region is at least two rows long (the row that triggers it and a later one that ends it)
+  const int ext_cap = Lcap / 2 + 2;
+  const int64_t rext_stride = (int64_t)kRextInts * ext_cap;
+  // rounds of as many pairs as 256 MB of region lists hold
+  const int per_round = (int)std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)64 << 20) / rext_stride));
+  if (e->d_rext.ensure(sizeof(int32_t) * (size_t)per_round * (size_t)rext_stride)) return WH_ENOMEM;
+  if (e->d_rrecs.cap < sizeof(ResolveRec) * (size_t)per_round) {
+    HIPCHK(hipStreamSynchronize(s));
+    if (e->d_rrecs.ensure(sizeof(ResolveRec) * (size_t)per_round)) return WH_ENOMEM;
+  }
+  e->rq_cap = std::max<int64_t>(e->rq_cap, per_round);
+  if (e->knobs.trace) fprintf(stderr, "[wh] %s: %d pairs, %d per round, queries of up to %d residues, up to %d regions each%s\n", what, n, per_round, Lcap, ext_cap, longq ? ", residues in HBM" : "");
+  for (int t0 = 0; t0 < n; t0 += per_round) {
+    const int n_round = std::min(per_round, n - t0);
+    GenericArgs g = front_args(c, Lcap, longq);
+    g.fwd_bits = nullptr;
+    g.rcap = n_round;
+    g.pair_list = d_pairs + t0; g.n_pairs = n_round;
+    g.rext = (int32_t *)e->d_rext.p; g.rext_stride = rext_stride; g.ext_cap = ext_cap;
+    int gblocks = 0;
+    if (int rc = front_blocks(c, g, n_round, what, &gblocks)) return rc;
+    HIPCHK(hipMemsetAsync(g.counter, 0, sizeof(int), s));
+    hipError_t gerr = launch_generic_front(g, gblocks, generic_lds_bytes(longq ? 0 : Lcap), s, longq);
+    if (gerr == hipSuccess && first) gerr = launch_long_fwd_bits((const ResolveRec *)e->d_rrecs.p, n_round, c.H, c.d_fwd_bits, c.d_detail, s);
+    if (gerr != hipSuccess) { set_error("%s: front kernel launch failed: %s", what, hipGetErrorString(gerr)); return WH_EHIP; }
+    // the resolver's queue is now this round's records: length and work-queue head
+    const int two[2] = {n_round, 0};
+    HIPCHK(hipMemcpyAsync(e->counter(kSlotResolveCount), two, sizeof two, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (int rc = resolve_queue(c, n_round, (const int32_t *)e->d_rext.p, rext_stride, rlaunches)) return rc;
+    *done += n_round;
+    if (!e->knobs.no_big_region || c.Lmain < c.Lc) {
+      // (a pair with many regions can have a big one among them, or a query beyond the main launch's cap; this read-back is
+      // paid by calls that have such pairs only)
+      ResolveFeedback fb;
+      if (int rc = read_feedback(c, &fb)) return rc;
+      if (int rc = follow_up(c, fb, {(const int32_t *)e->d_rext.p, rext_stride, n_round}, rlaunches)) return rc;
+    }
+  }
+  return WH_OK;
+}
+
 // ---- the long-list pass.  The scoring kernels keep the regions of a pair in a list of WH_MAX_ENVELOPES entries in LDS;
 // HMMER has no such limit.  A pair with more regions comes out of them flagged WH_FLAG_TRUNC - and is scored
 // AGAIN here: the any-size float64 front end (wh_generic.hip) with a region list in HBM that holds every region a
-// sequence of this length can have, then a resolver launch of its own that reads the regions from that list and sums
-// over all envelopes.  Costs one pass over the flags (a byte per pair) and one 4-byte read-back per call; the float64
-// kernels run only when a pair needs them.
+// sequence of this length can have, then a resolver launch of its own (front_rounds).  Costs one pass over the flags (a
+// byte per pair) and one 4-byte read-back per call; the float64 kernels run only when a pair needs them.
 // <n_multi>: length of the main launch's queue, whose big-region and long-query counts come back with this pass's own count
 // (ONE read-back of the feedback block per call for all of them); <long_list> false: only that.
 static int long_list_pass(const ScoreCall &c, int n_multi, bool long_list, int *rlaunches) {
   wh_ehmm *e = c.e;
   hipStream_t s = c.s;
-  const int Lc = c.Lc;
   int *d_tcount = &e->d_feedback()->long_list_pairs;
   const int list_cap = (int)std::min<int64_t>(c.npairs_all, (int64_t)1 << 22);
   HIPCHK(hipMemsetAsync(d_tcount, 0, sizeof(int), s));
@@ -356,42 +406,37 @@ static int long_list_pass(const ScoreCall &c, int n_multi, bool long_list, int *
   if (n_multi > 0) if (int rc = follow_up(c, fb, {nullptr, 0, n_multi}, rlaunches)) return rc;
   const int n_trunc = std::min(fb.long_list_pairs, list_cap);          // (beyond four million such pairs in one call the rest stay flagged)
   if (n_trunc <= 0) return WH_OK;
-  // a region is at least two rows long (the row that triggers it and a later one that ends it)
-  const int ext_cap = Lc / 2 + 2;
-  const int64_t rext_stride = (int64_t)kRextInts * ext_cap;
-  // rounds of as many pairs as 256 MB of region lists hold
-  const int per_round = (int)std::max<int64_t>(1, std::min<int64_t>(n_trunc, ((int64_t)64 << 20) / rext_stride));
-  if (e->d_rext.ensure(sizeof(int32_t) * (size_t)per_round * (size_t)rext_stride)) return WH_ENOMEM;
-  if (e->d_rrecs.cap < sizeof(ResolveRec) * (size_t)per_round) {
+  // (the flagged pairs were scored by the main launches: none is longer than their cap)
+  return front_rounds(c, (const int64_t *)e->d_tlist.p, n_trunc, c.Ls, false, "long-list pass", rlaunches, &e->last_long_list);
+}
+
+// ---- the long-query scoring pass.  The scoring launches of a call are sized for the length cap c.Ls and leave the pairs of
+// longer queries alone (decibits 0, no flag); those pairs - every model of every such query - are listed on the device and
+// scored here by the float64 front end and the resolver (front_rounds), one wavefront per pair: a correctness path, not a
+// fast one.  Runs after every other pass of the call (it overwrites the resolver's queue).
+static int long_score_pass(const ScoreCall &c, int *rlaunches) {
+  wh_ehmm *e = c.e;
+  hipStream_t s = c.s;
+  int *d_count2 = e->counter(kSlotLongScore);
+  if (e->d_lqlist.ensure(sizeof(int64_t) * (size_t)c.nq)) return WH_ENOMEM;
+  HIPCHK(hipMemsetAsync(d_count2, 0, 2 * sizeof(int), s));
+  hipError_t err = launch_long_queries(c.d_offsets, c.nq, c.Ls, d_count2, (int64_t *)e->d_lqlist.p, s);
+  if (err != hipSuccess) { set_error("long-query scoring pass: query scan launch failed: %s", hipGetErrorString(err)); return WH_EHIP; }
+  int count2[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(count2, d_count2, sizeof count2, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const int64_t n = (int64_t)count2[0] * c.H;
+  if (n <= 0) return WH_OK;
+  if (e->d_tlist.ensure(sizeof(int64_t) * (size_t)n)) return WH_ENOMEM;
+  err = launch_long_pairs((const int64_t *)e->d_lqlist.p, count2[0], c.H, (int64_t *)e->d_tlist.p, s);
+  if (err != hipSuccess) { set_error("long-query scoring pass: pair list launch failed: %s", hipGetErrorString(err)); return WH_EHIP; }
+  e->last_long_score[1] = count2[1];
+  const auto t0 = std::chrono::steady_clock::now();
+  if (int rc = front_rounds(c, (const int64_t *)e->d_tlist.p, (int)n, std::min(c.Lc, std::max(count2[1], 1)), true, "long-query scoring pass", rlaunches, &e->last_long_score[0])) return rc;
+  if (e->knobs.trace) {
     HIPCHK(hipStreamSynchronize(s));
-    if (e->d_rrecs.ensure(sizeof(ResolveRec) * (size_t)per_round)) return WH_ENOMEM;
-  }
-  e->rq_cap = std::max<int64_t>(e->rq_cap, per_round);
-  if (e->knobs.trace) fprintf(stderr, "[wh] long-list pass: %d pairs with more than %d regions, %d per round, up to %d regions each\n", n_trunc, WH_MAX_ENVELOPES, per_round, ext_cap);
-  for (int t0 = 0; t0 < n_trunc; t0 += per_round) {
-    const int n_round = std::min(per_round, n_trunc - t0);
-    GenericArgs g = front_args(c);
-    g.fwd_bits = nullptr;
-    g.rcap = n_round;
-    g.pair_list = (const int64_t *)e->d_tlist.p + t0; g.n_pairs = n_round;
-    g.rext = (int32_t *)e->d_rext.p; g.rext_stride = rext_stride; g.ext_cap = ext_cap;
-    int gblocks = 0;
-    if (int rc = front_blocks(c, g, n_round, "long-list front end", &gblocks)) return rc;
-    HIPCHK(hipMemsetAsync(g.counter, 0, sizeof(int), s));
-    hipError_t gerr = launch_generic_front(g, gblocks, generic_lds_bytes(Lc), s);
-    if (gerr != hipSuccess) { set_error("long-list front kernel launch failed: %s", hipGetErrorString(gerr)); return WH_EHIP; }
-    // the resolver's queue is now this round's records: length and work-queue head
-    const int two[2] = {n_round, 0};
-    HIPCHK(hipMemcpyAsync(e->counter(kSlotResolveCount), two, sizeof two, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (int rc = resolve_queue(c, n_round, (const int32_t *)e->d_rext.p, rext_stride, rlaunches)) return rc;
-    e->last_long_list += n_round;
-    if (!e->knobs.no_big_region || c.Lmain < c.Lc) {
-      // (a pair with many regions can have a big one among them, or a query beyond the main launch's cap; this read-back is
-      // paid by calls that have such pairs only)
-      if (int rc = read_feedback(c, &fb)) return rc;
-      if (int rc = follow_up(c, fb, {(const int32_t *)e->d_rext.p, rext_stride, n_round}, rlaunches)) return rc;
-    }
+    fprintf(stderr, "[wh] long-query scoring pass: %lld pairs of %d queries beyond %d residues (longest %d): %.1f ms (host clock, resolver rounds included)\n",
+            (long long)n, count2[0], c.Ls, count2[1], std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   }
   return WH_OK;
 }
@@ -422,7 +467,8 @@ int resolver_stage(const ScoreCall &c, bool *overflow, int *rlaunches) {
   }
   if (n_multi > 0) if (int rc = resolve_queue(c, n_multi, nullptr, 0, rlaunches)) return rc;
   reset_resolver_counts(e);
-  const bool long_list = c.resolve && generic_lds_bytes(c.Lc) <= kLdsBudget && !e->knobs.no_long_list;
-  if (long_list || (n_multi > 0 && (!e->knobs.no_big_region || c.Lmain < c.Lc))) return long_list_pass(c, n_multi, long_list, rlaunches);
+  const bool long_list = c.resolve && generic_lds_bytes(c.Ls) <= kLdsBudget && !e->knobs.no_long_list;
+  if (long_list || (n_multi > 0 && (!e->knobs.no_big_region || c.Lmain < c.Lc))) if (int rc = long_list_pass(c, n_multi, long_list, rlaunches)) return rc;
+  if (c.Ls < c.Lc) return long_score_pass(c, rlaunches);
   return WH_OK;
 }

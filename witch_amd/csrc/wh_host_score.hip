@@ -4,9 +4,6 @@
 
 static const int kStagedMaxBatches = 1 << 15;   // staged launches: batches per scoring call (32 counters each: 4 MB)
 static const int kStagedQB = 48;                // ... queries per work item
-// per-row special-state arrays of a wave's LDS block in the phase-call scoring kernel (wh_score7.hip is built with
-// WH_SLIM_SPEC: N, B, E, J, C, scale; an envelope's mask words share the B / E slots)
-static const int kScoreSpecArrays = 6;
 
 // the longest query of which the main resolver launch keeps all its waves per CU (no staged tables): the length cap of the
 // main launches of a call that has a query beyond the resolver's LDS block
@@ -36,11 +33,14 @@ static ScoreCall score_call(wh_ehmm *e, const uint8_t *d_residues, const int64_t
   c.wide_dense = getenv("WH_WIDE_DENSE"); c.wide_no_em_lds = getenv("WH_WIDE_NO_EM_LDS"); c.p2win_force = getenv("WH_P2WIN_FORCE");
   c.res_null2_gather = getenv("WH_RES_NULL2_GATHER"); c.res_no_lds_tables = getenv("WH_RES_NO_LDS_TABLES");
   if (const char *wv = getenv("WH_RES_WAVES")) c.res_waves = std::max(1, atoi(wv));
+  // The scoring launches keep the query in LDS.  A call whose longest query a size class cannot plan sizes them for the
+  // lengths every class accepts (wh_plan.h); the pairs of longer queries are scored by the long-query scoring pass, which
+  // hands them to the resolver like the float64 front end does - so it needs the resolver.
+  c.Ls = main_length_cap(e, c.Lc, false, c.resolve, c.p2win_force);
   return c;
 }
 
 // ------------------------------------------------------------------------------------ plans of the one-wave classes
-struct LdsPlan { int waves, SP, wave_lds; size_t lds; };
 struct StagedWaves { int wl, one, both, p2, p4; };    // floats per wave block; waves of the dense kernels (one / both orientations) and of the light ones
 enum class ScoreFamily { PhaseCall, PhaseCallB, TwoQuery, FourEnvelope, PassSync, Staged };
 static const char *const kFamilyName[] = {"phase-call", "phase-call(B)", "two-queries-per-wave", "phase-call", "pass-synchronous", "staged"};
@@ -59,19 +59,8 @@ struct ScoreClassPlan {
   StagedWaves st;
 };
 
-static int cap_waves(const Knobs &kn, int w) { return kn.max_waves > 0 ? std::max(1, std::min(w, kn.max_waves)) : w; }
-static size_t score_table_bytes(const wh_ehmm *e, int Q) { return (size_t)(e->K + 2 * FW_NARR) * Q * kWave * sizeof(float); }   // K emission rows + both transition orientations
-
-// LDS plan of the phase-call scoring kernel: tables + per wave one block (special-state arrays, null2 table, region
-// list, residues), up to twelve waves.  <b> is left alone when not even one wave fits.
-static bool plan_block1(const wh_ehmm *e, int Q, int Lcap, int extra_arrays, LdsPlan *b) {
-  const int sp = row_stride(Lcap);
-  const int wl = (kScoreSpecArrays + extra_arrays) * sp + 32 + kRegsInts + residue_words(Lcap);
-  const int w = fit_waves(kLdsHeader, score_table_bytes(e, Q), cap_waves(e->knobs, 12), wl);
-  if (w < 1) return false;
-  *b = {w, sp, wl, lds_bytes(kLdsHeader, score_table_bytes(e, Q), w, wl)};
-  return true;
-}
+static int cap_waves(const Knobs &kn, int w) { return cap_waves(kn.max_waves, w); }
+static size_t score_table_bytes(const wh_ehmm *e, int Q) { return score_table_bytes(e->K, Q); }
 
 // ---- staged launches (wh_staged.hip): a workgroup draws G work items of kStagedQB queries at a time and deals their
 // candidates to its waves one by one
@@ -96,54 +85,22 @@ static bool plan_staged(const wh_ehmm *e, int Q, int Lc, StagedWaves *w) {
 }
 
 // The plan of one size class: kernel family, LDS block, work items, workspace per wave, resident workgroups.  Launches
-// nothing and allocates nothing.  Three kernels serve a size class:
-//  * phase-call kernel, special states in LDS: models of up to 24 cells per lane, short queries
-//  * the same kernel with the special-state rows in HBM ("SG"): long queries
-//  * pass-synchronous kernel (wh_score_big.hip): 28+ cells per lane, and 20/24-cell models whose
-//    emission rows do not fit in LDS beside both orientations (protein)
-// and three opt-in schedules (WH_SCORE_KERNEL = 9, 10 / 11, 12) take the classes and batches they fit.
+// nothing and allocates nothing.  Three kernels serve a size class
+// (wh_plan.h: plan_score_lds), and three opt-in schedules (WH_SCORE_KERNEL = 9, 10 / 11, 12) take the classes and batches they fit.
 static int plan_score_class(const ScoreCall &c, int Q, int list_off, int n_list, ScoreClassPlan *out) {
   const wh_ehmm *e = c.e;
   const Knobs &kn = e->knobs;
-  const int Lc = c.Lc;
+  const int Lc = c.Ls;
   const int64_t nq = c.nq;
   const size_t table = score_table_bytes(e, Q);
   ScoreClassPlan p = {};
   p.Q = Q; p.list_off = list_off; p.n_list = n_list;
+  ScoreLds l;
+  if (!plan_score_lds(plan_knobs(e, c.p2win_force), e->K, Q, Lc, true, &l)) { set_error("query length %d with model class Q=%d does not fit in LDS", c.max_len, Q); return WH_ERANGE; }
+  p.b = l.b; p.Klds = l.Klds;
   LdsPlan &b = p.b;
-  bool big = Q > kMaxQFast, specg = false, pairk = false, p2win = false, p2inpl = false, quadk = false;
-  if (!big && kn.kernel == 9 && !kn.force_specg && (Q == 8 || Q == 12 || Q == 16)) {
-    // two queries per wavefront (wh_score9.hip): eight waves, each with two blocks of per-row arrays
-    const int wl9 = 2 * score9_block_floats(row_stride(Lc), Lc), w9 = cap_waves(kn, 8);
-    if (lds_bytes(kLdsHeader, table, w9, wl9) <= kLdsBudget) { pairk = true; b = {w9, row_stride(Lc), wl9, lds_bytes(kLdsHeader, table, w9, wl9)}; }
-  }
-  if (!big && !pairk) {
-    // (twelve waves = three per SIMD at 168 registers; 20-cell models keep that since the six-array block, 24-cell
-    // models get the nine or ten waves that fit beside their 120 KB of tables)
-    bool ok = plan_block1(e, Q, Lc, 0, &b);
-    // ... and, where the waves still fit with them, three more per-row arrays per wave: the multihit Backward sweep then
-    // tries a node window first (wh_score7.hip, "P2 on a node window")
-    if (ok && b.waves >= 4 && !kn.force_specg && !kn.no_window && !kn.no_p2win && Q >= 8) {
-      LdsPlan b2 = {};
-      if (plan_block1(e, Q, Lc, 3, &b2) && (b2.waves >= b.waves || (c.p2win_force && b2.waves >= 8))) { p2win = true; b = b2; }
-      else if (Q >= 20 && kn.kernel != 9) p2inpl = true;      // round 5: the window sweep in place, P1's rows backed up in HBM (ScoreArgs::p2win == 2)
-    }
-    if (!ok || b.waves < 4 || kn.force_specg) {
-      specg = true;
-      b.SP = row_stride(Lc);
-      b.wave_lds = 32 + kRegsInts + residue_words(Lc);
-      b.waves = fit_waves(kLdsHeader, table, cap_waves(kn, Q <= 16 ? 12 : 8), b.wave_lds);
-      ok = b.waves >= 1;
-      b.lds = lds_bytes(kLdsHeader, table, b.waves, b.wave_lds);
-      if (Q >= 20 && (!ok || b.waves < 4)) big = true;
-    }
-    if (!big && !ok) { set_error("query length %d with model class Q=%d does not fit in LDS", c.max_len, Q); return WH_ERANGE; }
-  }
-  if (big) {
-    b.waves = 4; b.SP = row_stride(Lc); b.wave_lds = 32 + kRegsInts + residue_words(Lc);
-    if (!plan_long_model(Q, e->K, b.wave_lds, &p.Klds, &b.lds)) { set_error("query length %d with model class Q=%d does not fit in LDS", c.max_len, Q); return WH_ERANGE; }
-    specg = true;
-  }
+  const bool big = l.big, specg = l.specg, pairk = l.pairk, p2win = l.p2win, p2inpl = l.p2inpl;
+  bool quadk = false;
   // ---- staged launches (wh_staged.hip): short-query batches of the one-wave classes, special states in LDS
   if ((kn.kernel == 10 || kn.kernel == 11) && !e->st_off && !big && !pairk && !specg && !kn.dbg && (Q == 8 || Q == 12 || Q == 16 || Q == 20 || Q == 24) &&
       plan_staged(e, Q, Lc, &p.st)) {
@@ -277,7 +234,7 @@ static int launch_staged_class(const ScoreCall &c, const ScoreClassPlan &p, int 
   hipStream_t s = c.s;
   const Knobs &kn = e->knobs;
   const bool split = kn.kernel == 11;           // 11: P3 and P4 as launches of their own too (one Forward slab per envelope of a batch)
-  const int Q = p.Q, Lc = c.Lc, K = e->K, w_one = p.st.one, w_both = p.st.both, w_p2 = p.st.p2, w_p4 = p.st.p4;
+  const int Q = p.Q, Lc = c.Ls, K = e->K, w_one = p.st.one, w_both = p.st.both, w_p2 = p.st.p2, w_p4 = p.st.p4;
   auto lds_of = [&](int arrays, int waves, int cand) { return staged_lds(Q, p.st.wl, arrays, waves, cand); };
   ScoreArgs a = class_args(c, p, *launches);
   StagedArgs g;
@@ -461,7 +418,7 @@ static size_t wide_score_stride(int Lc, int wq, int W, bool sparse) {
 static int score_wide_classes(const ScoreCall &c, int *launches, bool *wide_done) {
   wh_ehmm *e = c.e;
   hipStream_t s = c.s;
-  const int Lc = c.Lc;
+  const int Lc = c.Ls;
   const size_t wlds0 = wide_lds_bytes(Lc);
   *wide_done = wlds0 <= kLdsBudget;
   if (!*wide_done && e->force_wide) { set_error("WH_FORCE_WIDE: query length %d does not fit the wide kernel's LDS block", c.max_len); return WH_ERANGE; }
@@ -515,12 +472,12 @@ static int score_front_end(const ScoreCall &c, bool wide_done, int *launches) {
     set_error("models of more than %d nodes need the resolver stage (query length %d, %lld pairs)", kMaxQ * kWave, c.max_len, (long long)c.npairs_all);
     return WH_ERANGE;
   }
-  GenericArgs g = front_args(c);
+  GenericArgs g = front_args(c, c.Ls);
   size_t goff = 0;
   for (auto &kv : e->by_q) goff += kv.second.size();
   const size_t n_gen = wide_done ? e->generic_front.size() : e->generic.size();     // (front list and wide lists are adjacent)
   g.hmm_list = (const int32_t *)e->d_lists.p + goff; g.n_list = (int)n_gen;
-  const size_t glds = generic_lds_bytes(c.Lc);
+  const size_t glds = generic_lds_bytes(c.Ls);
   if (glds > kLdsBudget) { set_error("query length %d does not fit the any-size kernel's LDS", c.max_len); return WH_ERANGE; }
   const int64_t n_items = c.nq * (int64_t)n_gen;
   int blocks = 0;
@@ -562,7 +519,7 @@ static int read_staged_counters(const ScoreCall &c, bool *over) {
 // sit between the two stages).  Bounded: skipped when it would take more than a tenth of the free HBM.
 static void prefetch_align_workspace(const ScoreCall &c) {
   wh_ehmm *e = c.e;
-  const size_t need = (size_t)8 * (size_t)e->cu_count * (size_t)(c.Lc + 1) * 5 * (size_t)e->by_q.rbegin()->first * kWave * sizeof(float);
+  const size_t need = (size_t)8 * (size_t)e->cu_count * (size_t)(c.Ls + 1) * 5 * (size_t)e->by_q.rbegin()->first * kWave * sizeof(float);
   size_t free_b = 0, total_b = 0;
   if (need > e->d_ascratch.cap && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need < free_b / 10) (void)e->d_ascratch.ensure(need);
 }
@@ -628,15 +585,18 @@ extern "C" int wh_score_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t
   // beyond the one-wave float32 kernels, long queries): otherwise the call is refused before anything is launched.  (The
   // resolver's and the long-list pass's slabs depend on what the scoring launches queue: they are checked when planned.)
   if (nq > 0 && !e->generic.empty() &&
-      !one_block_fits(((generic_front_doubles(c.Lc, e->max_Q) + 1) & ~(size_t)1) * sizeof(double), e->d_rmx, e->max_M, c.Lc, "any-size front end"))
+      !one_block_fits(((generic_front_doubles(c.Ls, e->max_Q) + 1) & ~(size_t)1) * sizeof(double), e->d_rmx, e->max_M, c.Ls, "any-size front end"))
     return WH_ENOMEM;
   if (nq > 0 && !e->wide_by_w.empty()) {
     if ((int)e->wide_by_w.size() > kWideScoreClasses) { set_error("too many classes of long models (%zu)", e->wide_by_w.size()); return WH_ERANGE; }
     for (auto &kv : e->wide_by_w)
-      if (wide_lds_bytes(c.Lc) <= kLdsBudget &&
-          !one_block_fits(wide_score_stride(c.Lc, kv.first >> 4, kv.first & 15, !c.wide_dense) * sizeof(float), e->d_wscratch, e->max_M, c.Lc, "wide scoring"))
+      if (wide_lds_bytes(c.Ls) <= kLdsBudget &&
+          !one_block_fits(wide_score_stride(c.Ls, kv.first >> 4, kv.first & 15, !c.wide_dense) * sizeof(float), e->d_wscratch, e->max_M, c.Ls, "wide scoring"))
         return WH_ENOMEM;
   }
+  // ... and one wave's float64 slab of the long-query scoring pass (gigabytes at 100 000 residues x 1 000 nodes)
+  if (c.Ls < c.Lc && !one_block_fits(front_args(c, c.Lc, front_longq(e, c.Lc)).slab_stride * sizeof(double), e->d_rmx, e->max_M, c.Lc, "long-query scoring pass"))
+    return WH_ENOMEM;
   // The queue of pairs with a multidomain region is sized by ESTIMATE (a per-pair record is 296 bytes; the worst case,
   // one record per pair, was 3.4 GB at the headline for a class that is 0.005 % of its pairs).  The kernels count every
   // pair that wants a slot; when the count exceeds the capacity, the queue is grown to the count and the scoring pass

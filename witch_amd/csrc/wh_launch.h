@@ -305,11 +305,20 @@ struct GenericAlignArgs {
   double *slab;
   size_t slab_stride;
 };
-hipError_t launch_generic_front(const GenericArgs &a, int blocks, size_t lds, hipStream_t s);
-hipError_t launch_generic_align(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s);
+// <longq>: the instantiations that read the residues from the wave's slab in HBM, for queries beyond generic_lds_bytes: the
+// copy takes the last generic_seq_doubles(Lcap) doubles of the slab (slab_stride covers them), the LDS block is
+// generic_lds_bytes(0) / any size
+hipError_t launch_generic_front(const GenericArgs &a, int blocks, size_t lds, hipStream_t s, bool longq = false);
+hipError_t launch_generic_align(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s, bool longq = false);
 size_t generic_front_doubles(int Lcap, int Qmax);
 size_t generic_align_doubles(int Lcap, int Qmax);
 size_t generic_lds_bytes(int Lcap);
+size_t generic_seq_doubles(int Lcap);
+// the long-query scoring pass: queries longer than <Lmain> (count2: their number, the longest), their pairs on every model,
+// and the Forward log-odds of those pairs from the records the front end wrote
+hipError_t launch_long_queries(const int64_t *offsets, int64_t nq, int Lmain, int *count2, int64_t *qlist, hipStream_t s);
+hipError_t launch_long_pairs(const int64_t *qlist, int n_long, int H, int64_t *pair_list, hipStream_t s);
+hipError_t launch_long_fwd_bits(const ResolveRec *recs, int n, int H, float *fwd_bits, wh_pair_detail *detail, hipStream_t s);
 
 // final transitive merge (wh_merge.hip)
 struct MergeArgs {

@@ -696,6 +696,7 @@ static hipError_t launch_big_th(const ScoreArgs &a, int blocks, int threads, siz
 hipError_t WH_BIG_LAUNCH(int Q, const ScoreArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
   if (threads != WH_BIG_TH) return hipErrorInvalidValue;
   switch (Q) {
+    case 16: return launch_big_th<16, WH_BIG_TH>(a, blocks, threads, lds, s);     // (queries that leave a 16-cell class no wave beside its tables)
     case 20: return launch_big_th<20, WH_BIG_TH>(a, blocks, threads, lds, s);
     case 24: return launch_big_th<24, WH_BIG_TH>(a, blocks, threads, lds, s);
     case 28: return launch_big_th<28, WH_BIG_TH>(a, blocks, threads, lds, s);

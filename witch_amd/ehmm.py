@@ -147,6 +147,27 @@ class EHMM:
         check(lib().wh_last_long_query_pairs(self._h, o2.ctypes.data), "wh_last_long_query_pairs")
         return int(o2[0]), int(o2[1])
 
+    def last_long_score(self):
+        """The long-query scoring pass of the last score call: (pairs it scored because their query is longer than the length
+        cap of the call's scoring launches, the longest query among them); (0, 0) when every size class planned the call's
+        longest query.  include/witch_hip.h: wh_last_long_score_pairs."""
+        o2 = np.zeros(2, dtype=np.int64)
+        check(lib().wh_last_long_score_pairs(self._h, o2.ctypes.data), "wh_last_long_score_pairs")
+        return int(o2[0]), int(o2[1])
+
+    def last_long_align(self):
+        """The same for the last align call: (pairs handed to the any-size float64 alignment kernel for their query's length,
+        the longest query among them).  include/witch_hip.h: wh_last_long_align_pairs."""
+        o2 = np.zeros(2, dtype=np.int64)
+        check(lib().wh_last_long_align_pairs(self._h, o2.ctypes.data), "wh_last_long_align_pairs")
+        return int(o2[0]), int(o2[1])
+
+    def max_query_len(self) -> int:
+        """Length up to which queries stay on the float32 kernels (include/witch_hip.h: wh_ehmm_max_query_len)."""
+        n = lib().wh_ehmm_max_query_len(self._h)
+        check(min(n, 0), "wh_ehmm_max_query_len")
+        return int(n)
+
     def set_path_buffer(self, paths_t):
         """Registers a CUDA uint8 tensor of nq x H bytes that later score calls fill with WH_PATH_* bits per pair
         (staged launches only; None switches it off).  The caller keeps the tensor alive (include/witch_hip.h)."""

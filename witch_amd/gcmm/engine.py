@@ -63,6 +63,7 @@ class QueryAlignmentEngine:
         self.long_list_pairs = 0      # pairs with more regions than a scoring kernel lists, scored in full by the long-list pass
         self.big_region_pairs = 0     # pairs with a region beyond the resolver's fixed lists, scored in full by the big-region pass
         self.long_query_pairs = 0     # pairs of queries beyond the resolver's LDS block, resolved by the long-query pass
+        self.long_score_pairs = 0     # pairs of queries beyond a scoring class's LDS plan, scored by the long-query scoring pass
         self.unaligned_pairs = []     # (taxon, hmm label) the alignment stage returned unaligned
         self.query_text = None        # uint8: the local queries' characters (upper-cased on read), concatenated like query_offsets
         self.device = 0
@@ -148,6 +149,7 @@ class QueryAlignmentEngine:
             self.long_list_pairs += e.last_long_list_pairs()
             self.big_region_pairs += e.last_region_overflow()["pairs"]
             self.long_query_pairs += e.last_long_queries()[0]
+            self.long_score_pairs += e.last_long_score()[0]
             if multidomain_policy == "drop":
                 drop = (flags & 2) != 0
                 flags = np.where(drop, flags & ~np.uint8(1), flags).astype(np.uint8)
