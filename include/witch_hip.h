@@ -83,9 +83,9 @@ extern "C" {
  * multidomain regions stay one envelope).  The value stays 8 for binary compatibility. */
 #define WH_MAX_ENVELOPES 16
 
-/* Which code path a pair took through the scoring kernels (optional per-pair byte, wh_set_path_buffer; written by
- * the staged launches only).  A pair's result does not depend on the path except in the last bits of the float32
- * null2 correction (window vs full width): the tests draw their oracle samples per path. */
+/* Which code path a pair took through the scoring kernels: an optional per-pair record, 16 bits (wh_set_path_buffer16)
+ * or the low byte alone (wh_set_path_buffer).  A pair's result does not depend on the path except in the last bits of
+ * the float32 null2 correction (window vs full width): the tests draw their oracle samples per path. */
 #define WH_PATH_P2_WIN     1   /* regions from the multihit Backward sweep on a node window (certified)  */
 #define WH_PATH_P2_FULL    2   /* ... from the full-width sweep (no window fitted, or a decision in doubt) */
 #define WH_PATH_P4_W256    4   /* an envelope's Backward sweep kept from a 256-node window                */
@@ -94,6 +94,12 @@ extern "C" {
 #define WH_PATH_P4_FULL   32   /* an envelope's Backward sweep at full width                              */
 #define WH_PATH_DENSE     64   /* an envelope redone with every Forward row stored (WH_FLAG_EXACT)        */
 #define WH_PATH_MULTI    128   /* finished by the multidomain resolver                                    */
+/* ... and what was stored of an envelope's Forward rows (16-bit record only; the three attempts: envelope_attempts,
+ * wh_score7.hip): */
+#define WH_PATH_BAND_KEPT 256  /* an envelope accepted from the banded store (lane blocks around P1's dominant path) */
+#define WH_PATH_BAND_FAIL 512  /* an envelope's band failed its mass certificate and the rows were stored again
+                                  unbanded - whether that store was then accepted or the dense one followed (then
+                                  WH_PATH_DENSE is set as well).  An envelope without a band sets neither bit.       */
 
 typedef struct wh_ehmm wh_ehmm;
 
@@ -218,11 +224,27 @@ int wh_last_long_query_pairs(wh_ehmm *e, int64_t out[2]);
 int wh_last_long_score_pairs(wh_ehmm *e, int64_t out[2]);
 int wh_last_long_align_pairs(wh_ehmm *e, int64_t out[2]);
 
-/* Optional per-PAIR record of the same: a device array of nq x H bytes that the scoring calls made after this one fill
- * with WH_PATH_* bits (NULL switches it off again).  Written by the staged launches only (WH_SCORE_KERNEL=10; pairs
- * of the other kernels keep whatever the array held).  The buffer belongs to the caller and must stay valid for as many
- * pairs as the calls score.  tests/test_gpu_parity.py draws its headline-size oracle samples per path from it. */
+/* Optional per-PAIR record of the same, 8 bits: a device array of nq x H bytes that the scoring calls made after this one
+ * fill with the low eight WH_PATH_* bits (NULL switches it off again).  Written by the staged launches only
+ * (WH_SCORE_KERNEL=10 / 11; pairs of the other kernels keep whatever the array held; under 10 the envelopes run fused
+ * and the record carries the P2 and resolver bits alone).  The buffer belongs to the caller and must stay valid for as
+ * many pairs as the calls score.  tests/test_gpu_parity.py draws its headline-size oracle samples per path from it. */
 int wh_set_path_buffer(wh_ehmm *e, uint8_t *d_paths);
+/* The 16-bit record: a device array of nq x H uint16_t that every scoring kernel of a call fills, the default fused kernel
+ * included - one store per pair beside the pair's flags, so no pair keeps what the array held (NULL switches it off again;
+ * the kernels then take a wave-uniform branch around the record).  The low byte has the bits above, bits 8 and 9 are
+ * WH_PATH_BAND_KEPT / WH_PATH_BAND_FAIL.  An empty or unscored pair gets 0.
+ *  - score_kernel7 (the default for models of up to 24 cells per lane) derives the bits from what it counts anyway: a path
+ *    counter that moved while the pair was scored is a bit;
+ *  - the staged launches (WH_SCORE_KERNEL=10 / 11) record each sweep where it runs; the low byte is what wh_set_path_buffer
+ *    gets in the same call;
+ *  - the kernels without windows or bands (pass-synchronous, several waves per pair, the any-size float64 front end with
+ *    its long-list and long-query scoring passes): WH_PATH_P2_FULL | WH_PATH_P4_FULL for a pair with an envelope,
+ *    WH_PATH_DENSE with WH_FLAG_EXACT, WH_PATH_MULTI for a pair they queue for the resolver (the any-size front end queues
+ *    every pair with a region).  A pair that a later pass of the same call scores again carries that pass's record.
+ * Not written by the opt-in schedules WH_SCORE_KERNEL=9 and 12 (two queries per wave, four envelopes per sweep): their
+ * pairs keep what the array held.  Both buffers may be set; each is filled by its own rule. */
+int wh_set_path_buffer16(wh_ehmm *e, uint16_t *d_paths);
 
 /* Scoring passes the last wh_score call REPEATED (0 to 2: the loop in wh_score_dev allows two repeats, and a pass repeated
  * because a staged batch ran out of envelope units - WH_SCORE_KERNEL=10 / 11 - counts as well).  The queue that hands pairs with a multidomain region to the

@@ -71,6 +71,7 @@ SYMBOLS = {
     "wh_last_score_paths": (C.c_int, [_P, _P]),
     "wh_last_score_counters": (C.c_int, [_P, _P]),
     "wh_set_path_buffer": (C.c_int, [_P, _P]),
+    "wh_set_path_buffer16": (C.c_int, [_P, _P]),
     "wh_last_queue_reruns": (C.c_int, [_P]),
     "wh_last_region_overflow": (C.c_int, [_P, _P]),
     "wh_last_long_query_pairs": (C.c_int, [_P, _P]),

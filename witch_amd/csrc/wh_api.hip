@@ -305,13 +305,19 @@ int wh_last_score_counters(wh_ehmm *e, int64_t *out8) {
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(v, e->counter(kSlotScorePath), sizeof v, hipMemcpyDeviceToHost));
   for (int t = 0; t < 8; t++) out8[t] = (int64_t)v[t];
-  out8[7] = e->last_long_list;
+  out8[7] = e->last_long_list;      // (the device's slot 7 holds the ADDRESS of the 16-bit path record, kPathRecSlot: never reported)
   return WH_OK;
 }
 
 int wh_set_path_buffer(wh_ehmm *e, uint8_t *d_paths) {
   if (!e) { set_error("wh_set_path_buffer: null handle"); return WH_EINVAL; }
   e->path_buf = d_paths;
+  return WH_OK;
+}
+
+int wh_set_path_buffer16(wh_ehmm *e, uint16_t *d_paths) {
+  if (!e) { set_error("wh_set_path_buffer16: null handle"); return WH_EINVAL; }
+  e->path_buf16 = d_paths;
   return WH_OK;
 }
 

@@ -591,6 +591,8 @@ __global__ __launch_bounds__(64, 3) void WH_GENERIC_FRONT(GenericArgs a) {
       if (!queued) { a.decibits[out] = 0; a.flags[out] = (uint8_t)flags; }
       if (a.fwd_bits) a.fwd_bits[out] = fwd_bits_out;
     }
+    // the pair's 16-bit record (wh_set_path_buffer16): no window and no band here, and the resolver finishes every pair with a region
+    if (a.paths16 && lane == 0) a.paths16[out] = (uint16_t)(nenv_rec > 0 ? WH_PATH_P2_FULL | WH_PATH_P4_FULL | (queued ? WH_PATH_MULTI : 0) : 0);
     __builtin_amdgcn_wave_barrier();
   }
 }

@@ -100,7 +100,7 @@ enum CounterSlot {
   kAlignStatInts = 28,
   kSlotAlignCycles = 100,   //   [100..107] four 64-bit cycle counters (AlignArgs::wcyc)
   kSlotScorePath = 128,     // [128..143] eight 64-bit counters of the last scoring call: six paths (wh_last_score_paths),
-  kScorePathInts = 16,      //   bytes of Forward rows stored, spare (wh_last_score_counters)
+  kScorePathInts = 16,      //   bytes of Forward rows stored, and the ADDRESS of the 16-bit per-pair record (kPathRecSlot; 0: none)
   kSlotWideScore = 160,     // [160..175] work-queue heads of the wide scoring launches, one per (cells per lane, waves) class
   kWideScoreClasses = 16,   //   (13 exist: 12 x 5..8, 16 x 7..8, 24 x 6..8, 48 x 5..8; WH_FORCE_WIDE adds smaller workgroups of one of them)
   kSlotLongScore = 176,     // [176..177] long-query scoring pass: queries beyond the main length cap, the longest of them (long_queries_kernel)
@@ -159,6 +159,8 @@ struct wh_ehmm {
   int last_staged_batches = 0;              // batches the staged launches of the last scoring call went through
   std::vector<int> st_cnt_host;             // the batches' counters of the last call (read back once, at the end of the scoring pass)
   uint8_t *path_buf = nullptr;              // wh_set_path_buffer: device array [nq x H] the next scoring calls fill with WH_PATH_* bits
+  uint16_t *path_buf16 = nullptr;           // wh_set_path_buffer16: the 16-bit record (its address reaches the ScoreArgs kernels that write it
+                                            // through the spare slot of the path counters: kPathRecSlot, wh_launch.h)
   // staging for the host-pointer entry points
   DevBuf s_res, s_off, s_deci, s_flags, s_fwd, s_det, s_idx, s_w, s_nk, s_nu, s_pq, s_ph, s_co, s_cols, s_pos;
   DevBuf d_rkeys, d_rorder, d_rchunks, d_qorder, d_order, d_items, d_recs, d_spec, d_back, d_cwj, d_cwv, d_cwn, d_crow, c_buf[10];
@@ -333,6 +335,7 @@ static inline GenericArgs front_args(const ScoreCall &c, int Lcap, bool longq = 
   g.gtab = (const double *)c.e->d_gtab.p;
   g.counter = c.e->counter(kSlotGenericFront);
   g.Qmax = c.e->max_Q;
+  g.paths16 = c.e->path_buf16;
   g.slab_stride = (generic_front_doubles(Lcap, c.e->max_Q) + 1) & ~(size_t)1;
   if (longq) g.slab_stride += generic_seq_doubles(Lcap);
   return g;

@@ -278,7 +278,7 @@ static int launch_staged_class(const ScoreCall &c, const ScoreClassPlan &p, int 
   if (split) e->st_last_NB = NB;
   g.pairs = (StPair *)e->d_st_pairs.p; g.p1spec = (float *)e->d_st_p1spec.p;
   g.units = (StUnit *)e->d_st_units.p; g.p3spec = (float *)e->d_st_p3spec.p; g.slabs = (float *)e->d_st_slabs.p;
-  g.pair_paths = e->path_buf;
+  g.pair_paths = e->path_buf; g.pair_paths16 = e->path_buf16;
   int *cnt0 = (int *)e->d_st_cnt.p + 32 * (size_t)e->last_staged_batches;
   HIPCHK(hipMemsetAsync(cnt0, 0, sizeof(int) * 32 * (size_t)n_batches, s));
   const bool w512 = Q == 16 || Q == 24;
@@ -443,6 +443,7 @@ static int score_wide_classes(const ScoreCall &c, int *launches, bool *wide_done
     a.SP = row_stride(Lc);
     a.qorder = c.d_qorder;
     a.sparse = c.wide_dense ? 0 : 1;
+    a.paths16 = e->path_buf16;
     a.scratch_stride = wide_score_stride(Lc, wq, W, a.sparse != 0);
     const int64_t n_items = c.nq * (int64_t)a.n_list;
     const int per_cu = (W <= 4 && 2 * wlds <= kLdsBudget) ? 2 : 1;
@@ -539,6 +540,9 @@ static int score_dev_pass(ScoreCall &c, bool *overflow) {
     if ((int)e->by_q.size() > kMaxLaunches) { set_error("too many model size classes (%zu)", e->by_q.size()); return WH_ERANGE; }
     if (int rc = size_resolver_queue(c)) return rc;
     HIPCHK(hipMemsetAsync(e->counter(kSlotScorePath), 0, kScorePathInts * sizeof(int), s));
+    // the 16-bit per-pair record: its address goes where the ScoreArgs kernels look for it (wh_launch.h: path_record)
+    static_assert(2 * kPathRecSlot + 2 == kScorePathInts, "the record's address takes the last of the eight path counters");
+    if (e->path_buf16) HIPCHK(hipMemcpyAsync(e->counter(kSlotScorePath) + 2 * kPathRecSlot, &e->path_buf16, sizeof e->path_buf16, hipMemcpyHostToDevice, s));
     if (int rc = order_queries(c)) return rc;
     if (int rc = score_size_classes(c, &launches)) return rc;
     if (!e->wide_by_w.empty()) if (int rc = score_wide_classes(c, &launches, &wide_done)) return rc;

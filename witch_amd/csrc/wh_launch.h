@@ -65,9 +65,23 @@ struct ScoreArgs {
   unsigned long long *stats;   // WH_STATS: [4..11] wave cycles per phase (or NULL)
   unsigned long long *paths;   // 6 counters (always counted, one atomic per wave and counter at the end of the launch): envelope Backward
                                // sweeps on a 256-node window, on a 512-node window, windows that failed the certificate, full-width sweeps;
-                               // multihit Backward sweeps kept from a node window, windows whose region scan was in doubt (redone at full width)
+                               // multihit Backward sweeps kept from a node window, windows whose region scan was in doubt (redone at full width);
+                               // [6] bytes of Forward rows stored; [kPathRecSlot] the ADDRESS of the 16-bit per-pair record (path_record below)
   const int32_t *qorder;       // long-model kernel: queries in descending length order (or NULL: input order)
 };
+
+// The 16-bit per-pair record (wh_set_path_buffer16: [nq x H] WH_PATH_* bits, or none): a kernel that takes ScoreArgs finds its
+// address in the last of the eight path counters, which the host writes after zeroing them (score_dev_pass) - memory the
+// kernel addresses anyway.  As one more kernel argument the pointer would cost the main launch scratch, like the
+// resolver's feedback fields did (ResolveArgs::fb).  Wave-uniform: NULL = branch around the record.  (score_kernel7 reads it
+// where a pair's result is stored and the pass-synchronous kernel once per wave.)
+constexpr int kPathRecSlot = 7;
+__device__ __forceinline__ uint16_t *path_record(const ScoreArgs &a) {
+  if (!a.paths) return nullptr;
+  const unsigned long long v = a.paths[kPathRecSlot];
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return reinterpret_cast<uint16_t *>(((unsigned long long)hi << 32) | lo);
+}
 
 // ---- staged scoring launches (wh_staged.hip): the five sweeps of a pair as kernels of their own, each at the
 // occupancy it can use, over batches of pairs whose intermediate results live in HBM.
@@ -81,7 +95,7 @@ struct StPair {
                                      // 2 regions known, 3 the windowed region scan was in doubt (full-width P2 follows),
                                      // 4 the window of P2 needs 512 nodes
   int32_t nenv, nreg, flags;         // regions: flags = WH_FLAG_* | multidomain mask << 8
-  int32_t path;                      // WH_PATH_* bits of the pair (wh_set_path_buffer)
+  int32_t path;                      // WH_PATH_* bits of the pair (wh_set_path_buffer, wh_set_path_buffer16); kStWantedWindow: internal
   int32_t pad[3];
   int32_t regs[2 * WH_MAX_ENVELOPES];
   float envsc[WH_MAX_ENVELOPES], domcorr[WH_MAX_ENVELOPES];
@@ -108,7 +122,9 @@ struct StagedArgs {
   float *slabs; size_t slab_stride;  // per unit: Forward rows (floats per unit)
   int *cnt;                          // ST_NCOUNT counters of the batch (zeroed before its first launch)
   uint8_t *pair_paths;               // optional [nq x H]: WH_PATH_* bits per pair (or NULL)
+  uint16_t *pair_paths16;            // optional [nq x H]: the 16-bit record (or NULL); each buffer is written where it is set
 };
+constexpr int kStWantedWindow = 1 << 16;   // StPair::path: P2 wanted a window and none fitted (counted as the fused kernel counts it; never stored)
 // <threads> = 64 x waves; <lds> covers the header, the tables of the kind, the wave blocks and the candidate list
 hipError_t launch_staged_p1(int Q, const StagedArgs &a, int blocks, int threads, size_t lds, hipStream_t s);
 hipError_t launch_staged_p2win(int Q, int QB, const StagedArgs &a, int blocks, int threads, size_t lds, hipStream_t s);
@@ -232,6 +248,7 @@ struct WideArgs {
   int em_lds;                  // 12-cell kernels: the emission rows of the canonical residues are staged in LDS (behind the block)
   unsigned long long *stats;   // WH_STATS: [0..4] cycles of the first wave in P1, P2, region scan, P3, P4; [5] whole items (or NULL)
   int sparse;                  // envelope Forward rows: only the lanes above 2^-24 of the row's E are stored (+ masks behind the slab)
+  uint16_t *paths16;           // optional [nq x H]: the 16-bit per-pair record (wh_set_path_buffer16), or NULL
 };
 struct WideAlignArgs {
   const DevHMM *hmms;
@@ -285,6 +302,7 @@ struct GenericArgs {
   int32_t *rext;
   int64_t rext_stride;
   int ext_cap;
+  uint16_t *paths16;           // optional [nq x H]: the 16-bit per-pair record (wh_set_path_buffer16), or NULL
 };
 // pairs flagged WH_FLAG_TRUNC, appended to <list> (up to <cap>; <count> keeps counting)
 hipError_t launch_trunc_list(const uint8_t *flags, int64_t npairs, int *count, int64_t *list, int cap, hipStream_t s);

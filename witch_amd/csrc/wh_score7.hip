@@ -971,6 +971,21 @@ __device__ __noinline__ RegOut region_scan(lds_f *spec3, glb_f *specg, int SP, i
 }
 
 struct EnvCounters { unsigned n_w256, n_w512, n_wfail, n_full; unsigned long long spill; };   // ... and bytes of Forward rows the envelope sweeps stored
+// The 16-bit per-pair record (wh_set_path_buffer16) is derived from state the kernel keeps anyway - a mask carried through the
+// sweeps grew the scratch frame.  Where a record is set, lane 0 copies the wave's path counters to spare words
+// of the wave's LDS block when a pair begins (path_snapshot) and compares when its result is stored (path_bits): a counter that
+// moved is a bit.  The outcome of the banded store has no counter: envelope_attempts counts it in the top 16 bits of the byte
+// counter EnvCounters::spill, inside the add that is there already (band_event); take_band_events hands them over and clears them.
+constexpr int kBandEvShift = 48;
+__device__ __forceinline__ unsigned take_band_events(EnvCounters &ec) {
+  const unsigned ev = (unsigned)(ec.spill >> kBandEvShift);
+  ec.spill &= (1ull << kBandEvShift) - 1;
+  return ev;
+}
+__device__ __forceinline__ int band_path_bits(unsigned ev) {      // ev: banded attempts that had Forward mass | bands that failed << 8
+  const unsigned n0 = ev & 0xFF, nfail = ev >> 8;
+  return (nfail ? WH_PATH_BAND_FAIL : 0) | (n0 > nfail ? WH_PATH_BAND_KEPT : 0);
+}
 // An envelope's Backward sweep + null2 once its Forward rows are in c.Fs and its per-row arrays in the wave's block: on a
 // node window where one fits around the dominant alignment and passes the mass certificate, else at full width.
 // <dense>: the Forward sweep stored every row (the redo after a failed spill certificate): full width, no tolerance.
@@ -1108,7 +1123,8 @@ __device__ __forceinline__ float envelope_attempts(const ScoreArgs &a, WaveCtx &
   for (int attempt = first; attempt < 3; attempt++) {
     const float keep_scale = attempt < 2 ? (a.keep_scale > 0.f ? a.keep_scale : kKeepScale7) : -1.0f;
     const FwdOut f3 = uniform_fwd(sweep_forward<Q, true, TH, SG>(c, (lds_u8 *)eseq, Ld, cu, keep_scale, attempt == 0 ? band : kAllLanes));
-    ec.spill += (unsigned long long)f3.nst * (8 * Q);
+    // (+ the band's outcome, for the pair's record: a banded attempt with Forward mass; attempt 1 after a band = the band failed)
+    ec.spill += (unsigned long long)f3.nst * (8 * Q) + (attempt == 0 ? (f3.xC > 0.f ? 1ull << kBandEvShift : 0ull) : attempt == 1 && band != kAllLanes ? 1ull << (kBandEvShift + 8) : 0ull);
     // the rows were written by other lanes of this wave: order the stores before the loads
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     envsc = uniform_f((float)((double)f3.ef * LOG2 + dlog((double)(f3.xC * cu.move))));
@@ -1244,6 +1260,24 @@ __device__ __forceinline__ RegOut score_regions(const ScoreArgs &a, const WaveCt
   return ro;
 }
 
+__device__ __forceinline__ int *path_words(int *regs) { return regs + 2 * WH_MAX_ENVELOPES; }      // (spare: between the region list and the envelope results)
+__device__ __forceinline__ void path_snapshot(int *regs, const EnvCounters &ec, const FrontState &fs) {
+  int *pw = path_words(regs);
+  pw[0] = (int)ec.n_w256; pw[1] = (int)ec.n_w512; pw[2] = (int)ec.n_wfail; pw[3] = (int)ec.n_full; pw[4] = (int)fs.n_p2w;
+}
+// <p2_ran>: the pair reached its multihit Backward sweep; <queued>: it was handed to the resolver
+__device__ __forceinline__ int path_bits(const int *regs, const EnvCounters &ec, const FrontState &fs, bool p2_ran, int flags, bool queued, unsigned band_ev) {
+  const int *pw = regs + 2 * WH_MAX_ENVELOPES;
+  int path = p2_ran ? ((int)fs.n_p2w != pw[4] ? WH_PATH_P2_WIN : WH_PATH_P2_FULL) : 0;
+  if ((int)ec.n_w256 != pw[0]) path |= WH_PATH_P4_W256;
+  if ((int)ec.n_w512 != pw[1]) path |= WH_PATH_P4_W512;
+  if ((int)ec.n_wfail != pw[2]) path |= WH_PATH_P4_WFAIL;
+  if ((int)ec.n_full != pw[3]) path |= WH_PATH_P4_FULL;
+  if (flags & WH_FLAG_EXACT) path |= WH_PATH_DENSE;
+  if (queued) path |= WH_PATH_MULTI;
+  return path | band_path_bits(band_ev);
+}
+
 #ifndef WH_SWEEPS_ONLY
 
 template <int Q, int TH, bool SG>
@@ -1314,6 +1348,7 @@ __global__ __launch_bounds__(TH) void score_kernel7(ScoreArgs a) {
       const size_t out = (size_t)qi * a.H + h;
       int flags = 0, decibits = 0;
       float fwd_bits_out = -INFINITY;
+      if (lane == 0) path_snapshot(regs, ec, fs);
       wh_pair_detail *dp = (a.detail && lane == 0) ? a.detail + out : nullptr;
       if (dp) {
         dp->fwd_bits = -INFINITY; dp->seq_score = 0.f; dp->pre_score = 0.f; dp->seqbias_nats = 0.f;
@@ -1356,6 +1391,12 @@ __global__ __launch_bounds__(TH) void score_kernel7(ScoreArgs a) {
         a.decibits[out] = decibits;
         a.flags[out] = (uint8_t)flags;
         if (a.fwd_bits) a.fwd_bits[out] = fwd_bits_out;
+      }
+      // the pair's 16-bit record, where one is set (wave-uniform branch).  The Forward log-odds are finite exactly when the
+      // pair went on to P2; a pair with a multidomain region is queued wherever there is a queue.
+      const unsigned band_ev = take_band_events(ec);
+      if (uint16_t *rec = path_record(a)) {
+        if (lane == 0) rec[out] = (uint16_t)path_bits(regs, ec, fs, isfinite(fwd_bits_out), flags, (flags & WH_FLAG_MULTI) && a.rrecs != nullptr, band_ev);
       }
     }
   }
@@ -1634,6 +1675,7 @@ __global__ __launch_bounds__(TH) void score_kernel7q(ScoreArgs a) {
       }
     }
   }
+  (void)take_band_events(ec);       // (this kernel writes no per-pair record: the byte counter gets its top bits back)
   if (a.paths && lane == 0) {
     if (ec.n_w256) atomicAdd(a.paths + 0, (unsigned long long)ec.n_w256);
     if (ec.n_w512) atomicAdd(a.paths + 1, (unsigned long long)ec.n_w512);

@@ -336,6 +336,7 @@ __global__ __launch_bounds__(TH) void score_big_kernel(ScoreArgs a) {
       cur_orient = o;
     }
   };
+  uint16_t *const rec = path_record(a);     // the 16-bit per-pair record, or NULL (wave-uniform)
 
   for (;;) {
     if (threadIdx.x == 0) *s_item_p = atomicAdd(a.counter, 1);
@@ -675,6 +676,9 @@ __global__ __launch_bounds__(TH) void score_big_kernel(ScoreArgs a) {
         a.flags[out] = (uint8_t)flags;
         if (a.fwd_bits) a.fwd_bits[out] = fwd_bits_out;
       }
+      // the pair's 16-bit record (wh_set_path_buffer16): no window and no band in this kernel
+      if (rec && in_range && lane == 0)
+        rec[out] = (uint16_t)(nenv > 0 ? WH_PATH_P2_FULL | WH_PATH_P4_FULL | (flags & WH_FLAG_EXACT ? WH_PATH_DENSE : 0) | (queue_pair ? WH_PATH_MULTI : 0) : 0);
     }
   }
 }

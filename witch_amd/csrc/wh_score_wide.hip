@@ -732,6 +732,7 @@ __global__ __launch_bounds__(512) void score_wide_kernel(WideArgs a) {
     const int L = (int)(a.offsets[qi + 1] - off);
     const size_t out = (size_t)qi * a.H + h;
     int flags = 0, decibits = 0;
+    int path = 0;                          // the pair's 16-bit record (wh_set_path_buffer16): no window and no band in this kernel
     float fwd_bits_out = -INFINITY;
     wh_pair_detail *dp = (a.detail && threadIdx.x == 0) ? a.detail + out : nullptr;
     if (dp) { dp->fwd_bits = -INFINITY; dp->seq_score = 0.f; dp->pre_score = 0.f; dp->seqbias_nats = 0.f; dp->nregions = 0; dp->nenv = 0; }
@@ -802,6 +803,7 @@ __global__ __launch_bounds__(512) void score_wide_kernel(WideArgs a) {
           float seqbias_sum = 0.f, sum_score = 0.f, sb2 = 0.f;
           int Ld_tot = 0;
           const bool queue_pair = multi_mask != 0 && a.rrecs != nullptr;
+          path = WH_PATH_P2_FULL | WH_PATH_P4_FULL | (queue_pair ? WH_PATH_MULTI : 0);
           float *envres = reinterpret_cast<float *>(regs + 3 * WH_MAX_ENVELOPES);
           for (int e = 0; e < nenv; e++) {
             if (queue_pair && ((multi_mask >> e) & 1)) { if (threadIdx.x == 0) { envres[e] = 0.f; envres[WH_MAX_ENVELOPES + e] = 0.f; } continue; }
@@ -863,6 +865,7 @@ __global__ __launch_bounds__(512) void score_wide_kernel(WideArgs a) {
       a.decibits[out] = decibits;
       a.flags[out] = (uint8_t)flags;
       if (a.fwd_bits) a.fwd_bits[out] = fwd_bits_out;
+      if (a.paths16) a.paths16[out] = (uint16_t)(path | (flags & WH_FLAG_EXACT ? WH_PATH_DENSE : 0));
     }
     __syncthreads();
   }

@@ -264,7 +264,7 @@ __global__ __launch_bounds__(kStTH) void staged_p1_kernel(StagedArgs g) {
       }
       if (lane == 0) {
         pp->state = state; pp->path = 0; pp->nenv = 0; pp->nreg = 0; pp->flags = 0;
-        if (state == 0) { a.decibits[out] = 0; a.flags[out] = 0; if (g.pair_paths) g.pair_paths[out] = 0; }
+        if (state == 0) { a.decibits[out] = 0; a.flags[out] = 0; if (g.pair_paths) g.pair_paths[out] = 0; if (g.pair_paths16) g.pair_paths16[out] = 0; }
         if (a.fwd_bits) a.fwd_bits[out] = fwd_bits_out;
       }
     });
@@ -432,13 +432,15 @@ __global__ __launch_bounds__(kStTH) void staged_p4full_kernel(StagedArgs g) {
       const float xC = u->xC; const int ef = u->ef;
       ST_T0();
       const P1Mask um1 = {((unsigned long long)(unsigned)bcast_i((int)pp->um_hi) << 32) | (unsigned)bcast_i((int)pp->um_lo), (unsigned)bcast_i((int)pp->um_steady)};
-      const float tol = spill_tol(spill_band<Q>(a, um1) != kAllLanes);
+      const bool banded = spill_band<Q>(a, um1) != kAllLanes;
+      const float tol = spill_tol(banded);
       const P4Out p4 = sweep_backward_null2<Q, kStTH, false>(c, (lds_u8 *)seq, Ld, cu, 1.0f / (xC * cu.move), ef, tol);
       ST_T1(7);
       n_full++;
       const bool ok = fabsf((float)Ld - p4.mass) <= tol * (float)Ld;
       if (lane == 0) {
-        atomicOr(&pp->path, WH_PATH_P4_FULL);
+        // (the rows are P3's first attempt: kept -> the band held; lost -> the dense kernel stores them again, envelope_attempts from 1)
+        atomicOr(&pp->path, WH_PATH_P4_FULL | (banded ? (ok ? WH_PATH_BAND_KEPT : WH_PATH_BAND_FAIL) : 0));
         if (ok) { pp->domcorr[e] = p4.domcorr; pp->cls[e] = ST_CLS_NONE; }
         else pp->cls[e] = ST_CLS_DENSE;
       }
@@ -491,6 +493,7 @@ __global__ __launch_bounds__(kStTH) void staged_dense_kernel(StagedArgs g) {
       long long t_last = 0;
       float envsc;
       const float domcorr = envelope_attempts<Q, kStTH, false>(a, c, seq, Ld, cu, band, band != kAllLanes ? 1 : 2, ec, lane, flags, t_last, envsc);
+      (void)take_band_events(ec);       // (the band's failure was recorded by the P4 kernel that saw it)
       if (lane == 0) {
         pp->envsc[e] = envsc; pp->domcorr[e] = domcorr; pp->cls[e] = ST_CLS_NONE;
         if (flags & WH_FLAG_EXACT) { atomicOr(&pp->flags, WH_FLAG_EXACT); atomicOr(&pp->path, WH_PATH_DENSE); }
@@ -562,12 +565,14 @@ __global__ __launch_bounds__(kStTH) void staged_env_kernel(StagedArgs g) {
         score_envelopes<Q, kStTH, false>(a, c, seq, regs, L, lane, h, qi, nenv, nreg, multi_mask, fwdsc, nullsc, fwd_bits_out, dp, flags, decibits, ec, t_last, um1);
         ST_T1(4);
         if (multi_mask != 0 && a.rrecs != nullptr) path |= WH_PATH_MULTI;
+        path |= band_path_bits(take_band_events(ec)) | (flags & WH_FLAG_EXACT ? WH_PATH_DENSE : 0);
       }
       if (lane == 0) {
-        if ((path & 256) && a.paths) atomicAdd(a.paths + 5, 1ull);      // wanted a window for P2, none fitted (counted as the fused kernel counts it)
+        if ((path & kStWantedWindow) && a.paths) atomicAdd(a.paths + 5, 1ull);      // wanted a window for P2, none fitted (counted as the fused kernel counts it)
         a.decibits[out] = decibits;
         a.flags[out] = (uint8_t)flags;
         if (g.pair_paths) g.pair_paths[out] = (uint8_t)path;
+        if (g.pair_paths16) g.pair_paths16[out] = (uint16_t)path;
       }
     });
   if (a.paths && lane == 0) {
@@ -623,7 +628,7 @@ __global__ __launch_bounds__(kLightTH) __attribute__((amdgpu_waves_per_eu(QB == 
         int m0 = 0;
         const int w = (Q >= 8 && !a.no_window) ? place_window<Q>(um, m0) : 0;
         if (w == 8) { pp->state = 4; return; }
-        if (w == 0) { pp->state = 3; if (um != 0) pp->path |= 256; return; }     // (bit 8: a window was wanted - counted below)
+        if (w == 0) { pp->state = 3; if (um != 0) pp->path |= kStWantedWindow; return; }     // (a window was wanted - counted below)
       }
       emit(pl);
     },
@@ -703,13 +708,15 @@ __global__ __launch_bounds__(kLightTH) __attribute__((amdgpu_waves_per_eu(QB == 
       c.Fs = (glb_f *)(g.slabs + (size_t)uid * g.slab_stride);
       const LenCfg cu = len_config(L, false);
       const float xC = u->xC;
+      const P1Mask um1 = {((unsigned long long)(unsigned)bcast_i((int)pp->um_hi) << 32) | (unsigned)bcast_i((int)pp->um_lo), (unsigned)bcast_i((int)pp->um_steady)};
+      const int kept = spill_band<Q>(a, um1) != kAllLanes ? WH_PATH_BAND_KEPT : 0;      // (the rows are P3's banded attempt: a window that holds accepts it)
       ST_T0();
       const P4Out p4 = sweep_backward_null2_win<QB, Q, kLightTH, false, true>(c, (lds_u8 *)seq, Ld, cu, 1.0f / (xC * cu.move), kWinTol7, m0);
       ST_T1((QB == 4 ? 5 : 6));
       const bool ok = fabsf((float)Ld - p4.mass) <= kWinTol7 * (float)Ld;
       if (ok) n_ok++; else n_fail++;
       if (lane == 0) {
-        if (ok) { pp->domcorr[e] = p4.domcorr; pp->cls[e] = ST_CLS_NONE; atomicOr(&pp->path, QB == 4 ? WH_PATH_P4_W256 : WH_PATH_P4_W512); }
+        if (ok) { pp->domcorr[e] = p4.domcorr; pp->cls[e] = ST_CLS_NONE; atomicOr(&pp->path, (QB == 4 ? WH_PATH_P4_W256 : WH_PATH_P4_W512) | kept); }
         else { pp->cls[e] = ST_CLS_FULL; atomicOr(&pp->path, WH_PATH_P4_WFAIL); }
       }
     });
@@ -743,8 +750,8 @@ __global__ __launch_bounds__(256) void staged_assemble_kernel(StagedArgs g) {
   const int nenv = pp->nenv, nreg = pp->nreg, multi_mask = (pp->flags >> 8) & 0xFFFF;
   wh_pair_detail *dp = a.detail ? a.detail + out : nullptr;
   int path = pp->path;
-  if ((path & 256) && a.paths) atomicAdd(a.paths + 5, 1ull);     // wanted a window for P2, none fitted (the fused kernel counts these as rejected)
-  path &= 255;
+  if ((path & kStWantedWindow) && a.paths) atomicAdd(a.paths + 5, 1ull);     // wanted a window for P2, none fitted (the fused kernel counts these as rejected)
+  path &= kStWantedWindow - 1;
   if (nenv > 0) {
     const bool queue_pair = multi_mask != 0 && a.rrecs != nullptr;
     float seqbias_sum = 0.f, sum_score = 0.f, sb2 = 0.f;
@@ -789,6 +796,7 @@ __global__ __launch_bounds__(256) void staged_assemble_kernel(StagedArgs g) {
   a.decibits[out] = decibits;
   a.flags[out] = (uint8_t)flags;
   if (g.pair_paths) g.pair_paths[out] = (uint8_t)path;
+  if (g.pair_paths16) g.pair_paths16[out] = (uint16_t)path;
 }
 
 template <class K>

@@ -174,6 +174,17 @@ class EHMM:
         check(lib().wh_set_path_buffer(self._h, paths_t.data_ptr() if paths_t is not None else None), "wh_set_path_buffer")
         self._path_t = paths_t
 
+    def set_path_buffer16(self, paths_t):
+        """Registers a contiguous CUDA int16 / uint16 tensor of nq x H elements that later score calls fill with the 16-bit
+        WH_PATH_* record per pair (None switches it off): the default kernel writes it, as do the staged launches and the
+        kernels without windows.  The caller keeps the tensor alive (include/witch_hip.h: wh_set_path_buffer16)."""
+        if paths_t is not None:
+            import torch
+            if paths_t.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or not paths_t.is_cuda or not paths_t.is_contiguous():
+                raise ValueError("set_path_buffer16: a contiguous CUDA tensor of torch.int16 or torch.uint16")
+        check(lib().wh_set_path_buffer16(self._h, paths_t.data_ptr() if paths_t is not None else None), "wh_set_path_buffer16")
+        self._path16_t = paths_t
+
     def last_queue_reruns(self) -> int:
         """Scoring passes the last score call repeated because the resolver's queue overflowed its estimate (0 or 1)."""
         n = lib().wh_last_queue_reruns(self._h)
