@@ -330,11 +330,29 @@ int  wh_hmmbuild(const char *molecule, int32_t nseq, int64_t alen, const char *c
  * and Forward locations come out in hmmbuild's printed digits on all 47 golden model files; the reference's bundled
  * hmmsearch then prints the same report, E-values included, as for hmmbuild's own file).  WITCH never reads them
  * (hmmsearch -E 99999999, only bit scores are parsed); stock HMMER refuses a file without them.  Costs about 0.5 s
- * per 1 000-node model on one core, against 15 ms for the build itself. */
+ * per 1 000-node model on one core, against 15 ms for the build itself: wh_hmmbuild_batch calibrates a whole eHMM
+ * on the device instead. */
 #define WH_BUILD_STATS 1
 int  wh_hmmbuild2(const char *molecule, int32_t nseq, int64_t alen, const char *const *rows, const char *name,
                   double ere, double symfrac, double fragthresh, int32_t flags, char **out_text, int64_t *out_len,
                   int32_t *out_M, double *out_neff);
+/* All models of an eHMM in one call: model i from nseq[i] rows of alen[i] characters (rows[i]), named names[i] (names or
+ * names[i] NULL: "sub"), built on the host exactly as wh_hmmbuild2 builds it; out_text[i] is byte for byte what
+ * wh_hmmbuild2 returns for it (release each with wh_free_text).  With WH_BUILD_STATS all n models are calibrated in one
+ * batch: device >= 0 on that HIP device (wh_calibrate.hip: one lane per (model, random sequence), the host's sweeps
+ * compiled for the device, the integer filters and the float64 Forward recurrence bit for bit the host's), device < 0
+ * on the host, without any HIP call.  The device's row workspace is 200 x 62 x (M + 1) + 160 000 bytes per model (+ its tables, 124 (M + 1) bytes for DNA);
+ * the models run in groups that fit a budget of 1 GiB (environment, read per call: WH_CALIB_WS_MB=<n> MiB) and half of
+ * the device's free memory; a model that does not fit alone is refused with WH_ENOMEM before anything is launched
+ * (wh_last_error: the figures).  out_M, out_neff (optional): [n]; out_stats (optional): [n][4] lambda, MSV mu, Viterbi mu,
+ * Forward tau as doubles (the text holds them as float32; zeros without WH_BUILD_STATS).  On failure every out_text[i] is
+ * NULL, nothing is left allocated and wh_last_error names the model.  n == 0: WH_OK. */
+#define WH_BUILD_CALIB_NO_LDS 4   /* test hook: calibration tables from global memory whatever their size */
+int  wh_hmmbuild_batch(int device, const char *molecule, int32_t n,
+                       const int32_t *nseq, const int64_t *alen, const char *const *const *rows,
+                       const char *const *names, double ere, double symfrac, double fragthresh, int32_t flags,
+                       char **out_text, int64_t *out_len, int32_t *out_M, double *out_neff,
+                       double *out_stats /* optional, [n][4]: lambda, MSV mu, Viterbi mu, Forward tau */);
 void wh_free_text(char *text);
 
 #ifdef __cplusplus

@@ -17,6 +17,7 @@ WH_MAX_ENVELOPES = 16
 FLAG_REPORTED, FLAG_MULTI, FLAG_OVERRIDE, FLAG_TRUNC, FLAG_EXACT = 1, 2, 4, 8, 16
 ALPH_DNA, ALPH_RNA, ALPH_AMINO = 0, 1, 2
 WH_OK, WH_EINVAL, WH_EIO, WH_ENODEV, WH_EHIP, WH_ERANGE, WH_ENOMEM = 0, -1, -2, -3, -4, -5, -6      # include/witch_hip.h
+WH_BUILD_STATS, WH_BUILD_CALIB_NO_LDS = 1, 4
 PATH_P2_WIN, PATH_P2_FULL, PATH_P4_W256, PATH_P4_W512, PATH_P4_WFAIL, PATH_P4_FULL, PATH_DENSE, PATH_MULTI = 1, 2, 4, 8, 16, 32, 64, 128
 
 
@@ -46,6 +47,9 @@ SYMBOLS = {
                             C.c_double, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "wh_hmmbuild2": (C.c_int, [C.c_char_p, C.c_int32, C.c_int64, C.POINTER(C.c_char_p), C.c_char_p, C.c_double, C.c_double,
                              C.c_double, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "wh_hmmbuild_batch": (C.c_int, [C.c_int, C.c_char_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.POINTER(C.c_char_p)),
+                                  C.POINTER(C.c_char_p), C.c_double, C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_void_p),
+                                  C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "wh_free_text": (None, [C.c_void_p]),
     "wh_merge_sharded": (C.c_int, [C.c_int, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_void_p),
                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

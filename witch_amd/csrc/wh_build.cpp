@@ -20,8 +20,11 @@
 //   6. parameters = posterior mean under HMMER's default mixture Dirichlet priors (constants below: nucleic
 //      and amino; they are data of the published defaults);
 //   7. composition (occupancy-weighted), consensus letters, MAP, and the text file.
-// NOT written: the STATS lines (E-value calibration by simulation) and MAXL - this path's consumer
-// (wh_ehmm_load) reads probabilities only; HMMER's own hmmsearch refuses a file without STATS.
+// The STATS lines (E-value calibration by simulation, wh_calibrate.h) are written on request (WH_BUILD_STATS): this
+// path's consumer (wh_ehmm_load) reads probabilities only; HMMER's own hmmsearch refuses a file without them.
+// Three steps: build_model (alignment -> model in memory), the calibration of that float model where asked for (on the
+// host, or for a whole batch on the device: wh_calibrate.hip), print_model (-> text).  hmmbuild calibrates the model
+// in memory, not the rounded text, so the calibration sits between the two.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -34,14 +37,19 @@
 #include <vector>
 
 #include "../../include/witch_hip.h"
+#include "wh_calibrate.h"
 
 namespace wh {
 void set_error(const char *fmt, ...);
+#ifndef WH_HOST_ONLY
+// wh_calibrate.hip: the sweeps of n prepared models on a HIP device; msv / vit / fwd: [n][kCalibN] as calib_finish takes them
+int calibrate_device(int device, int n, const whc::CalibPrep *preps, const whc::CalibSeqs &seqs, int flags, int *msv, int *vit, double *fwd);
+#endif
 }
 
 namespace {
 
-enum { tMM = 0, tMI, tMD, tIM, tII, tDM, tDD };
+using namespace whc;
 
 struct Alphabet {
   int K = 0, Kp = 0;
@@ -261,8 +269,6 @@ double mean_match_relent(const Model &h, const float *bg) {
   return KL / (double)h.M;
 }
 
-#include "wh_calibrate.h"
-
 // hmmbuild's MAXL line (p7_Builder_MaxLength at its default tail mass 1e-7): the length beyond which the core model,
 // entered at match state 1 and left at its end, emits a sequence with probability below 1e-7.  Restated from the
 // numbers: one unit of mass in M_1 at length 1; per step the delete states are closed over the current match masses,
@@ -323,29 +329,32 @@ void put_prob(std::string &s, float p) {
   else append(s, " %8.5f", (double)-(float)std::log((double)p));   // a correctly rounded logf (the binary's libm; glibc's differs in rare last bits)
 }
 
-}  // namespace
-
-extern "C" int wh_hmmbuild(const char *molecule, int32_t nseq, int64_t alen, const char *const *rows, const char *name,
-                           double ere, double symfrac, double fragthresh, char **out_text, int64_t *out_len,
-                           int32_t *out_M, double *out_neff) {
-  return wh_hmmbuild2(molecule, nseq, alen, rows, name, ere, symfrac, fragthresh, 0, out_text, out_len, out_M, out_neff);
-}
-
-extern "C" int wh_hmmbuild2(const char *molecule, int32_t nseq, int64_t alen, const char *const *rows, const char *name,
-                            double ere, double symfrac, double fragthresh, int32_t flags, char **out_text, int64_t *out_len,
-                            int32_t *out_M, double *out_neff) {
-  if (!molecule || !rows || !out_text || !out_len || nseq < 1 || alen < 1) { wh::set_error("wh_hmmbuild: bad argument"); return WH_EINVAL; }
+// a model in memory, with what the text needs beside its probabilities
+struct Built {
   Alphabet abc;
-  if (!make_alphabet(molecule, abc)) { wh::set_error("wh_hmmbuild: unknown molecule '%s' (dna, rna, amino)", molecule); return WH_EINVAL; }
+  Model h;
+  int nseq = 0;
+  double neff = 0.0;
+  uint32_t cksum = 0;
+  std::vector<int32_t> matcol;      // 1-based alignment column of node k (index k-1)
+  std::vector<float> compo;
+};
+
+// who: the caller's name for the messages ("wh_hmmbuild", "wh_hmmbuild_batch: model 3")
+int build_model(const char *who, const char *molecule, int32_t nseq, int64_t alen, const char *const *rows, double ere, double symfrac,
+                double fragthresh, Built &b) {
+  if (!molecule || !rows || nseq < 1 || alen < 1) { wh::set_error("%s: bad argument", who); return WH_EINVAL; }
+  Alphabet &abc = b.abc;
+  if (!make_alphabet(molecule, abc)) { wh::set_error("%s: unknown molecule '%s' (dna, rna, amino)", who, molecule); return WH_EINVAL; }
   const int K = abc.K;
   // ---- digitize
   std::vector<uint8_t> ax((size_t)nseq * alen);
   for (int i = 0; i < nseq; i++) {
-    if (!rows[i]) { wh::set_error("wh_hmmbuild: row %d is NULL", i); return WH_EINVAL; }
+    if (!rows[i]) { wh::set_error("%s: row %d is NULL", who, i); return WH_EINVAL; }
     for (int64_t p = 0; p < alen; p++) {
       const unsigned char ch = (unsigned char)rows[i][p];
       const uint8_t x = abc.code[ch];
-      if (ch == 0 || x == 255) { wh::set_error("wh_hmmbuild: row %d, column %lld: character 0x%02x is not in the %s alphabet (or the row is short)", i, (long long)p + 1, ch, abc.name); return WH_EINVAL; }
+      if (ch == 0 || x == 255) { wh::set_error("%s: row %d, column %lld: character 0x%02x is not in the %s alphabet (or the row is short)", who, i, (long long)p + 1, ch, abc.name); return WH_EINVAL; }
       ax[(size_t)i * alen + p] = x;
     }
   }
@@ -401,7 +410,7 @@ extern "C" int wh_hmmbuild2(const char *molecule, int32_t nseq, int64_t alen, co
     if (r > 0.0 && r / tot >= symfrac) { match[p] = 1; matcol.push_back((int32_t)(p + 1)); }
   }
   const int M = (int)matcol.size();
-  if (M < 1) { wh::set_error("wh_hmmbuild: the alignment has no consensus column"); return WH_EINVAL; }
+  if (M < 1) { wh::set_error("%s: the alignment has no consensus column", who); return WH_EINVAL; }
   // ---- 4. counts
   Model cnt;
   cnt.M = M; cnt.K = K;
@@ -482,6 +491,20 @@ extern "C" int wh_hmmbuild2(const char *molecule, int32_t nseq, int64_t alen, co
     for (int pass = 0; pass < 2; pass++)
       for (int x = 0; x < K; x++) compo[x] += (pass == 0 ? h.mat[(size_t)k * K + x] * mocc[k] : h.ins[(size_t)k * K + x] * iocc[k]);
   fnorm(compo.data(), K);
+  b.nseq = nseq; b.neff = neff; b.cksum = cksum;
+  b.h = std::move(h);
+  b.matcol = std::move(matcol);
+  b.compo = std::move(compo);
+  return WH_OK;
+}
+
+// ev: lambda, MSV mu, Viterbi mu, Forward tau (calibrate_model), or NULL for a file without STATS lines
+std::string print_model(const Built &b, const char *name, const double *ev) {
+  const Alphabet &abc = b.abc;
+  const Model &h = b.h;
+  const int M = h.M, K = h.K;
+  const std::vector<float> &compo = b.compo;
+  const std::vector<int32_t> &matcol = b.matcol;
   // ---- text
   std::string s;
   s.reserve((size_t)M * (size_t)(3 * (K + 8) * 9) + 1024);
@@ -491,15 +514,11 @@ extern "C" int wh_hmmbuild2(const char *molecule, int32_t nseq, int64_t alen, co
   if (K == 4) append(s, "MAXL  %d\n", max_length(h));      // nucleotide models only, as hmmbuild
   append(s, "ALPH  %s\n", abc.name);
   s += "RF    no\nMM    no\nCONS  yes\nCS    no\nMAP   yes\n";
-  append(s, "NSEQ  %d\n", nseq);
-  append(s, "EFFN  %f\n", neff);
-  append(s, "CKSUM %u\n", cksum);
-  if (flags & WH_BUILD_STATS) {
+  append(s, "NSEQ  %d\n", b.nseq);
+  append(s, "EFFN  %f\n", b.neff);
+  append(s, "CKSUM %u\n", b.cksum);
+  if (ev) {
     // E-value calibration (wh_calibrate.h): what stock HMMER needs to accept the file; this path never reads it
-    CalibModel cm;
-    cm.M = M; cm.K = K; cm.t = h.t.data(); cm.mat = h.mat.data(); cm.bg = abc.bg;
-    double ev[4];
-    calibrate_model(cm, mean_match_relent(h, abc.bg), ev);
     // (the model keeps them as float32, and that is what hmmbuild prints)
     append(s, "STATS LOCAL MSV      %8.4f %8.5f\n", (double)(float)ev[1], (double)(float)ev[0]);
     append(s, "STATS LOCAL VITERBI  %8.4f %8.5f\n", (double)(float)ev[2], (double)(float)ev[0]);
@@ -530,14 +549,118 @@ extern "C" int wh_hmmbuild2(const char *molecule, int32_t nseq, int64_t alen, co
     s += "\n";
   }
   s += "//\n";
+  return s;
+}
+
+void calib_model_of(const Built &b, CalibModel &cm) {
+  cm.M = b.h.M; cm.K = b.h.K; cm.t = b.h.t.data(); cm.mat = b.h.mat.data(); cm.bg = b.abc.bg;
+}
+
+int text_out(const char *who, const std::string &s, char **out_text, int64_t *out_len) {
   char *buf = (char *)malloc(s.size() + 1);
-  if (!buf) { wh::set_error("wh_hmmbuild: out of memory"); return WH_ENOMEM; }
+  if (!buf) { wh::set_error("%s: out of memory", who); return WH_ENOMEM; }
   memcpy(buf, s.data(), s.size());
   buf[s.size()] = 0;
   *out_text = buf;
   *out_len = (int64_t)s.size();
-  if (out_M) *out_M = M;
-  if (out_neff) *out_neff = neff;
+  return WH_OK;
+}
+
+}  // namespace
+
+extern "C" int wh_hmmbuild(const char *molecule, int32_t nseq, int64_t alen, const char *const *rows, const char *name,
+                           double ere, double symfrac, double fragthresh, char **out_text, int64_t *out_len,
+                           int32_t *out_M, double *out_neff) {
+  return wh_hmmbuild2(molecule, nseq, alen, rows, name, ere, symfrac, fragthresh, 0, out_text, out_len, out_M, out_neff);
+}
+
+extern "C" int wh_hmmbuild2(const char *molecule, int32_t nseq, int64_t alen, const char *const *rows, const char *name,
+                            double ere, double symfrac, double fragthresh, int32_t flags, char **out_text, int64_t *out_len,
+                            int32_t *out_M, double *out_neff) {
+  if (!out_text || !out_len) { wh::set_error("wh_hmmbuild: bad argument"); return WH_EINVAL; }
+  Built b;
+  const int rc = build_model("wh_hmmbuild", molecule, nseq, alen, rows, ere, symfrac, fragthresh, b);
+  if (rc) return rc;
+  double ev[4];
+  if (flags & WH_BUILD_STATS) {
+    CalibModel cm;
+    calib_model_of(b, cm);
+    calibrate_model(cm, mean_match_relent(b.h, b.abc.bg), ev);
+  }
+  const std::string s = print_model(b, name, (flags & WH_BUILD_STATS) ? ev : nullptr);
+  const int rc2 = text_out("wh_hmmbuild", s, out_text, out_len);
+  if (rc2) return rc2;
+  if (out_M) *out_M = b.h.M;
+  if (out_neff) *out_neff = b.neff;
+  return WH_OK;
+}
+
+extern "C" int wh_hmmbuild_batch(int device, const char *molecule, int32_t n, const int32_t *nseq, const int64_t *alen,
+                                 const char *const *const *rows, const char *const *names, double ere, double symfrac, double fragthresh,
+                                 int32_t flags, char **out_text, int64_t *out_len, int32_t *out_M, double *out_neff, double *out_stats) {
+  if (n < 0 || (n > 0 && (!nseq || !alen || !rows || !out_text || !out_len))) { wh::set_error("wh_hmmbuild_batch: bad argument"); return WH_EINVAL; }
+  for (int i = 0; i < n; i++) { out_text[i] = nullptr; out_len[i] = 0; }
+  if (n == 0) return WH_OK;
+  const bool stats = (flags & WH_BUILD_STATS) != 0;
+  char who[64];
+  // ---- build: every model in memory
+  std::vector<Built> built((size_t)n);
+  for (int i = 0; i < n; i++) {
+    snprintf(who, sizeof who, "wh_hmmbuild_batch: model %d", i);
+    if (!rows[i]) { wh::set_error("%s: no rows", who); return WH_EINVAL; }
+    const int rc = build_model(who, molecule, nseq[i], alen[i], rows[i], ere, symfrac, fragthresh, built[(size_t)i]);
+    if (rc) return rc;
+  }
+  // ---- calibrate: one batch, one set of sequences (they depend on the alphabet's background alone)
+  std::vector<double> ev;
+  if (stats) {
+    ev.assign((size_t)n * 4, 0.0);
+    CalibSeqs seqs;
+    calib_draw(built[0].abc.bg, built[0].abc.K, seqs);
+    if (device < 0) {
+      for (int i = 0; i < n; i++) {
+        CalibModel cm;
+        calib_model_of(built[(size_t)i], cm);
+        CalibPrep p;
+        calib_prepare(cm, mean_match_relent(built[(size_t)i].h, built[(size_t)i].abc.bg), p);
+        int msv[kCalibN], vit[kCalibN];
+        double fwd[kCalibN];
+        calib_sweeps_host(p, seqs, msv, vit, fwd);
+        calib_finish(p, msv, vit, fwd, &ev[(size_t)i * 4]);
+      }
+    } else {
+#ifdef WH_HOST_ONLY
+      wh::set_error("wh_hmmbuild_batch: this build has no device code (device %d asked for; device < 0 calibrates on the host)", device);
+      return WH_ENODEV;
+#else
+      std::vector<CalibPrep> preps((size_t)n);
+      for (int i = 0; i < n; i++) {
+        CalibModel cm;
+        calib_model_of(built[(size_t)i], cm);
+        calib_prepare(cm, mean_match_relent(built[(size_t)i].h, built[(size_t)i].abc.bg), preps[(size_t)i]);
+      }
+      std::vector<int> msv((size_t)n * kCalibN), vit((size_t)n * kCalibN);
+      std::vector<double> fwd((size_t)n * kCalibN);
+      const int rc = wh::calibrate_device(device, n, preps.data(), seqs, flags, msv.data(), vit.data(), fwd.data());
+      if (rc) return rc;
+      for (int i = 0; i < n; i++)
+        calib_finish(preps[(size_t)i], &msv[(size_t)i * kCalibN], &vit[(size_t)i * kCalibN], &fwd[(size_t)i * kCalibN], &ev[(size_t)i * 4]);
+#endif
+    }
+  }
+  // ---- print
+  for (int i = 0; i < n; i++) {
+    snprintf(who, sizeof who, "wh_hmmbuild_batch: model %d", i);
+    const std::string s = print_model(built[(size_t)i], names ? names[i] : nullptr, stats ? &ev[(size_t)i * 4] : nullptr);
+    const int rc = text_out(who, s, &out_text[i], &out_len[i]);
+    if (rc) {
+      for (int j = 0; j < i; j++) { free(out_text[j]); out_text[j] = nullptr; out_len[j] = 0; }
+      return rc;
+    }
+    if (out_M) out_M[i] = built[(size_t)i].h.M;
+    if (out_neff) out_neff[i] = built[(size_t)i].neff;
+    if (out_stats) for (int z = 0; z < 4; z++) out_stats[(size_t)i * 4 + z] = stats ? ev[(size_t)i * 4 + z] : 0.0;
+  }
   return WH_OK;
 }
 

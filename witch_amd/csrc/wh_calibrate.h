@@ -15,12 +15,56 @@
 //    dynamic programmes, so a scalar restatement gives the striped SSE code's numbers;
 //  * the Forward score only enters a maximum-likelihood Gumbel fit of 200 values: float64 here against HMMER's
 //    float32 parser moves tau in its fifth decimal at most.
-// Included by wh_build.cpp inside its unnamed namespace (uses its transition indices tMM .. tDD).
+//
+// One source for the host and the device: the three dynamic programmes (calib_msv_core, calib_viterbi_core,
+// calib_forward_core) are plain functions over row / table accessors, marked WH_HD, and hold no container.  The host
+// path (calibrate_model) runs them over vectors with stride 1; wh_calibrate.hip runs the same functions with one lane
+// per (model, sequence) over lane-interleaved rows in HBM.  The overflow exits of the two filters (xE + bias == 255,
+// xE >= 32767) are not reachable with the seeded sequences, so no test can cover them on either side: they are the
+// same statements on both.  Everything with a libm call in it (profile conversion, exp tables, the final log, the
+// Gumbel fits) is host code, before and after the sweeps.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <vector>
+
+#if defined(__HIPCC__)
+#define WH_HD __host__ __device__
+#else
+#define WH_HD
+#endif
+#if defined(__clang__)
+#define WH_UNROLL _Pragma("unroll")
+#else
+#define WH_UNROLL
+#endif
+
+namespace whc {
+
+enum { tMM = 0, tMI, tMD, tIM, tII, tDM, tDD };
+
+// hmmbuild's defaults: 200 sequences per filter; MSV and Viterbi on 200 residues, Forward on 100
+enum { kCalibN = 200, kCalibEmL = 200, kCalibEvL = 200, kCalibEfL = 100 };
+
+// The sweeps read row i-1 kCalibChunk nodes at a time, all loads of a chunk ahead of its first store: on the device the
+// loads are in flight together instead of one memory latency per node.  Data movement only: the cells are computed in
+// the same order from the same values, whatever the chunk.
+enum { kCalibChunk = 8 };
+
+// element k of a row (or of a sequence) that is <stride> elements apart: 1 on the host, the lanes of a launch on the device
+template <class T> struct CalibRow {
+  T *p;
+  size_t stride;
+  WH_HD T get(int k) const { return p[(size_t)k * stride]; }
+  WH_HD void set(int k, T v) const { p[(size_t)k * stride] = v; }
+  WH_HD CalibRow plus(size_t elems) const { return CalibRow{p + elems * stride, stride}; }
+};
+
+
+template <class T> WH_HD inline T calib_max(T a, T b) { return a < b ? b : a; }
 
 struct CalibModel {
   int M, K;
@@ -54,6 +98,26 @@ struct CalibRng {
     return K - 1;
   }
 };
+
+// The 600 sequences of one calibration: the generator is re-seeded with 42 for every model and draws from the
+// background alone, so they are the same for every model of an alphabet.  s[0] MSV, s[1] Viterbi, s[2] Forward, each
+// [kCalibN][L + 2] with the residues at 1 .. L.
+struct CalibSeqs {
+  int L[3];
+  std::vector<uint8_t> s[3];
+  const uint8_t *seq(int phase, int i) const { return s[phase].data() + (size_t)i * (size_t)(L[phase] + 2); }
+};
+
+inline void calib_draw(const float *bg, int K, CalibSeqs &q) {
+  CalibRng rng(42u);
+  q.L[0] = kCalibEmL; q.L[1] = kCalibEvL; q.L[2] = kCalibEfL;
+  for (int ph = 0; ph < 3; ph++) {
+    const int L = q.L[ph];
+    q.s[ph].assign((size_t)kCalibN * (size_t)(L + 2), 0);
+    for (int n = 0; n < kCalibN; n++)
+      for (int i = 1; i <= L; i++) q.s[ph][(size_t)n * (size_t)(L + 2) + (size_t)i] = (uint8_t)rng.choose(bg, K);
+  }
+}
 
 // the float32 log-odds profile p7_ProfileConfig builds in local multihit mode (what the optimized profile is converted from)
 struct CalibProfile {
@@ -117,33 +181,52 @@ inline void calib_msv_convert(const CalibProfile &gm, CalibMSV &om) {
   om.tjb = 0;
 }
 
-inline uint8_t sat_addu8(uint8_t a, uint8_t b) { const int s = (int)a + (int)b; return s > 255 ? 255 : (uint8_t)s; }
-inline uint8_t sat_subu8(uint8_t a, uint8_t b) { return a > b ? (uint8_t)(a - b) : 0; }
+WH_HD inline uint8_t sat_addu8(uint8_t a, uint8_t b) { const int s = (int)a + (int)b; return s > 255 ? 255 : (uint8_t)s; }
+WH_HD inline uint8_t sat_subu8(uint8_t a, uint8_t b) { return a > b ? (uint8_t)(a - b) : 0; }
 
-// score in nats; overflow returns the filter's ceiling like p7_MSVMu does
-inline float calib_msv(const CalibMSV &om, const uint8_t *dsq, int L, std::vector<uint8_t> &dp) {
-  const int M = om.M;
-  dp.assign((size_t)M + 1, 0);
+// the filter's scalars, as the sweep takes them
+struct CalibMSVPar { uint8_t base, bias, tbm, tec, tjb; };
+
+// The sweep: rb [K][M+1] (any pointer: host memory, LDS, HBM), dsq residues 1 .. L, two rows r0 / r1 of M+1 bytes that
+// it ping-pongs (the loads of row i-1 never alias the stores of row i).  Returns xJ, or -1 where the filter overflows
+// (p7_MSVMu then takes the filter's ceiling: calib_msv_score).
+template <class Tab, class Seq, class Row>
+WH_HD inline int calib_msv_core(int M, CalibMSVPar om, Tab rb, Seq dsq, int L, Row r0, Row r1) {
+  for (int k = 0; k <= M; k++) r0.set(k, 0);
   const uint8_t tjbm = (uint8_t)((int8_t)om.tjb + (int8_t)om.tbm);
   uint8_t xJ = 0, xB = sat_subu8(om.base, tjbm);
   for (int i = 1; i <= L; i++) {
-    const uint8_t *rsc = &om.rb[(size_t)dsq[i] * (M + 1)];
+    const Tab rsc = rb + (size_t)dsq.get(i) * (size_t)(M + 1);
     uint8_t xE = 0, prev = 0;          // prev = M(i-1, k-1); node 0 is -infinity (0)
-    for (int k = 1; k <= M; k++) {
-      uint8_t sv = std::max(prev, xB);
+    auto cell = [&](int k, uint8_t up) {      // up = M(i-1, k)
+      uint8_t sv = calib_max(prev, xB);
       sv = sat_addu8(sv, om.bias);
       sv = sat_subu8(sv, rsc[k]);
-      xE = std::max(xE, sv);
-      prev = dp[(size_t)k];
-      dp[(size_t)k] = sv;
+      xE = calib_max(xE, sv);
+      prev = up;
+      r1.set(k, sv);
+    };
+    int k = 1;
+    for (; k + kCalibChunk <= M + 1; k += kCalibChunk) {
+      uint8_t up[kCalibChunk];
+      WH_UNROLL for (int j = 0; j < kCalibChunk; j++) up[j] = r0.get(k + j);
+      WH_UNROLL for (int j = 0; j < kCalibChunk; j++) cell(k + j, up[j]);
     }
-    if (sat_addu8(xE, om.bias) == 255) return (float)(255 - om.base) / om.scale;
+    for (; k <= M; k++) cell(k, r0.get(k));
+    if (sat_addu8(xE, om.bias) == 255) return -1;
     xE = sat_subu8(xE, om.tec);
-    xJ = std::max(xJ, xE);
-    xB = std::max(om.base, xJ);
+    xJ = calib_max(xJ, xE);
+    xB = calib_max(om.base, xJ);
     xB = sat_subu8(xB, tjbm);
+    const Row t = r0; r0 = r1; r1 = t;
   }
-  float sc = (float)((int)xJ - (int)om.tjb) - (float)om.base;
+  return (int)xJ;
+}
+
+// score in nats; overflow returns the filter's ceiling like p7_MSVMu does
+inline float calib_msv_score(const CalibMSV &om, int raw) {
+  if (raw < 0) return (float)(255 - om.base) / om.scale;
+  float sc = (float)(raw - (int)om.tjb) - (float)om.base;
   sc /= om.scale;
   sc -= 3.0f;
   return sc;
@@ -194,42 +277,63 @@ inline void calib_vit_convert(const CalibProfile &gm, CalibVit &om) {
   om.xNCJ_move = 0;
 }
 
-inline int16_t sat_add16(int16_t a, int16_t b) { const int s = (int)a + (int)b; return s > 32767 ? 32767 : s < -32768 ? -32768 : (int16_t)s; }
+WH_HD inline int16_t sat_add16(int16_t a, int16_t b) { const int s = (int)a + (int)b; return s > 32767 ? 32767 : s < -32768 ? -32768 : (int16_t)s; }
 
-inline float calib_viterbi(const CalibVit &om, const uint8_t *dsq, int L, std::vector<int16_t> &mx) {
-  const int M = om.M;
-  mx.assign((size_t)3 * (M + 1), -32768);
-  int16_t *Mx = mx.data(), *Ix = Mx + (M + 1), *Dx = Ix + (M + 1);
+struct CalibVitPar { int16_t base, xE_loop, xE_move, xNCJ_move; };
+enum { kCalibVitOverflow = 32768 };
+
+// The sweep: rw [K][M+1], tw [M+1][8]; a / b: two sets of three rows (M, I, D; M+1 words each, one after the other)
+// that it ping-pongs.  Only nodes 1 .. M of a row are ever read.  Returns xC (-32768: no path), or kCalibVitOverflow
+// where the filter overflows (calib_vit_score).
+template <class Tab, class Seq, class Row>
+WH_HD inline int calib_viterbi_core(int M, CalibVitPar om, Tab rw, Tab tw, Seq dsq, int L, Row a, Row b) {
+  const size_t W = (size_t)M + 1;
+  for (int k = 0; k < 3 * (M + 1); k++) a.set(k, -32768);
   int16_t xN = om.base, xB = (int16_t)((int)xN + (int)om.xNCJ_move), xJ = -32768, xC = -32768, xE;
   for (int i = 1; i <= L; i++) {
-    const int16_t *rsc = &om.rw[(size_t)dsq[i] * (M + 1)];
+    const Tab rsc = rw + (size_t)dsq.get(i) * W;
+    const Row pM = a, pI = a.plus(W), pD = a.plus(2 * W);
+    const Row cM = b, cI = b.plus(W), cD = b.plus(2 * W);
     int16_t pm = -32768, pi_ = -32768, pd = -32768;     // row i-1 at node k-1
     int16_t dcv = -32768;                               // D(i,k): M(i,k-1) + MD, closed over DD below
     xE = -32768;
-    for (int k = 1; k <= M; k++) {
-      const int16_t *tp = &om.tw[(size_t)k * 8];
+    auto cell = [&](int k, int16_t um, int16_t ui, int16_t ud) {      // um, ui, ud = M, I, D of row i-1 at node k
+      const Tab tp = tw + (size_t)k * 8;
       int16_t sv = sat_add16(xB, tp[vBM]);
-      sv = std::max(sv, sat_add16(pm, tp[vMM]));
-      sv = std::max(sv, sat_add16(pi_, tp[vIM]));
-      sv = std::max(sv, sat_add16(pd, tp[vDM]));
+      sv = calib_max(sv, sat_add16(pm, tp[vMM]));
+      sv = calib_max(sv, sat_add16(pi_, tp[vIM]));
+      sv = calib_max(sv, sat_add16(pd, tp[vDM]));
       sv = sat_add16(sv, rsc[k]);
-      xE = std::max(xE, sv);
-      pm = Mx[k]; pi_ = Ix[k]; pd = Dx[k];
-      Mx[k] = sv;
+      xE = calib_max(xE, sv);
+      pm = um; pi_ = ui; pd = ud;
+      cM.set(k, sv);
       // D(i,k) = max(M(i,k-1) + MD(k-1), D(i,k-1) + DD(k-1)): the lazy-F passes of the SSE code reach this closure
-      Dx[k] = dcv;
-      const int16_t fromD = sat_add16(Dx[k], tp[vDD]);
-      dcv = std::max(sat_add16(sv, tp[vMD]), fromD);
-      Ix[k] = std::max(sat_add16(pm, tp[vMI]), sat_add16(pi_, tp[vII]));
+      cD.set(k, dcv);
+      const int16_t fromD = sat_add16(dcv, tp[vDD]);
+      dcv = calib_max(sat_add16(sv, tp[vMD]), fromD);
+      cI.set(k, calib_max(sat_add16(pm, tp[vMI]), sat_add16(pi_, tp[vII])));
+    };
+    int k = 1;
+    for (; k + kCalibChunk <= M + 1; k += kCalibChunk) {
+      int16_t um[kCalibChunk], ui[kCalibChunk], ud[kCalibChunk];
+      WH_UNROLL for (int j = 0; j < kCalibChunk; j++) { um[j] = pM.get(k + j); ui[j] = pI.get(k + j); ud[j] = pD.get(k + j); }
+      WH_UNROLL for (int j = 0; j < kCalibChunk; j++) cell(k + j, um[j], ui[j], ud[j]);
     }
-    if (xE >= 32767) return (32767.0f - (float)om.base) / om.scale;
+    for (; k <= M; k++) cell(k, pM.get(k), pI.get(k), pD.get(k));
+    if (xE >= 32767) return kCalibVitOverflow;
     // NN = CC = JJ = 0 (the -3 nat approximation)
-    xC = (int16_t)std::max((int)xC, (int)xE + (int)om.xE_move);
-    xJ = (int16_t)std::max((int)xJ, (int)xE + (int)om.xE_loop);
-    xB = (int16_t)std::max((int)xJ + (int)om.xNCJ_move, (int)xN + (int)om.xNCJ_move);
+    xC = (int16_t)calib_max((int)xC, (int)xE + (int)om.xE_move);
+    xJ = (int16_t)calib_max((int)xJ, (int)xE + (int)om.xE_loop);
+    xB = (int16_t)calib_max((int)xJ + (int)om.xNCJ_move, (int)xN + (int)om.xNCJ_move);
+    const Row t = a; a = b; b = t;
   }
-  if (xC > -32768) {
-    float sc = (float)xC + (float)om.xNCJ_move - (float)om.base;
+  return (int)xC;
+}
+
+inline float calib_vit_score(const CalibVit &om, int raw) {
+  if (raw == kCalibVitOverflow) return (32767.0f - (float)om.base) / om.scale;
+  if (raw > -32768) {
+    float sc = (float)(int16_t)raw + (float)om.xNCJ_move - (float)om.base;
     sc /= om.scale;
     sc -= 3.0f;
     return sc;
@@ -238,58 +342,99 @@ inline float calib_viterbi(const CalibVit &om, const uint8_t *dsq, int L, std::v
 }
 
 // ---- Forward, local multihit, length model L (float64, scaled rows) ------------------------------------------
-inline double calib_forward(const CalibProfile &gm, const uint8_t *dsq, int L, std::vector<double> &w) {
+// probabilities from the float scores, as the optimized profile holds them
+enum { fMM = 0, fIM, fDM, fBM, fMD, fMI, fII, fDD };
+struct CalibFwd {
+  int M, K;
+  std::vector<double> ft;    // [M+1][8]: MM IM DM BM (into node k), MD MI II DD (out of node k)
+  std::vector<double> em;    // [K][M+1]: exp(match emission score)
+  double pmove, ploop;
+};
+
+inline void calib_fwd_convert(const CalibProfile &gm, int L, CalibFwd &f) {
   const int M = gm.M, K = gm.K;
-  // probabilities from the float scores, as the optimized profile holds them
-  w.assign((size_t)8 * (M + 1) + (size_t)3 * (M + 1) * 2, 0.0);
-  double *tMMp = w.data(), *tIMp = tMMp + (M + 1), *tDMp = tIMp + (M + 1), *tBMp = tDMp + (M + 1);
-  double *tMDp = tBMp + (M + 1), *tMIp = tMDp + (M + 1), *tIIp = tMIp + (M + 1), *tDDp = tIIp + (M + 1);
-  double *row0 = tDDp + (M + 1), *row1 = row0 + 3 * (M + 1);
+  f.M = M; f.K = K;
+  f.ft.assign((size_t)(M + 1) * 8, 0.0);
+  f.em.assign((size_t)K * (M + 1), 0.0);
   for (int k = 1; k <= M; k++) {
     const int kb = k - 1;
-    tBMp[k] = std::exp((double)gm.bm[(size_t)kb]);
-    tMMp[k] = std::exp((double)gm.tsc[(size_t)kb * 7 + tMM]);
-    tIMp[k] = std::exp((double)gm.tsc[(size_t)kb * 7 + tIM]);
-    tDMp[k] = std::exp((double)gm.tsc[(size_t)kb * 7 + tDM]);
+    double *tp = &f.ft[(size_t)k * 8];
+    tp[fBM] = std::exp((double)gm.bm[(size_t)kb]);
+    tp[fMM] = std::exp((double)gm.tsc[(size_t)kb * 7 + tMM]);
+    tp[fIM] = std::exp((double)gm.tsc[(size_t)kb * 7 + tIM]);
+    tp[fDM] = std::exp((double)gm.tsc[(size_t)kb * 7 + tDM]);
     if (k < M) {
-      tMDp[k] = std::exp((double)gm.tsc[(size_t)k * 7 + tMD]);
-      tMIp[k] = std::exp((double)gm.tsc[(size_t)k * 7 + tMI]);
-      tIIp[k] = std::exp((double)gm.tsc[(size_t)k * 7 + tII]);
-      tDDp[k] = std::exp((double)gm.tsc[(size_t)k * 7 + tDD]);
+      tp[fMD] = std::exp((double)gm.tsc[(size_t)k * 7 + tMD]);
+      tp[fMI] = std::exp((double)gm.tsc[(size_t)k * 7 + tMI]);
+      tp[fII] = std::exp((double)gm.tsc[(size_t)k * 7 + tII]);
+      tp[fDD] = std::exp((double)gm.tsc[(size_t)k * 7 + tDD]);
     }
+    for (int x = 0; x < K; x++) f.em[(size_t)x * (M + 1) + k] = std::exp((double)gm.msc[(size_t)k * K + x]);
   }
   const float pmove_f = 3.0f / ((float)L + 3.0f), ploop_f = 1.0f - pmove_f;
-  const double pmove = pmove_f, ploop = ploop_f;
-  double xN = 1.0, xB = pmove, xJ = 0.0, xC = 0.0, logscale = 0.0;
-  double *prev = row0, *cur = row1;
-  for (int k = 0; k <= 3 * M + 2; k++) prev[k] = 0.0;
+  f.pmove = pmove_f; f.ploop = ploop_f;
+}
+
+// The sweep: float64 multiplies and adds in one fixed order, never fused (a fused multiply-add rounds once where the
+// host rounds twice), so the device's values are the host's to the bit.  a / b: two sets of three rows (M, I, D) of M+1
+// doubles; only nodes 1 .. M are read.  A row whose sums leave the double range is rescaled by s; the factors go to
+// scales[0 .. *nscale) and the host takes their logarithms (calib_forward_score).  Returns xC * pmove.
+template <class Tab, class Seq, class Row, class Sc>
+WH_HD inline double calib_forward_core(int M, Tab ft, Tab em, double pmove, double ploop, Seq dsq, int L, Row a, Row b, Sc scales, int *nscale) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const size_t W = (size_t)M + 1;
+  double xN = 1.0, xB = pmove, xJ = 0.0, xC = 0.0;
+  int ns = 0;
+  for (int k = 0; k < 3 * (M + 1); k++) a.set(k, 0.0);
   for (int i = 1; i <= L; i++) {
-    const int x = dsq[i];
-    double *pM = prev, *pI = prev + (M + 1), *pD = pI + (M + 1);
-    double *cM = cur, *cI = cur + (M + 1), *cD = cI + (M + 1);
-    cM[0] = cI[0] = cD[0] = 0.0;
+    const Tab esc = em + (size_t)dsq.get(i) * W;
+    const Row pM = a, pI = a.plus(W), pD = a.plus(2 * W);
+    const Row cM = b, cI = b.plus(W), cD = b.plus(2 * W);
     double xE = 0.0;
-    for (int k = 1; k <= M; k++) {
-      const double e = std::exp((double)gm.msc[(size_t)k * K + x]);
-      const double m = e * (xB * tBMp[k] + pM[k - 1] * tMMp[k] + pI[k - 1] * tIMp[k] + pD[k - 1] * tDMp[k]);
-      cM[k] = m;
-      cI[k] = k < M ? pM[k] * tMIp[k] + pI[k] * tIIp[k] : 0.0;
-      cD[k] = k > 1 ? cM[k - 1] * tMDp[k - 1] + cD[k - 1] * tDDp[k - 1] : 0.0;
-      xE += m + cD[k];
+    double pm1 = 0.0, pi1 = 0.0, pd1 = 0.0;      // row i-1 at node k-1 (node 0: 0)
+    double cm1 = 0.0, cd1 = 0.0, tmd1 = 0.0, tdd1 = 0.0;      // row i at node k-1, and that node's MD / DD
+    auto cell = [&](int k, double um, double ui, double ud) {      // um, ui, ud = M, I, D of row i-1 at node k
+      const Tab tp = ft + (size_t)k * 8;
+      const double e = esc[k];
+      const double m = e * (xB * tp[fBM] + pm1 * tp[fMM] + pi1 * tp[fIM] + pd1 * tp[fDM]);
+      pm1 = um; pi1 = ui; pd1 = ud;
+      cM.set(k, m);
+      cI.set(k, k < M ? pm1 * tp[fMI] + pi1 * tp[fII] : 0.0);
+      const double d = k > 1 ? cm1 * tmd1 + cd1 * tdd1 : 0.0;
+      cD.set(k, d);
+      xE += m + d;
+      cm1 = m; cd1 = d; tmd1 = tp[fMD]; tdd1 = tp[fDD];
+    };
+    int k = 1;
+    for (; k + kCalibChunk <= M + 1; k += kCalibChunk) {
+      double um[kCalibChunk], ui[kCalibChunk], ud[kCalibChunk];
+      WH_UNROLL for (int j = 0; j < kCalibChunk; j++) { um[j] = pM.get(k + j); ui[j] = pI.get(k + j); ud[j] = pD.get(k + j); }
+      WH_UNROLL for (int j = 0; j < kCalibChunk; j++) cell(k + j, um[j], ui[j], ud[j]);
     }
+    for (; k <= M; k++) cell(k, pM.get(k), pI.get(k), pD.get(k));
     xJ = xJ * ploop + xE * 0.5;
     xC = xC * ploop + xE * 0.5;
     xN = xN * ploop;
     xB = (xN + xJ) * pmove;
     if (xE > 1e100 || (xE > 0.0 && xE < 1e-100) || xN < 1e-250) {
-      const double s = 1.0 / std::max(std::max(xE, xN), std::max(xJ, xC));
-      for (int k = 0; k <= 3 * M + 2; k++) cur[k] *= s;
+      const double s = 1.0 / calib_max(calib_max(xE, xN), calib_max(xJ, xC));
+      for (int k = 1; k <= M; k++) { cM.set(k, cM.get(k) * s); cI.set(k, cI.get(k) * s); cD.set(k, cD.get(k) * s); }
       xN *= s; xB *= s; xJ *= s; xC *= s;
-      logscale -= std::log(s);
+      scales.set(ns++, s);
     }
-    std::swap(prev, cur);
+    const Row t = a; a = b; b = t;
   }
-  return std::log(xC * pmove) + logscale;
+  *nscale = ns;
+  return xC * pmove;
+}
+
+// the Forward score in nats from what the sweep returns
+inline double calib_forward_score(double xCp, const double *scales, size_t stride, int nscale) {
+  double logscale = 0.0;
+  for (int j = 0; j < nscale; j++) logscale -= std::log(scales[(size_t)j * stride]);
+  return std::log(xCp) + logscale;
 }
 
 // ---- Gumbel fits (Easel) -----------------------------------------------------------------------------------
@@ -341,64 +486,96 @@ inline void calib_fit_complete(const std::vector<double> &x, double &mu, double 
   mu = -std::log(esum / n) / lambda;
 }
 
-// lambda, MSV mu, Viterbi mu, Forward tau
-inline void calibrate_model(const CalibModel &h, double meanrelent_bits, double out[4]) {
+// ---- one model: what the host prepares, and what it does with the sweeps' results ---------------------------
+struct CalibPrep {
+  CalibMSV msv;
+  CalibVit vit;
+  CalibFwd fwd;
+  double lambda;
+};
+
+inline void calib_prepare(const CalibModel &h, double meanrelent_bits, CalibPrep &p) {
   const double LOG2 = 0.69314718055994529;
-  const int EmL = 200, EmN = 200, EvL = 200, EvN = 200, EfL = 100, EfN = 200;
-  const double Eft = 0.04;
   CalibProfile gm;
   calib_profile(h, gm);
-  const double lambda = LOG2 + 1.44 / ((double)h.M * meanrelent_bits);
-  CalibRng rng(42u);
-  std::vector<uint8_t> dsq;
-  auto draw = [&](int L) {
-    dsq.assign((size_t)L + 2, 0);
-    for (int i = 1; i <= L; i++) dsq[(size_t)i] = (uint8_t)rng.choose(h.bg, h.K);
-  };
+  p.lambda = LOG2 + 1.44 / ((double)h.M * meanrelent_bits);
+  calib_msv_convert(gm, p.msv);
+  p.msv.tjb = p.msv.unbiased(logf(3.0f / (float)(kCalibEmL + 3)));
+  calib_vit_convert(gm, p.vit);
+  p.vit.xNCJ_move = p.vit.wordify(logf(3.0f / ((float)kCalibEvL + 3.0f)));
+  calib_fwd_convert(gm, kCalibEfL, p.fwd);
+}
+
+inline CalibMSVPar calib_msv_par(const CalibMSV &om) { return CalibMSVPar{om.base, om.bias, om.tbm, om.tec, om.tjb}; }
+inline CalibVitPar calib_vit_par(const CalibVit &om) { return CalibVitPar{om.base, om.xE_loop, om.xE_move, om.xNCJ_move}; }
+
+// msv / vit: the kCalibN raw results of the two filters; fwd: the kCalibN Forward scores in nats (calib_forward_score).
+// out: lambda, MSV mu, Viterbi mu, Forward tau
+inline void calib_finish(const CalibPrep &p, const int *msv, const int *vit, const double *fwd, double out[4]) {
+  const double LOG2 = 0.69314718055994529;
+  const double Eft = 0.04;
+  const double lambda = p.lambda;
   std::vector<double> xv;
-  // MSV
   {
-    CalibMSV om;
-    calib_msv_convert(gm, om);
-    om.tjb = om.unbiased(logf(3.0f / (float)(EmL + 3)));
-    const float nullsc = calib_nullone(EmL);
-    std::vector<uint8_t> dp;
-    xv.clear();
-    for (int i = 0; i < EmN; i++) {
-      draw(EmL);
-      const float sc = calib_msv(om, dsq.data(), EmL, dp);
-      xv.push_back((double)(sc - nullsc) / LOG2);
-    }
+    const float nullsc = calib_nullone(kCalibEmL);
+    for (int i = 0; i < kCalibN; i++) xv.push_back((double)(calib_msv_score(p.msv, msv[i]) - nullsc) / LOG2);
   }
   const double mmu = calib_fit_loc(xv, lambda);
-  // Viterbi
   {
-    CalibVit om;
-    calib_vit_convert(gm, om);
-    om.xNCJ_move = om.wordify(logf(3.0f / ((float)EvL + 3.0f)));
-    const float nullsc = calib_nullone(EvL);
-    std::vector<int16_t> mx;
+    const float nullsc = calib_nullone(kCalibEvL);
     xv.clear();
-    for (int i = 0; i < EvN; i++) {
-      draw(EvL);
-      const float sc = calib_viterbi(om, dsq.data(), EvL, mx);
-      xv.push_back((double)(sc - nullsc) / LOG2);
-    }
+    for (int i = 0; i < kCalibN; i++) xv.push_back((double)(calib_vit_score(p.vit, vit[i]) - nullsc) / LOG2);
   }
   const double vmu = calib_fit_loc(xv, lambda);
-  // Forward
   {
-    const float nullsc = calib_nullone(EfL);
-    std::vector<double> w;
+    const float nullsc = calib_nullone(kCalibEfL);
     xv.clear();
-    for (int i = 0; i < EfN; i++) {
-      draw(EfL);
-      const float fsc = (float)calib_forward(gm, dsq.data(), EfL, w);
-      xv.push_back((double)(fsc - nullsc) / LOG2);
-    }
+    for (int i = 0; i < kCalibN; i++) xv.push_back((double)((float)fwd[i] - nullsc) / LOG2);
   }
   double gmu, glam;
   calib_fit_complete(xv, gmu, glam);
   const double tau = (gmu - std::log(-1. * std::log(1.0 - Eft)) / glam) + (std::log(Eft) / lambda);
   out[0] = lambda; out[1] = mmu; out[2] = vmu; out[3] = tau;
 }
+
+// the three sweeps of one prepared model on the host, sequence after sequence
+inline void calib_sweeps_host(const CalibPrep &p, const CalibSeqs &q, int *msv, int *vit, double *fwd) {
+  const int M = p.msv.M;
+  const size_t W = (size_t)M + 1;
+  typedef CalibRow<const uint8_t> Seq;
+  {
+    std::vector<uint8_t> dp(2 * W);
+    for (int i = 0; i < kCalibN; i++)
+      msv[i] = calib_msv_core(M, calib_msv_par(p.msv), p.msv.rb.data(), Seq{q.seq(0, i), 1}, q.L[0],
+                              CalibRow<uint8_t>{dp.data(), 1}, CalibRow<uint8_t>{dp.data() + W, 1});
+  }
+  {
+    std::vector<int16_t> mx(6 * W);
+    for (int i = 0; i < kCalibN; i++)
+      vit[i] = calib_viterbi_core(M, calib_vit_par(p.vit), p.vit.rw.data(), p.vit.tw.data(), Seq{q.seq(1, i), 1}, q.L[1],
+                                  CalibRow<int16_t>{mx.data(), 1}, CalibRow<int16_t>{mx.data() + 3 * W, 1});
+  }
+  {
+    std::vector<double> w(6 * W), sc((size_t)q.L[2]);
+    for (int i = 0; i < kCalibN; i++) {
+      int ns = 0;
+      const double xCp = calib_forward_core(M, p.fwd.ft.data(), p.fwd.em.data(), p.fwd.pmove, p.fwd.ploop, Seq{q.seq(2, i), 1}, q.L[2],
+                                            CalibRow<double>{w.data(), 1}, CalibRow<double>{w.data() + 3 * W, 1}, CalibRow<double>{sc.data(), 1}, &ns);
+      fwd[i] = calib_forward_score(xCp, sc.data(), 1, ns);
+    }
+  }
+}
+
+// lambda, MSV mu, Viterbi mu, Forward tau
+inline void calibrate_model(const CalibModel &h, double meanrelent_bits, double out[4]) {
+  CalibPrep p;
+  calib_prepare(h, meanrelent_bits, p);
+  CalibSeqs q;
+  calib_draw(h.bg, h.K, q);
+  int msv[kCalibN], vit[kCalibN];
+  double fwd[kCalibN];
+  calib_sweeps_host(p, q, msv, vit, fwd);
+  calib_finish(p, msv, vit, fwd, out);
+}
+
+}  // namespace whc
