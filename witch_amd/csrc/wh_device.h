@@ -293,30 +293,65 @@ __device__ __forceinline__ LenCfg len_config(int Lcfg, bool multihit) {
   return c;
 }
 
-// Per-wave LDS block: six float arrays of SP entries (special states per row) + small tables.
+// Per-wave LDS block: the special states of every row - six float arrays of SP entries, or one 6-word record per row
+// (SpecAt below; 6 x SP words either way) - + small tables.
 enum { SP_N = 0, SP_B, SP_E, SP_J, SP_C, SP_S, SP_ML, SP_MH, SP_NARR };   // SP_S: cumulative scale exponent (int bits);
                                                                   // SP_ML/MH: 64-bit mask of lanes whose row block was stored
 
 constexpr float kRescaleHi = 1048576.0f;   // 2^20
+
+// Where word (field, row) of the block lives.  SPEC_SOA: six (eight) arrays of SP entries, field-major - the layout of every
+// kernel but the one named below.  SPEC_ROWS (the LDS instantiations of score_kernel7, six fields only): one 6-word record per
+// row, the fields a sweep reads together side by side - (B,E) (S,N) (J,C); the stored unihit rows of an envelope keep their
+// mask words in the B / E slots as before, so their record reads (ML,MH) (S,N) (-,C).  A row's words then sit at constant
+// offsets from ONE address: the compiler pairs their accesses (ds_read2_b32 / ds_write2_b32, which need no 8-byte alignment)
+// where the field-major arrays, a run-time stride apart, cost one dependent LDS access each.  The block is 6 x SP words either way.
+enum { SPEC_SOA = 0, SPEC_ROWS = 1 };
+template <int LAYOUT>
+struct SpecAt {
+  int SP;
+  __device__ __forceinline__ int operator()(int field, int row) const {
+    if (LAYOUT == SPEC_ROWS) {
+      // SP_N, SP_B, SP_E, SP_J, SP_C, SP_S -> word of the record
+      return 6 * row + (field == SP_B ? 0 : field == SP_E ? 1 : field == SP_S ? 2 : field == SP_N ? 3 : field == SP_J ? 4 : 5);
+    }
+    return field * SP + row;
+  }
+  __device__ __forceinline__ int row0(int field) const { return LAYOUT == SPEC_ROWS ? (*this)(field, 0) : field * SP; }
+  // word (field, row - back), and its address: the arrays' index is formed as the kernels have always written it
+  // (SP_x * SP + i - 1: the long-query and A/B objects compile to the instructions they had)
+  __device__ __forceinline__ int operator()(int field, int row, int back) const {
+    if (LAYOUT == SPEC_ROWS) return (*this)(field, row - back);
+    return field * SP + row - back;
+  }
+  template <class T>
+  __device__ __forceinline__ T *ptr(T *spec, int field, int row, int back = 0) const {
+    if (LAYOUT == SPEC_ROWS) return spec + (*this)(field, row - back);
+    return back ? spec + field * SP + row - back : spec + field * SP + row;
+  }
+};
 
 // ------------------------------------------------------------------ region scan over special states in HBM
 // A.4's scan over rows 1..L (thresholds rt1/rt2) when the per-row arrays live in global memory: 64 rows are
 // fetched with one coalesced load per array and walked with v_readlane, instead of three dependent L2/HBM
 // round trips per row; the running sums are formed in the same order, so the result is bit-identical to the
 // row-by-row loop.  Writes the cumulative sums into SP_J / SP_C (coalesced) and the regions into regs[].
+// (SPEC_ROWS: the column reads are stride-6 reads of the records - three per 64 rows, a two-way bank conflict each)
+template <int LAYOUT = SPEC_SOA>
 __device__ __forceinline__ void region_scan_global(float *spec, int SP, int L, int *regs, int lane, int &nenv,
                                                    int &nreg, int &flags) {
+  const SpecAt<LAYOUT> at{SP};
   const float rt1 = 0.25f, rt2 = 0.10f;
   float btot = 0.f, etot = 0.f;
   int i0 = -1;
   bool trig = false;
-  if (lane == 0) { spec[SP_J * SP] = 0.f; spec[SP_C * SP] = 0.f; }
+  if (lane == 0) { spec[at.row0(SP_J)] = 0.f; spec[at.row0(SP_C)] = 0.f; }
   for (int j0 = 1; j0 <= L; j0 += kWave) {
     const int jj = j0 + lane;
     const bool valid = jj <= L;
-    const float nv = valid ? __builtin_nontemporal_load(spec + SP_N * SP + jj) : 0.f;
-    const float bv = valid ? __builtin_nontemporal_load(spec + SP_B * SP + jj - 1) : 0.f;
-    const float ev = valid ? __builtin_nontemporal_load(spec + SP_E * SP + jj) : 0.f;
+    const float nv = valid ? __builtin_nontemporal_load(at.ptr(spec, SP_N, jj)) : 0.f;
+    const float bv = valid ? __builtin_nontemporal_load(at.ptr(spec, SP_B, jj, 1)) : 0.f;
+    const float ev = valid ? __builtin_nontemporal_load(at.ptr(spec, SP_E, jj)) : 0.f;
     float jout = 0.f, cout = 0.f;
     const int cnt = L - j0 + 1 < kWave ? L - j0 + 1 : kWave;
     for (int t = 0; t < cnt; t++) {
@@ -340,7 +375,7 @@ __device__ __forceinline__ void region_scan_global(float *spec, int SP, int L, i
         trig = false;
       }
     }
-    if (valid) { spec[SP_J * SP + jj] = jout; spec[SP_C * SP + jj] = cout; }
+    if (valid) { spec[at(SP_J, jj)] = jout; spec[at(SP_C, jj)] = cout; }
   }
 }
 
@@ -357,11 +392,17 @@ __device__ __forceinline__ void region_scan_global(float *spec, int SP, int L, i
 // above E(row)/2 - written to um_out[0..1]; the multihit sweep uses it to place the node window of its Backward sweep.
 // BLK (with STORE): the stored rows keep a lane block's pieces contiguous (fs_piece, above: the scoring kernels); without it
 // piece-major rows (the alignment kernels, whose passes read and rewrite whole rows).
-template <int Q, bool TREG, bool STORE, bool USEP = false, bool SLIM = false, bool UM = false, bool COUNT = false, bool BLK = false>
+// UNI: <cfg> is a unihit length model, known at compile time (EJ == 0, EC == 1: the envelope sweeps of the scoring kernel).  J
+// stays 0 on every row, so the sweep keeps no J recurrence and stores no J row - what it leaves out multiplies by 0 or by 1, the
+// stored values are the same bits - and the Backward sweep that reads the rows must not read J (its UNI flag).
+// LAYOUT: where a row's special states go (SpecAt, above).
+template <int Q, bool TREG, bool STORE, bool USEP = false, bool SLIM = false, bool UM = false, bool COUNT = false, bool BLK = false, bool UNI = false, int LAYOUT = SPEC_SOA>
 __device__ __forceinline__ void forward_sweep(const TransTab<Q, TREG> &T, const ScanC &sc, const float *emL,
                                               const float *emG, int K, const uint8_t *seq, int L, LenCfg cfg,
                                               float *spec, int SP, float *Fs, float keep_scale, int lane,
                                               float &xC_out, int &ef_out, unsigned *um_out = nullptr, int *nstored_out = nullptr, int keep_lanes = 63 << 8) {
+  static_assert(LAYOUT == SPEC_SOA || !STORE || SLIM, "a record has six words: the mask words of a stored sweep share the B / E slots");
+  const SpecAt<LAYOUT> at{SP};
   float Mp[Q], Ip[Q], Dp[Q];
 #pragma unroll
   for (int q = 0; q < Q; q++) { Mp[q] = 0.f; Ip[q] = 0.f; Dp[q] = 0.f; }
@@ -373,8 +414,8 @@ __device__ __forceinline__ void forward_sweep(const TransTab<Q, TREG> &T, const 
                                      // envelope's dominant alignment runs.  The first rows set no bit: it takes ~25 nucleotides
                                      // until the true diagonal outweighs the chance matches among ~1000 others
   if (lane == 0) {
-    spec[SP_N * SP] = xN; spec[SP_B * SP] = xB; spec[SP_E * SP] = 0.f; spec[SP_J * SP] = 0.f;
-    spec[SP_C * SP] = 0.f; reinterpret_cast<int *>(spec)[SP_S * SP] = 0;
+    spec[at.row0(SP_N)] = xN; spec[at.row0(SP_B)] = xB; spec[at.row0(SP_E)] = 0.f; spec[at.row0(SP_J)] = 0.f;
+    spec[at.row0(SP_C)] = 0.f; reinterpret_cast<int *>(spec)[at.row0(SP_S)] = 0;
   }
 #pragma unroll 1
   for (int i = 1; i <= L; i++) {
@@ -435,22 +476,29 @@ __device__ __forceinline__ void forward_sweep(const TransTab<Q, TREG> &T, const 
     }
     xE = wave_sum(es);
     xN = xN * cfg.loop;
-    xC = fmaf(xC, cfg.loop, xE * cfg.EC);
-    xJ = fmaf(xJ, cfg.loop, xE * cfg.EJ);
+    if (UNI) {
+      xC = fmaf(xC, cfg.loop, xE);
+    } else {
+      xC = fmaf(xC, cfg.loop, xE * cfg.EC);
+      xJ = fmaf(xJ, cfg.loop, xE * cfg.EJ);
+    }
     if (xE > kRescaleHi) {
       const int e = f32_exponent(xE);
       const float r = pow2f_int(-e);
 #pragma unroll
       for (int q = 0; q < Q; q++) { Mp[q] *= r; Ip[q] *= r; Dp[q] *= r; }
-      xN *= r; xC *= r; xJ *= r; xE *= r;
+      xN *= r; xC *= r;
+      if (!UNI) xJ *= r;
+      xE *= r;
       ef += e;
     }
-    xB = (xJ + xN) * cfg.move;
+    xB = UNI ? xN * cfg.move : (xJ + xN) * cfg.move;
     if (lane == 0) {
-      spec[SP_N * SP + i] = xN;
-      if (!(STORE && SLIM)) { spec[SP_B * SP + i] = xB; spec[SP_E * SP + i] = xE; }
-      spec[SP_J * SP + i] = xJ; spec[SP_C * SP + i] = xC;
-      reinterpret_cast<int *>(spec)[SP_S * SP + i] = ef;
+      spec[at(SP_N, i)] = xN;
+      if (!(STORE && SLIM)) { spec[at(SP_B, i)] = xB; spec[at(SP_E, i)] = xE; }
+      if (!UNI) spec[at(SP_J, i)] = xJ;
+      spec[at(SP_C, i)] = xC;
+      reinterpret_cast<int *>(spec)[at(SP_S, i)] = ef;
     }
     if (UM && !STORE) {
       if ((i & 7) == 0) {
@@ -486,8 +534,8 @@ __device__ __forceinline__ void forward_sweep(const TransTab<Q, TREG> &T, const 
       const unsigned long long mask = __ballot(keep);
       if (COUNT) nstored += __builtin_popcountll(mask);
       if (lane == 0) {
-        reinterpret_cast<unsigned *>(spec)[ML * SP + i] = (unsigned)(mask & 0xFFFFFFFFull);
-        reinterpret_cast<unsigned *>(spec)[MH * SP + i] = (unsigned)(mask >> 32);
+        reinterpret_cast<unsigned *>(spec)[at(ML, i)] = (unsigned)(mask & 0xFFFFFFFFull);
+        reinterpret_cast<unsigned *>(spec)[at(MH, i)] = (unsigned)(mask >> 32);
       }
       if (keep) {
         float4 *row = reinterpret_cast<float4 *>(Fs) + (size_t)i * (2 * (Q / 4) * kWave);
@@ -502,8 +550,8 @@ __device__ __forceinline__ void forward_sweep(const TransTab<Q, TREG> &T, const 
   }
   if (STORE && lane == 0) {
     // row 0 of the two mask arrays is free (rows are 1..L): the dominant-path mask of the sweep
-    reinterpret_cast<unsigned *>(spec)[(SLIM ? SP_B : SP_ML) * SP] = (unsigned)(umask & 0xFFFFFFFFull);
-    reinterpret_cast<unsigned *>(spec)[(SLIM ? SP_E : SP_MH) * SP] = (unsigned)(umask >> 32);
+    reinterpret_cast<unsigned *>(spec)[at.row0(SLIM ? SP_B : SP_ML)] = (unsigned)(umask & 0xFFFFFFFFull);
+    reinterpret_cast<unsigned *>(spec)[at.row0(SLIM ? SP_E : SP_MH)] = (unsigned)(umask >> 32);
   }
   if (UM && !STORE && lane == 0) {
     um_out[0] = (unsigned)(umask & 0xFFFFFFFFull); um_out[1] = (unsigned)(umask >> 32);
@@ -536,6 +584,27 @@ __device__ __forceinline__ void mirror_scale(int dn, float (&Mb)[Q], float (&Ib)
     for (int p = 0; p < Q; p++) { Mb[p] *= r; Ib[p] *= r; }
     xJ *= r; xC *= r; xN *= r;
   }
+}
+
+// (unihit known at compile time: no J state - it follows N's recurrence from the same start and only ever meets EJ == 0)
+template <int Q>
+__device__ __forceinline__ void mirror_scale(int dn, float (&Mb)[Q], float (&Ib)[Q], float &xC, float &xN) {
+  if (dn != 0) {
+    const float r = __builtin_bit_cast(float, (127 - dn) << 23);
+#pragma unroll
+    for (int p = 0; p < Q; p++) { Mb[p] *= r; Ib[p] *= r; }
+    xC *= r; xN *= r;
+  }
+}
+template <int Q>
+__device__ __forceinline__ bool clamp_backward(float (&Mb)[Q], float (&Ib)[Q], float &xB, float &xC, float &xN) {
+  if (fmaxf(xB, fmaxf(xN, xC)) > kClampHi) {
+#pragma unroll
+    for (int p = 0; p < Q; p++) { Mb[p] = fminf(Mb[p], kClampHi); Ib[p] = fminf(Ib[p], kClampHi); }
+    xB = fminf(xB, kClampHi); xN = fminf(xN, kClampHi); xC = fminf(xC, kClampHi);
+    return true;
+  }
+  return false;
 }
 
 template <int Q>

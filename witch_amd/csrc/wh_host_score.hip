@@ -162,6 +162,9 @@ static ScoreArgs class_args(const ScoreCall &c, const ScoreClassPlan &p, int lau
   a.keep_scale = kn.keep_scale;
   a.spill_band = kn.kernel != 9 ? kn.spill_band : 0;
   a.Klds = p.Klds; a.SP = p.b.SP; a.wave_lds = p.b.wave_lds; a.spec_arrays = kScoreSpecArrays;
+  // (+ the layout of the block this build expects of the default scoring object, wh_score7.o: row records or arrays.  Its
+  // launchers refuse the other one - an object left over from a build with other flags - as they refuse six against eight arrays)
+  if (p.family == ScoreFamily::PhaseCall || p.family == ScoreFamily::FourEnvelope) a.spec_arrays |= kScoreSpecLayout << 8;
   a.paths = reinterpret_cast<unsigned long long *>(e->counter(kSlotScorePath));
   a.p2win = p.p2win;
   a.qorder = p.use_qorder ? c.d_qorder : nullptr;

@@ -20,6 +20,12 @@ constexpr size_t kLdsHeader = 16;   // work-item slot in front of the tables (ke
 // per-row special-state arrays of a wave's LDS block in the phase-call scoring kernel (wh_score7.hip is built with
 // WH_SLIM_SPEC: N, B, E, J, C, scale; an envelope's mask words share the B / E slots), and of the alignment kernel (AL_NARR)
 constexpr int kScoreSpecArrays = 6;
+// ... and how the default scoring object lays that block out: 0 six arrays, 1 one 6-word record per row (SpecAt, wh_device.h; the
+// Makefile hands the same K7_LAYOUT to the object and to the host).  The sizes are the same either way.
+#ifndef WH_K7_LAYOUT
+#define WH_K7_LAYOUT 1
+#endif
+constexpr int kScoreSpecLayout = WH_K7_LAYOUT;
 constexpr int kAlignSpecRows = 14;
 constexpr int kMaxPlanLength = 1 << 24;                                    // the length searches below end here
 

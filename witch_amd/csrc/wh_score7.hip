@@ -50,6 +50,27 @@ constexpr bool kSlim = false;
 constexpr int kSpML = SP_ML, kSpMH = SP_MH, kSpArr = SP_NARR;
 #endif
 constexpr bool kMaskedAcc = true;   // P4: only lanes that own a stored Forward block accumulate
+// WH_SPEC_ROWS=1: the per-wave LDS block holds one 6-word record per row instead of six arrays (SpecAt, wh_device.h), and the
+// window sweeps load each record once.  WH_UNI=1: the envelope sweeps know at compile time that their length model is unihit.
+// Both are the default of the scoring object itself and apply to its LDS instantiations only: the long-query sweeps (SG, rows
+// in HBM) and the objects that compile this file for its sweeps (wh_score9.hip, wh_staged.hip: WH_SWEEPS_ONLY) keep the arrays
+// and the run-time length model, and so does the A/B slot (K7B_FLAGS in the Makefile sets both to 0).
+#if defined(WH_SWEEPS_ONLY) || !defined(WH_SLIM_SPEC)
+#define WH_K7_NEW_DEFAULT 0
+#else
+#define WH_K7_NEW_DEFAULT 1
+#endif
+#ifndef WH_SPEC_ROWS
+#define WH_SPEC_ROWS WH_K7_NEW_DEFAULT
+#endif
+#ifndef WH_UNI
+#define WH_UNI WH_K7_NEW_DEFAULT
+#endif
+constexpr int kLayout = WH_SPEC_ROWS ? SPEC_ROWS : SPEC_SOA;
+constexpr bool kUni = WH_UNI != 0;
+static_assert(kLayout == SPEC_SOA || kSlim, "a row record has six words (WH_SLIM_SPEC)");
+template <bool SG> using SpecOf = SpecAt<SG ? (int)SPEC_SOA : kLayout>;
+constexpr int kSpecTag = kSpArr | (kLayout << 8);      // what ScoreArgs::spec_arrays must say for this object
 
 // log() / exp() in double, out of line: inlined, each call site left its polynomial's constants in registers that the kernel then
 // kept alive across every sweep of a pair (the same instructions either way)
@@ -100,6 +121,11 @@ __device__ __forceinline__ int64_t uniform_i64(int64_t v) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
   return (int64_t)(((unsigned long long)hi << 32) | lo);
 }
+// A sweep that knows its length model to be unihit (WH_UNI) still READS all four words of it, once: with two words read
+// the compiler hands them over as scalars instead of the 16-byte struct, the call no longer refers to the caller's frame and becomes
+// a tail-call candidate, and a function with such a call site saves every callee-saved register it touches (the
+// full-width sweep 0 -> 72..312 B of scratch, the 512-node window 40 -> 292 B: the caps of tests/test_kernel_resources.py).
+__device__ __forceinline__ void touch_len_config(const LenCfg &cfg) { asm volatile("" :: "v"(cfg.EJ), "v"(cfg.EC)); }
 struct P4Out { float mass, domcorr; };
 struct RegOut { int nenv, nreg, flags; };   // flags: WH_FLAG_* | multidomain mask of the stored regions << 8 (12 bytes: stays in return registers)
 
@@ -110,6 +136,7 @@ __device__ __forceinline__ FwdOut uniform_fwd(FwdOut o) { return FwdOut{uniform_
 // ---------------------------------------------------------------- P1 / P3
 // (the sweep without STORE is the multihit one, P1: it also leaves the dominant-path mask in n2tab[30..31] for P2's window)
 constexpr int kUmSlot = 30;
+// (STORE: an envelope's sweep - every caller passes the unihit length model, which WH_UNI builds into the sweep)
 template <int Q, bool STORE, int TH, bool SG>
 __device__ __noinline__ FwdOut sweep_forward(const WaveCtx c, lds_u8 *seq3, int L, LenCfg cfg, float keep_scale, int keep_lanes = 63 << 8) {
   const uint8_t *seq = (const uint8_t *)seq3;
@@ -118,8 +145,9 @@ __device__ __noinline__ FwdOut sweep_forward(const WaveCtx c, lds_u8 *seq3, int 
   const ScanC sc = scan_prepare(lane_product<Q, false>(T, FW_D2));
   FwdOut o;
   constexpr bool UM = !STORE && !SG && Q >= 8;
+  if (STORE && kUni && !SG) touch_len_config(cfg);
   o.nst = 0;
-  forward_sweep<Q, false, STORE, (Q <= kMaxQP), kSlim, UM, STORE, !SG>(T, sc, (const float *)c.emL, (const float *)c.emG, ctxKlds(c), seq, L, cfg, SG ? (float *)c.specg : (float *)c.spec, c.SP, (float *)c.Fs, keep_scale, c.lane, o.xC, o.ef,
+  forward_sweep<Q, false, STORE, (Q <= kMaxQP), kSlim, UM, STORE, !SG, (STORE && kUni && !SG), (SG ? (int)SPEC_SOA : kLayout)>(T, sc, (const float *)c.emL, (const float *)c.emG, ctxKlds(c), seq, L, cfg, SG ? (float *)c.specg : (float *)c.spec, c.SP, (float *)c.Fs, keep_scale, c.lane, o.xC, o.ef,
                                                                   reinterpret_cast<unsigned *>((float *)c.n2tab) + kUmSlot, &o.nst, keep_lanes);
   if (SG) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the rows were written by lane 0, every lane reads them next
   return o;
@@ -135,6 +163,7 @@ __device__ __noinline__ void sweep_backward_decode(const WaveCtx c, lds_u8 *seq3
   T.load(nullptr, (const float *)c.bwL, c.lane);
   const ScanC sc = scan_prepare(lane_product<Q, false>(T, BW_DD));
   const int lane = c.lane, SP = c.SP;
+  const SpecOf<SG> at{SP};
   float *spec = SG ? (float *)c.specg : (float *)c.spec;
   // long-query mode: L1-bypassing loads (the slots are rewritten for every pair)
   auto ldf = [&](int idx) -> float { return SG ? __builtin_nontemporal_load(spec + idx) : spec[idx]; };
@@ -179,22 +208,22 @@ __device__ __noinline__ void sweep_backward_decode(const WaveCtx c, lds_u8 *seq3
       xB *= r; xJ *= r; xC *= r; xN *= r; xE *= r;
       eb += e;
     }
-    const float s_i = ldexpf(invZ, (SG ? R.s(0, i) : ldi(SP_S * SP + i)) + eb - ef_L);
-    const float pe = (SG ? R.f(2, i) : ldf(SP_E * SP + i)) * xE * s_i;
-    const float pb = (SG ? R.f(3, i) : ldf(SP_B * SP + i)) * xB * s_i;
+    const float s_i = ldexpf(invZ, (SG ? R.s(0, i) : ldi(at(SP_S, i))) + eb - ef_L);
+    const float pe = (SG ? R.f(2, i) : ldf(at(SP_E, i))) * xE * s_i;
+    const float pb = (SG ? R.f(3, i) : ldf(at(SP_B, i))) * xB * s_i;
     float njc = 0.f;
     if (i >= 1) {
-      const float s_p = ldexpf(invZ, (SG ? R.s(1, i) : ldi(SP_S * SP + i - 1)) + eb - ef_L);
-      njc = (SG ? R.f(4, i) : ldf(SP_N * SP + i - 1)) * xN;
-      njc = fmaf(SG ? R.f(5, i) : ldf(SP_J * SP + i - 1), xJ, njc);
-      njc = fmaf(SG ? R.f(6, i) : ldf(SP_C * SP + i - 1), xC, njc);
+      const float s_p = ldexpf(invZ, (SG ? R.s(1, i) : ldi(at(SP_S, i, 1))) + eb - ef_L);
+      njc = (SG ? R.f(4, i) : ldf(at(SP_N, i, 1))) * xN;
+      njc = fmaf(SG ? R.f(5, i) : ldf(at(SP_J, i, 1)), xJ, njc);
+      njc = fmaf(SG ? R.f(6, i) : ldf(at(SP_C, i, 1)), xC, njc);
       njc = njc * cm.loop * s_p;
     }
     if (SG) {
       if (lane == R.top - i) { wE = pe; wB = pb; wN = njc; }
     } else {
       __builtin_amdgcn_wave_barrier();
-      if (lane == 0) { spec[SP_E * SP + i] = pe; spec[SP_B * SP + i] = pb; spec[SP_N * SP + i] = njc; }
+      if (lane == 0) { spec[at(SP_E, i)] = pe; spec[at(SP_B, i)] = pb; spec[at(SP_N, i)] = njc; }
       __builtin_amdgcn_wave_barrier();
     }
   }
@@ -212,6 +241,12 @@ __device__ __noinline__ P4Out sweep_backward_null2(const WaveCtx c, lds_u8 *eseq
   T.load(nullptr, (const float *)c.bwL, c.lane);
   const ScanC sc = scan_prepare(lane_product<Q, false>(T, BW_DD));
   const int lane = c.lane, SP = c.SP;
+  const SpecOf<SG> at{SP};
+  // WH_UNI: the envelope's Forward sweep stored no J row, so none is read: J_F is the constant 0 it always held.  The J STATE stays in
+  // this sweep (the window sweeps drop it): without it the register allocation of the 12-cell class's sweep changes such that the
+  // kernel around it keeps 64 B more per lane in scratch, past its cap (tests/test_kernel_resources.py), and the full-width sweep
+  // runs for 2 % of the envelopes.
+  constexpr bool NOJ = kUni && !SG;
   const float *spec = SG ? (const float *)c.specg : (const float *)c.spec;
   auto ldf = [&](int idx) -> float { return SG ? __builtin_nontemporal_load(spec + idx) : spec[idx]; };
   auto ldi = [&](int idx) -> int { return SG ? __builtin_nontemporal_load(reinterpret_cast<const int *>(spec) + idx) : reinterpret_cast<const int *>(spec)[idx]; };
@@ -230,7 +265,7 @@ __device__ __noinline__ P4Out sweep_backward_null2(const WaveCtx c, lds_u8 *eseq
   for (int i = Ld; i >= 1; i--) {
     asm volatile("" ::: "memory");
     if (SG && R.spent(i)) R.load(spec, r_off, r_sh, i, lane);
-    auto mask_word = [&]() -> unsigned { return SG ? (src < 32 ? R.u(0, i) : R.u(1, i)) : (src < 32 ? ldu(kSpML * SP + i) : ldu(kSpMH * SP + i)); };
+    auto mask_word = [&]() -> unsigned { return SG ? (src < 32 ? R.u(0, i) : R.u(1, i)) : (src < 32 ? ldu(at(kSpML, i)) : ldu(at(kSpMH, i))); };
     // Forward row i: with three or more waves per SIMD the other waves cover the HBM latency,
     // so the row is requested only after the cell update (TH >= 768; saves 2*Q registers
     // across backward_cells); with two waves it is requested first.
@@ -252,8 +287,8 @@ __device__ __noinline__ P4Out sweep_backward_null2(const WaveCtx c, lds_u8 *eseq
     };
     if (TH < 768) request_row();
     // mirrored scaling (wh_device.h, "envelope Backward scaling")
-    const int S_i = SG ? R.s(2, i) : ldi(SP_S * SP + i);
-    const int dS = S_i - (SG ? R.s(3, i) : ldi(SP_S * SP + i - 1));      // Forward rescale at row i (>= 0)
+    const int S_i = SG ? R.s(2, i) : ldi(at(SP_S, i));
+    const int dS = S_i - (SG ? R.s(3, i) : ldi(at(SP_S, i, 1)));      // Forward rescale at row i (>= 0)
     if (i < Ld) {
       mirror_scale<Q>(S_next - S_i, Mb, Ib, xJ, xC, xN);
       xB = wave_sum(backward_emit<Q, false>(T, emL, (const float *)c.emG, eseq[i], ctxKlds(c), lane, Mb));
@@ -301,9 +336,9 @@ __device__ __noinline__ P4Out sweep_backward_null2(const WaveCtx c, lds_u8 *eseq
       }
       fIs = fmaf(idot, s_i, fIs);
     }
-    float nj = (SG ? R.f(4, i) : ldf(SP_N * SP + i - 1)) * xN;
-    nj = fmaf(SG ? R.f(5, i) : ldf(SP_J * SP + i - 1), xJ, nj);
-    nj = fmaf(SG ? R.f(6, i) : ldf(SP_C * SP + i - 1), xC, nj);
+    float nj = (SG ? R.f(4, i) : ldf(at(SP_N, i, 1))) * xN;
+    nj = fmaf(SG ? R.f(5, i) : NOJ ? 0.f : ldf(at(SP_J, i, 1)), xJ, nj);
+    nj = fmaf(SG ? R.f(6, i) : ldf(at(SP_C, i, 1)), xC, nj);
     S_next = S_i;
     xfac = fmaf(nj * cu.loop, s_p, xfac);
   }
@@ -367,6 +402,10 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c, lds_u8 *
   constexpr int Q4 = Q / 4, B4 = QB / 4;
   const uint8_t *eseq = (const uint8_t *)eseq3;
   const int lane = c.lane, SP = c.SP, Klds = ctxKlds(c);
+  const SpecOf<SG> at{SP};
+  constexpr bool UNI = kUni && !SG;                               // no J state, no J row (forward_sweep's UNI wrote none)
+  if (UNI) touch_len_config(cu);
+  constexpr bool CARRY = !SG && kLayout == SPEC_ROWS;              // record i - 1 is read once per row, all of it at the row's start
   const float *spec = SG ? (const float *)c.specg : (const float *)c.spec;
   auto ldf = [&](int idx) -> float { return SG ? __builtin_nontemporal_load(spec + idx) : spec[idx]; };
   auto ldi = [&](int idx) -> int { return SG ? __builtin_nontemporal_load(reinterpret_cast<const int *>(spec) + idx) : reinterpret_cast<const int *>(spec)[idx]; };
@@ -409,7 +448,7 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c, lds_u8 *
   if (SG) R.load(spec, r_off, r_sh, Ld, lane);
   auto request_row = [&](int r, bool first) {
     const unsigned mword = SG ? (first ? (lanef < 32 ? ldu(kSpML * SP + r) : ldu(kSpMH * SP + r)) : (lanef < 32 ? R.u(0, r + 1) : R.u(1, r + 1)))
-                              : (lanef < 32 ? ldu(kSpML * SP + r) : ldu(kSpMH * SP + r));
+                              : (lanef < 32 ? ldu(at(kSpML, r)) : ldu(at(kSpMH, r)));
     have_n = (mword >> (lanef & 31)) & 1u;
     if (have_n) {
       const float4 *row = reinterpret_cast<const float4 *>((const float *)c.Fs) + (size_t)r * (2 * Q4 * kWave);
@@ -418,6 +457,9 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c, lds_u8 *
     }
   };
   request_row(Ld, true);
+  // CARRY: the words of record i - 1 are loaded together where row i begins - beside its mask word, which the row request
+  // reads there anyway - and its scale exponent is row i - 1's own one iteration later: one LDS round trip per row, not six
+  int S_row = CARRY ? ldi(at(SP_S, Ld)) : 0;
 #pragma unroll 1
   for (int i = Ld; i >= 1; i--) {
     asm volatile("" ::: "memory");
@@ -427,10 +469,16 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c, lds_u8 *
     for (int p4 = 0; p4 < B4; p4++) { fm_c[p4] = fm_n[p4]; fi_c[p4] = fi_n[p4]; }
     const bool have = have_n;
     if (i > 1) request_row(i - 1, false);
-    const int S_i = SG ? R.s(2, i) : ldi(SP_S * SP + i);
-    const int dS = S_i - (SG ? R.s(3, i) : ldi(SP_S * SP + i - 1));
+    int S_p = 0;
+    float N_p = 0.f, J_p = 0.f, C_p = 0.f;
+    if (CARRY) {
+      S_p = ldi(at(SP_S, i, 1)); N_p = ldf(at(SP_N, i, 1)); C_p = ldf(at(SP_C, i, 1));
+      if (!UNI) J_p = ldf(at(SP_J, i, 1));
+    }
+    const int S_i = CARRY ? S_row : SG ? R.s(2, i) : ldi(at(SP_S, i));
+    const int dS = S_i - (CARRY ? S_p : SG ? R.s(3, i) : ldi(at(SP_S, i, 1)));
     if (i < Ld) {
-      mirror_scale<QB>(S_next - S_i, Mb, Ib, xJ, xC, xN);
+      if (UNI) mirror_scale<QB>(S_next - S_i, Mb, Ib, xC, xN); else mirror_scale<QB>(S_next - S_i, Mb, Ib, xJ, xC, xN);
       const int x = __builtin_amdgcn_readfirstlane((int)eseq[i]);
       float part = 0.f;
       // the consumer sits inside each branch: a value live across the merge would be one flat load (wh_device.h)
@@ -448,13 +496,13 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c, lds_u8 *
       if (x < Klds) emit([&](int p4) { return em4L[x * (Q * 16) + fwd[p4]]; });
       else emit([&](int p4) { return em4G[(size_t)x * (Q * 16) + fwd[p4]]; });
       xB = wave_sum(part);
-      xJ = fmaf(xJ, cu.loop, xB * cu.move);
+      if (!UNI) xJ = fmaf(xJ, cu.loop, xB * cu.move);
       xC = xC * cu.loop;
       xN = fmaf(xN, cu.loop, xB * cu.move);
     }
-    const float xE = fmaf(xC, cu.EC, xJ * cu.EJ);
+    const float xE = UNI ? xC : fmaf(xC, cu.EC, xJ * cu.EJ);
     backward_cells<QB, true, false>(T, sc, Mb, Ib, xE);
-    clamp_backward<QB>(Mb, Ib, xB, xJ, xC, xN);
+    if (UNI) clamp_backward<QB>(Mb, Ib, xB, xC, xN); else clamp_backward<QB>(Mb, Ib, xB, xJ, xC, xN);
     const float s_i = invZe;
     const float s_p = ldexpf(invZe, -dS);
     if (have) {
@@ -472,10 +520,11 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c, lds_u8 *
       }
       fIs = fmaf(idot, s_i, fIs);
     }
-    float nj = (SG ? R.f(4, i) : ldf(SP_N * SP + i - 1)) * xN;
-    nj = fmaf(SG ? R.f(5, i) : ldf(SP_J * SP + i - 1), xJ, nj);
-    nj = fmaf(SG ? R.f(6, i) : ldf(SP_C * SP + i - 1), xC, nj);
+    float nj = (CARRY ? N_p : SG ? R.f(4, i) : ldf(at(SP_N, i, 1))) * xN;
+    if (!UNI) nj = fmaf(CARRY ? J_p : SG ? R.f(5, i) : ldf(at(SP_J, i, 1)), xJ, nj);
+    nj = fmaf(CARRY ? C_p : SG ? R.f(6, i) : ldf(at(SP_C, i, 1)), xC, nj);
     S_next = S_i;
+    if (CARRY) S_row = S_p;
     xfac = fmaf(nj * cu.loop, s_p, xfac);
   }
   float sm = 0.f;
@@ -654,13 +703,13 @@ __device__ __noinline__ void sweep_backward_null2_quad(const WaveCtx c, lds_i *s
         if (x < Klds) emit([&](int p4) { return em4L[x * (Q * 16) + (3 - p4) * kWave + lanef]; });
         else emit([&](int p4) { return em4G[(size_t)x * (Q * 16) + (3 - p4) * kWave + lanef]; });
         xB = row_sum(part);
-        xJ = fmaf(xJ, cu.loop, xB * cu.move);
+        if (!kUni) xJ = fmaf(xJ, cu.loop, xB * cu.move);
         xC = xC * cu.loop;
         xN = fmaf(xN, cu.loop, xB * cu.move);
       }
-      const float xE = fmaf(xC, cu.EC, xJ * cu.EJ);
+      const float xE = kUni ? xC : fmaf(xC, cu.EC, xJ * cu.EJ);
       backward_cells_row(T, sc, Mb, Ib, xE);
-      clamp_backward<16>(Mb, Ib, xB, xJ, xC, xN);
+      if (kUni) clamp_backward<16>(Mb, Ib, xB, xC, xN); else clamp_backward<16>(Mb, Ib, xB, xJ, xC, xN);
       const float s_i = invZe;
       const float s_p = ldexpf(invZe, S_p - S_i);       // the Forward rescale between rows i-1 and i
       if ((w_i >> (lanef & 31)) & 1u) {                 // the Forward sweep stored my lane block on this row
@@ -678,13 +727,13 @@ __device__ __noinline__ void sweep_backward_null2_quad(const WaveCtx c, lds_i *s
         fIs = fmaf(idot, s_i, fIs);
       }
       float nj = n_p * xN;
-      nj = fmaf(j_p, xJ, nj);
+      if (!kUni) nj = fmaf(j_p, xJ, nj);      // (WH_UNI: the envelope's Forward sweep stored no J row - the copy holds stale words there)
       nj = fmaf(c_p, xC, nj);
       xfac = fmaf(nj * cu.loop, s_p, xfac);
       // the Forward rescale between this row and the next one down, applied to the carried state NOW (the window sweep
       // applies it at the top of the next row: the same exact power of two on the same values, but here no row begins by
       // waiting for a scale exponent that was requested a moment ago)
-      mirror_scale<16>(S_i - S_p, Mb, Ib, xJ, xC, xN);
+      if (kUni) mirror_scale<16>(S_i - S_p, Mb, Ib, xC, xN); else mirror_scale<16>(S_i - S_p, Mb, Ib, xJ, xC, xN);
     }
     // (uniform) the next step's row, for every lane
     if (j + 1 < Lmax) {
@@ -769,9 +818,11 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c, lds_u8
   constexpr int Q4 = Q / 4, B4 = QB / 4;
   const uint8_t *seq = (const uint8_t *)seq3;
   const int lane = c.lane, SP = c.SP, Klds = ctxKlds(c);
+  const SpecAt<kLayout> at{SP};
+  constexpr bool CARRY = kLayout == SPEC_ROWS;          // record i - 1 is read once per row; its E, B and scale words wait a row for their turn
   const float *spec = (const float *)c.spec;
-  float *tmp = (float *)c.spec + kSpArr * SP;          // [0] pe, [1] pb, [2] njc rows of the window sweep
-  float *tE = INPL ? (float *)c.spec + SP_E * SP : tmp, *tB = INPL ? (float *)c.spec + SP_B * SP : tmp + SP, *tN = INPL ? (float *)c.spec + SP_N * SP : tmp + 2 * SP;
+  float *tmp = (float *)c.spec + kSpArr * SP;          // [0] pe, [1] pb, [2] njc rows of the window sweep (three arrays in either layout)
+  float *specw = (float *)c.spec;
   glb_f *gE = c.specg, *gB = c.specg + SP, *gN = c.specg + 2 * SP;
   const int *speci = reinterpret_cast<const int *>(spec);
   int fwd[B4];
@@ -797,9 +848,23 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c, lds_u8
   float xC = cm.move, xJ = 0.f, xN = 0.f, xB = 0.f;
   int eb = 0;
   float ratio = 0.f;
+  int S_row = 0;
+  float E_row = 0.f, B_row = 0.f;                        // CARRY: record i's words, loaded one iteration ago
+  if (CARRY) { S_row = speci[at(SP_S, L)]; E_row = spec[at(SP_E, L)]; B_row = spec[at(SP_B, L)]; }
 #pragma unroll 1
   for (int i = L; i >= 0; i--) {
     asm volatile("" ::: "memory");
+    // (the loads that define the carried words: nothing else is assigned to them, so no copy waits for a load at the loop's edge)
+    const int S_i = CARRY ? S_row : 0;
+    const float E_i = CARRY ? E_row : 0.f, B_i = CARRY ? B_row : 0.f;
+    int S_p = 0;
+    float N_p = 0.f, J_p = 0.f, C_p = 0.f;
+    if (CARRY) {
+      const int ip = i >= 1 ? i - 1 : 0;                 // (row 0 reads its own record: N(0) for the window's share, the rest unused)
+      S_p = speci[at(SP_S, ip)]; N_p = spec[at(SP_N, ip)]; J_p = spec[at(SP_J, ip)]; C_p = spec[at(SP_C, ip)];
+      E_row = spec[at(SP_E, ip)]; B_row = spec[at(SP_B, ip)];
+      S_row = S_p;
+    }
     if (i < L) {
       const int x = __builtin_amdgcn_readfirstlane((int)seq[i]);
       float part = 0.f;
@@ -832,22 +897,25 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c, lds_u8
       xB *= r; xJ *= r; xC *= r; xN *= r; xE *= r;
       eb += e;
     }
-    const float s_i = ldexpf(invZ, speci[SP_S * SP + i] + eb - ef_L);
-    const float pe = spec[SP_E * SP + i] * xE * s_i;
-    const float pb = spec[SP_B * SP + i] * xB * s_i;
+    const float s_i = ldexpf(invZ, (CARRY ? S_i : speci[at(SP_S, i)]) + eb - ef_L);
+    const float pe = (CARRY ? E_i : spec[at(SP_E, i)]) * xE * s_i;
+    const float pb = (CARRY ? B_i : spec[at(SP_B, i)]) * xB * s_i;
     float njc = 0.f;
     if (i >= 1) {
-      const float s_p = ldexpf(invZ, speci[SP_S * SP + i - 1] + eb - ef_L);
-      njc = spec[SP_N * SP + i - 1] * xN;
-      njc = fmaf(spec[SP_J * SP + i - 1], xJ, njc);
-      njc = fmaf(spec[SP_C * SP + i - 1], xC, njc);
+      const float s_p = ldexpf(invZ, (CARRY ? S_p : speci[at(SP_S, i, 1)]) + eb - ef_L);
+      njc = (CARRY ? N_p : spec[at(SP_N, i, 1)]) * xN;
+      njc = fmaf(CARRY ? J_p : spec[at(SP_J, i, 1)], xJ, njc);
+      njc = fmaf(CARRY ? C_p : spec[at(SP_C, i, 1)], xC, njc);
       njc = njc * cm.loop * s_p;
     } else {
-      ratio = spec[SP_N * SP] * xN * s_i;               // N_F(0) N_B(0) / Z: the share of the paths that stay inside the window
+      ratio = (CARRY ? N_p : spec[at(SP_N, 0)]) * xN * s_i;               // N_F(0) N_B(0) / Z: the share of the paths that stay inside the window
     }
     __builtin_amdgcn_wave_barrier();
     if (TMPG) { if (lane == 0) { gE[i] = pe; gB[i] = pb; gN[i] = njc; } }
-    else if (lane == 0) { tE[i] = pe; tB[i] = pb; tN[i] = njc; }
+    else if (lane == 0) {
+      if (INPL) { specw[at(SP_E, i)] = pe; specw[at(SP_B, i)] = pb; specw[at(SP_N, i)] = njc; }
+      else { tmp[i] = pe; tmp[SP + i] = pb; tmp[2 * SP + i] = njc; }
+    }
     __builtin_amdgcn_wave_barrier();
   }
   WinDec o;
@@ -862,7 +930,15 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c, lds_u8
 template <int TH, bool INPL = false, bool TMPG = false>
 __device__ __noinline__ RegOut region_scan_cert(lds_f *spec3, int SP, int L, lds_i *regs3, int lane, float eps, glb_f *tmpg = nullptr) {
   float *tmp = TMPG ? (float *)tmpg : (float *)spec3 + kSpArr * SP;
-  float *tE = INPL ? (float *)spec3 + SP_E * SP : tmp, *tB = INPL ? (float *)spec3 + SP_B * SP : tmp + SP, *tN = INPL ? (float *)spec3 + SP_N * SP : tmp + 2 * SP;
+  // word <row> of the three posterior rows: INPL the E, B and N words of the wave's block (stride-6 column reads where the block
+  // holds records), else three arrays of their own
+  const SpecAt<kLayout> at{SP};
+  struct Col {
+    float *base; int field; SpecAt<kLayout> at;
+    __device__ __forceinline__ float *operator+(int row) const { return INPL ? base + at(field, row) : base + row; }
+    __device__ __forceinline__ operator float *() const { return *this + 0; }
+  };
+  const Col tE{INPL ? (float *)spec3 : tmp, SP_E, at}, tB{INPL ? (float *)spec3 : tmp + SP, SP_B, at}, tN{INPL ? (float *)spec3 : tmp + 2 * SP, SP_N, at};
   if (TMPG) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");       // the rows were stored by lane 0, every lane reads them next
   int *regs = (int *)regs3;
   const float rt1 = 0.25f, rt2 = 0.10f, rt3 = 0.20f;
@@ -882,7 +958,7 @@ __device__ __noinline__ RegOut region_scan_cert(lds_f *spec3, int SP, int L, lds
     const int jj = j0 + lane;
     const bool valid = jj <= L;
     const float nv = valid ? ldt(tN + jj) : 0.f;
-    const float bv = valid ? (jj - 1 == 0 ? pb0 : ldt(tB + jj - 1)) : 0.f;
+    const float bv = valid ? (jj - 1 == 0 ? pb0 : ldt(tB + (jj - 1))) : 0.f;
     const float ev = valid ? ldt(tE + jj) : 0.f;
     float jout = 0.f, cout = 0.f;
     const int cnt = L - j0 + 1 < kWave ? L - j0 + 1 : kWave;
@@ -924,9 +1000,9 @@ __device__ __noinline__ RegOut region_scan_cert(lds_f *spec3, int SP, int L, lds
   for (int e = 0; e < nenv; e++) {
     const int ri = regs[2 * e], rj = regs[2 * e + 1];
     float mx = -1.0f;
-    const float e0 = ldt(tE + ri - 1), bj = ldt(tN + rj);
+    const float e0 = ldt(tE + (ri - 1)), bj = ldt(tN + rj);
     for (int z = ri + lane; z <= rj; z += kWave) {
-      const float u = ldt(tE + z) - e0, v = bj - ldt(tN + z - 1);
+      const float u = ldt(tE + z) - e0, v = bj - ldt(tN + (z - 1));
       mx = fmaxf(mx, fminf(u, v));
     }
     mx = wave_max(mx);
@@ -949,7 +1025,8 @@ __device__ __noinline__ RegOut region_scan(lds_f *spec3, glb_f *specg, int SP, i
   int nenv = 0, nreg = 0, flags = 0;
   // 64 rows per fetch, walked with v_readlane (wh_device.h): in HBM mode one round trip per 64 rows, in LDS mode no
   // ds_read latency inside the serial recurrence; the sums are formed in the row-by-row order either way
-  region_scan_global(spec, SP, L, regs, lane, nenv, nreg, flags);
+  const SpecOf<SG> at{SP};
+  region_scan_global<(SG ? (int)SPEC_SOA : kLayout)>(spec, SP, L, regs, lane, nenv, nreg, flags);
   __builtin_amdgcn_wave_barrier();
   if (SG) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   // multidomain test: max_z min(etot[z]-etot[i-1], btot[j]-btot[z-1]) >= rt3
@@ -957,9 +1034,9 @@ __device__ __noinline__ RegOut region_scan(lds_f *spec3, glb_f *specg, int SP, i
   for (int e = 0; e < nenv; e++) {
     const int ri = regs[2 * e], rj = regs[2 * e + 1];
     float mx = -1.0f;
-    const float e0 = ldf(SP_C * SP + ri - 1), bj = ldf(SP_J * SP + rj);
+    const float e0 = ldf(at(SP_C, ri, 1)), bj = ldf(at(SP_J, rj));
     for (int z = ri + lane; z <= rj; z += kWave) {
-      const float u = ldf(SP_C * SP + z) - e0, v = bj - ldf(SP_J * SP + z - 1);
+      const float u = ldf(at(SP_C, z)) - e0, v = bj - ldf(at(SP_J, z, 1));
       mx = fmaxf(mx, fminf(u, v));
     }
     mx = wave_max(mx);
@@ -1012,7 +1089,8 @@ __device__ __forceinline__ P4Out envelope_backward(const ScoreArgs &a, const Wav
       // the node window around the lane blocks the dominant alignment runs through (two blocks in
       // front: the envelope's first ~25 rows set no bit and lie that many nodes ahead; one block behind)
       const unsigned *su = reinterpret_cast<const unsigned *>(SG ? (const float *)c.specg : (const float *)c.spec);
-      unsigned long long um = ((unsigned long long)su[kSpMH * SP] << 32) | su[kSpML * SP];
+      const SpecOf<SG> at{SP};
+      unsigned long long um = ((unsigned long long)su[at.row0(kSpMH)] << 32) | su[at.row0(kSpML)];
       um = mask_in_band(um, band);
       if (um != 0) {
         int lo = __builtin_ctzll(um), hi = 63 - __builtin_clzll(um);
@@ -1220,8 +1298,12 @@ __device__ __forceinline__ RegOut score_regions(const ScoreArgs &a, const WaveCt
         wd.eps = 1.0f;
         if (TMPG && nodes <= (Q % 8 == 0 && Q > 8 ? 8 : 4) * kWave) {
           const float *spec = (const float *)c.spec;
-          for (int arr = 0; arr < kSpArr; arr++)
-            for (int u = lane; u <= L; u += kWave) __builtin_nontemporal_store(spec[arr * SP + u], tmpg + arr * SP + u);
+          if (kLayout == SPEC_ROWS) {
+            for (int u = lane; u < kSpArr * (L + 1); u += kWave) __builtin_nontemporal_store(spec[u], tmpg + u);      // (records 0..L are contiguous)
+          } else {
+            for (int arr = 0; arr < kSpArr; arr++)
+              for (int u = lane; u <= L; u += kWave) __builtin_nontemporal_store(spec[arr * SP + u], tmpg + arr * SP + u);
+          }
           saved = true;
         }
         if (nodes <= 4 * kWave) wd = sweep_backward_decode_win<4, Q, TH, TMPG, false, false>(c, (lds_u8 *)seq, L, cm, 1.0f / (f1.xC * cm.move), f1.ef, min((63 - hi) * Q, kWave * (Q - 4)));
@@ -1249,8 +1331,12 @@ __device__ __forceinline__ RegOut score_regions(const ScoreArgs &a, const WaveCt
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       float *spec = (float *)c.spec;
       __builtin_amdgcn_wave_barrier();
-      for (int arr = 0; arr < kSpArr; arr++)
-        for (int u = lane; u <= L; u += kWave) spec[arr * SP + u] = __builtin_nontemporal_load(tmpg + arr * SP + u);
+      if (kLayout == SPEC_ROWS) {
+        for (int u = lane; u < kSpArr * (L + 1); u += kWave) spec[u] = __builtin_nontemporal_load(tmpg + u);
+      } else {
+        for (int arr = 0; arr < kSpArr; arr++)
+          for (int u = lane; u <= L; u += kWave) spec[arr * SP + u] = __builtin_nontemporal_load(tmpg + arr * SP + u);
+      }
       __builtin_amdgcn_wave_barrier();
     }
     sweep_backward_decode<Q, TH, SG>(c, (lds_u8 *)seq, L, cm, 1.0f / (f1.xC * cm.move), f1.ef);
@@ -1553,7 +1639,8 @@ __global__ __launch_bounds__(TH) void score_kernel7q(ScoreArgs a) {
               bool done = !(f3.xC > 0.f);
               if (!done) {
                 const unsigned *su = reinterpret_cast<const unsigned *>((const float *)c.spec);
-                const unsigned long long um = mask_in_band(((unsigned long long)su[kSpMH * SP] << 32) | su[kSpML * SP], band);
+                const SpecAt<kLayout> at{SP};
+                const unsigned long long um = mask_in_band(((unsigned long long)su[at.row0(kSpMH)] << 32) | su[at.row0(kSpML)], band);
                 int m0 = -1;
                 if (um != 0) {
                   int lo = __builtin_ctzll(um), hi = 63 - __builtin_clzll(um);
@@ -1564,8 +1651,8 @@ __global__ __launch_bounds__(TH) void score_kernel7q(ScoreArgs a) {
                   // the six per-row arrays of this envelope -> the wave's HBM copy t (coalesced), the slot and the record
                   glb_f *dst = specg0 + (size_t)t * spec_stride1;
                   const float *spec = (const float *)c.spec;
-                  for (int arr = 0; arr < kSpArr; arr++)
-                    for (int u = lane; u <= Ld; u += kWave) __builtin_nontemporal_store(spec[arr * SP + u], dst + arr * SP + u);
+                  for (int arr = 0; arr < kSpArr; arr++)      // (the copy is six arrays whatever the block's layout: the quad sweep reads columns)
+                    for (int u = lane; u <= Ld; u += kWave) __builtin_nontemporal_store(spec[at(arr, u)], dst + arr * SP + u);
                   if (lane == 0) {
                     int *sl = qslots + t * QS_INTS;
                     sl[QS_ACTIVE] = 1; sl[QS_LD] = Ld; sl[QS_M0] = m0;
@@ -1650,8 +1737,9 @@ __global__ __launch_bounds__(TH) void score_kernel7q(ScoreArgs a) {
             float *spec = (float *)c.spec;
             const glb_f *src = specg0 + (size_t)t * spec_stride1;
             __builtin_amdgcn_wave_barrier();
+            const SpecAt<kLayout> at{SP};
             for (int arr = 0; arr < kSpArr; arr++)
-              for (int u = lane; u <= Ld; u += kWave) spec[arr * SP + u] = __builtin_nontemporal_load(src + arr * SP + u);
+              for (int u = lane; u <= Ld; u += kWave) spec[at(arr, u)] = __builtin_nontemporal_load(src + arr * SP + u);
             __builtin_amdgcn_wave_barrier();
             c.Fs = Fs0 + (size_t)t * slab1;
             FwdOut f3; f3.xC = __builtin_bit_cast(float, qr[QR_XC3]); f3.ef = qr[QR_EF3];
@@ -1733,7 +1821,7 @@ static hipError_t launch7_q(int Q, const ScoreArgs &a, int blocks, int threads, 
 // four envelopes per Backward sweep (score_kernel7q): models of 16 cells per lane
 hipError_t launch_score7q(int Q, const ScoreArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
   using namespace WH_K7NS;
-  if (a.spec_arrays != kSpArr || !a.spec_scratch || threads > 768) return hipErrorInvalidValue;
+  if (a.spec_arrays != kSpecTag || !a.spec_scratch || threads > 768) return hipErrorInvalidValue;
   if (Q == 16) return launch7q<16, 768>(a, blocks, threads, lds, s);
   return hipErrorInvalidValue;
 }
@@ -1741,7 +1829,7 @@ hipError_t launch_score7q(int Q, const ScoreArgs &a, int blocks, int threads, si
 #ifndef WH_SWEEPS_ONLY
 hipError_t WH_K7LAUNCH(int Q, const ScoreArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
   using namespace WH_K7NS;
-  if (!a.spec_scratch && a.spec_arrays != kSpArr) return hipErrorInvalidValue;   // planner and kernel disagree about the LDS block
+  if (!a.spec_scratch && a.spec_arrays != kSpecTag) return hipErrorInvalidValue;   // planner and kernel disagree about the LDS block: arrays, or their layout
   if (threads <= 512) return launch7_q<512>(Q, a, blocks, threads, lds, s);
   if (threads <= 768) return launch7_q<768>(Q, a, blocks, threads, lds, s);
   return hipErrorInvalidValue;
