@@ -173,6 +173,44 @@ int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets
                  const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
                  const int64_t *d_col_offsets, int32_t *d_cols, void *stream);
 
+/* The same alignment with hmmalign's per-residue confidence (its "#=GR <name> PP" line): pp is CSR by the same
+ * col_offsets as cols, one float per residue - the posterior probability that residue i was emitted by the state the
+ * returned path puts it in: M_k where cols >= 0, else I_k (an insert) or N / C (a flank residue; J cannot occur, the
+ * alignment profile is unihit).  pp == NULL is wh_align / wh_align_dev: same columns, same launches, same workspace.
+ * Nothing outside the pairs' ranges is written.  A pair returned without a path (all columns -1) gets 0 for every
+ * residue; a pair that a later pass of the call aligns again (several-waves -> any-size hand-over, long-query pass)
+ * carries that pass's values.
+ * Precision, by the kernel that aligned the pair:
+ *  - register kernels (models of up to 3 072 nodes) and the several-waves kernel: float32 Forward x Backward / Z, within
+ *    2e-4 + 3e-6 L of a float64 evaluation (measured: 3e-6).  A pair aligned on a node window (wh_last_align_paths)
+ *    carries LOWER BOUNDS: the mass certificate lets a window drop 3e-6 * L (kAlnWinTol * L) of posterior mass in total
+ *    over the pair, so no value is more than that below the full-width one.
+ *  - a pair that leaves float32 range (n_logspace of wh_last_align_status; typically several copies of a long family in
+ *    one query): with pp == NULL it is redone by the float32 log-space pass, whose posteriors - differences of
+ *    logarithms of thousands of nats - are good to a few percent only; they are NOT returned.  A call with pp hands such
+ *    a pair to the float64 any-size kernel instead, like every pair that kernel serves anyway (models beyond 3 072
+ *    nodes, the long-query pass): float64 throughout, in log space where needed, within 5e-16 L^2 of exact (1e-9 for
+ *    the pairs in probability space), rounded to float once at the store: 2^-25 = 3e-8 below 1.  The columns are
+ *    hmmalign's from either kernel.
+ * witch_amd.shim.formats.pp_char turns a value into hmmalign's character. */
+int wh_align_pp(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq,
+                const int64_t *pair_q, const int32_t *pair_h, int64_t npairs,
+                const int64_t *col_offsets, int32_t *cols, float *pp);
+int wh_align_pp_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq,
+                    int64_t total_residues, int32_t max_len,
+                    const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
+                    const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, void *stream);
+/* The same with pp as doubles.  What the float32 kernels return is their float32 value widened; the any-size float64
+ * kernel (models beyond 3 072 nodes, the long-query pass, pairs handed over by the several-waves kernel) returns its
+ * float64 posterior unrounded - a float holds a value below 1 only to 2^-25 = 3e-8. */
+int wh_align_pp64(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq,
+                  const int64_t *pair_q, const int32_t *pair_h, int64_t npairs,
+                  const int64_t *col_offsets, int32_t *cols, double *pp);
+int wh_align_pp64_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq,
+                      int64_t total_residues, int32_t max_len,
+                      const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
+                      const int64_t *d_col_offsets, int32_t *d_cols, double *d_pp, void *stream);
+
 /* Outcome classes of the last wh_align / wh_align_dev call on this handle (the call itself returns WH_OK for
  * them): n_logspace = pairs that left the float range and were redone in log space (same columns as hmmalign's
  * own log-space fallback); n_unaligned = pairs returned with ALL columns -1 where hmmalign (aligner.py:96-142) would

@@ -68,6 +68,10 @@ SYMBOLS = {
     "wh_topk_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P]),
     "wh_align": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
     "wh_align_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, _P, _P]),
+    "wh_align_pp": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),
+    "wh_align_pp_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "wh_align_pp64": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),
+    "wh_align_pp64_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "wh_consensus": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),
     "wh_consensus_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "wh_last_align_status": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, C.c_int64]),

@@ -19,7 +19,26 @@
 #include "wh_align_log.h"
 #include "wh_launch.h"
 
+// The file is compiled twice (Makefile): wh_align.o without the PP output - WH_PP(...) expands to nothing there, so its
+// kernels are compiled from the text a build without the feature has - and wh_align_pp.o (WH_ALIGN_PP=1) with it, launched
+// when AlignArgsPP::pp or pp64 is set.  The log-space pass has no PP instantiation: with PP the pairs it would redo go to the
+// float64 any-size kernel (wh_host_align.hip).
+#ifndef WH_ALIGN_PP
+#define WH_ALIGN_PP 0
+#endif
+#if WH_ALIGN_PP
+#define WH_PP(...) __VA_ARGS__
+#else
+#define WH_PP(...)
+#endif
+
 namespace wh {
+
+#if WH_ALIGN_PP
+using KArgs = AlignArgsPP;
+#else
+using KArgs = AlignArgs;
+#endif
 
 enum { AL_PN = 0, AL_B, AL_E, AL_PJ, AL_PC, AL_S, AL_ML, AL_MH, AL_ON, AL_OB, AL_OE, AL_OJ, AL_OC, AL_WPC, AL_NARR };
 static_assert(AL_NARR == kAlignSpecArrays, "wh_launch.h sizes the special-state rows");
@@ -65,9 +84,12 @@ __device__ __forceinline__ float tab_load(const float *tab, int arr, int k) {
 // A path mostly runs along a diagonal (M -> M): lane t evaluates the choice at cell (i - t, k - t), a ballot finds
 // the first cell whose choice is not M, and the run up to it is consumed at once - one memory round trip per run
 // instead of one per residue.  Same comparisons in the same order: the path is the serial walk's.
-template <bool SPECG, int PJ, int PC, class OA, class TAB, class EST>
-__device__ __forceinline__ void oa_traceback(float *spec, int SP, int L, int M, int lane, int32_t *cols, float tNl, float tNm,
-                                             float tEJ, float tEC, OA oa, TAB tab, EST estate) {
+// <pp> (the object with PP alone): the posterior probability that residue i was emitted by the state the path puts it in -
+// <post(row, 0 / 1, k)> reads the posterior of M_k / I_k, PN / PJ / PC the flank arrays.  The cells of an M -> M run are
+// gathered like its columns: lane t loads the posterior of its own cell.
+template <bool SPECG, WH_PP(int PN,) int PJ, int PC, class OA, class TAB, class EST WH_PP(, class POST)>
+__device__ __forceinline__ void oa_traceback(float *spec, int SP, int L, int M, int lane, int32_t *cols, WH_PP(PPOut pp,) float tNl, float tNm,
+                                             float tEJ, float tEC, OA oa, TAB tab, EST estate WH_PP(, POST post)) {
   enum { stS, stN, stB, stM, stI, stD, stE, stJ, stC };
   int s0 = stC, s1 = stS, i = L, k = 0;
   int guard = 4 * (L + M) + 16;
@@ -107,7 +129,11 @@ __device__ __forceinline__ void oa_traceback(float *spec, int SP, int L, int M, 
         }
         const unsigned long long stop = __ballot(!valid || best != 1);
         const int t = stop ? __builtin_ctzll(stop) : kWave - 1;      // last cell of this run
+#if WH_ALIGN_PP
+        if (valid && lane <= t) { cols[it - 1] = kt - 1; pp.put(it - 1, post(it, 0, kt)); }
+#else
         if (valid && lane <= t) cols[it - 1] = kt - 1;
+#endif
         const int bt = __shfl(best, t);
         s1 = stop == 0 ? stM : bt == 0 ? stB : bt == 1 ? stM : bt == 2 ? stI : stD;
         k -= t + 1; i -= t + 1;
@@ -125,6 +151,7 @@ __device__ __forceinline__ void oa_traceback(float *spec, int SP, int L, int M, 
         const float piv = i > 1 ? oa(i - 1, 1, k) : -INFINITY;
         const float av = gate(tab(FW_MI, k), pmv), bv = gate(tab(FW_II, k), piv);
         s1 = bv > av ? stI : stM;
+        WH_PP(if (lane == 0 && i >= 1) pp.put(i - 1, post(i, 1, k));)     // residue i sits in I_k
         i--;
         break;
       }
@@ -136,7 +163,14 @@ __device__ __forceinline__ void oa_traceback(float *spec, int SP, int L, int M, 
       case stN: s1 = i == 0 ? stS : stN; break;
       default: s1 = stS; break;
     }
+#if WH_ALIGN_PP
+    if ((s1 == stN || s1 == stJ || s1 == stC) && s1 == s0) {     // a flank residue
+      if (lane == 0 && i >= 1) pp.put(i - 1, SPR((s1 == stN ? PN : s1 == stJ ? PJ : PC) * SP + i));
+      i--;
+    }
+#else
     if ((s1 == stN || s1 == stJ || s1 == stC) && s1 == s0) i--;
+#endif
     if (i < 0 || k < 0 || (s1 == stM && (k < 1 || i < 1)) || ((s1 == stC || s1 == stJ) && i < 1)) break;   // defensive
     s0 = s1;
   }
@@ -201,7 +235,7 @@ enum { AW_PN = AL_B, AW_PJ = AL_E, AW_PC = AL_WPC };
 
 // 1: columns written; 0: the window lost mass (or left float32 range), nothing was written
 template <int QB, int Q, bool SPECG>
-__device__ __noinline__ int align_window(const AlnWinCtx c, int32_t *cols, int L, int M, int m0, int Lcap, int Klds, LenCfg cu, float invZ, unsigned long long *wcyc) {
+__device__ __noinline__ int align_window(const AlnWinCtx c, int32_t *cols, WH_PP(PPOut pp,) int L, int M, int m0, int Lcap, int Klds, LenCfg cu, float invZ, unsigned long long *wcyc) {
   long long t_last = wcyc ? (long long)__builtin_readcyclecounter() : 0;
 #define AW_TICK(slot) do { if (wcyc) { const long long t_now = __builtin_readcyclecounter(); if (c.lane == 0) atomicAdd(wcyc + (slot), (unsigned long long)(t_now - t_last)); t_last = t_now; } } while (0)
   static_assert(Q % QB == 0 && QB % 4 == 0, "a window lane must stay inside one forward lane block");
@@ -484,7 +518,19 @@ __device__ __noinline__ int align_window(const AlnWinCtx c, int32_t *cols, int L
       }
       s1 = estate_argmax<QB>(om, odd, n0 + lane * QB, M, k) ? 3 : 5;   // stM : stD
     };
+#if WH_ALIGN_PP
+    // the window's posteriors (compact rows of Wpp, laid out like the OA rows): lower bounds, see above
+    const float *ppf = reinterpret_cast<const float *>(Wpp);
+    auto post = [&](int row, int st, int k) -> float {
+      const int pw = k - 1 - n0;
+      if (pw < 0 || pw >= kWave * QB) return 0.f;
+      const int ln = pw / QB, q = pw % QB;
+      return __builtin_nontemporal_load(ppf + ((size_t)(row * 2 + st) * B4 + q / 4) * (kWave * 4) + ln * 4 + (q % 4));
+    };
+    oa_traceback<SPECG, AW_PN, AW_PJ, AW_PC>(spec, SP, L, M, lane, cols, pp, tNl, tNm, tEJ, tEC, oa, tab, estate, post);
+#else
     oa_traceback<SPECG, AW_PJ, AW_PC>(spec, SP, L, M, lane, cols, tNl, tNm, tEJ, tEC, oa, tab, estate);
+#endif
   }
   AW_TICK(3);
   return 1;
@@ -494,8 +540,8 @@ __device__ __noinline__ int align_window(const AlnWinCtx c, int32_t *cols, int L
 // SWAP (long models, Q > 24): only ONE transition orientation is resident in LDS; the waves of a
 // workgroup run the three sweeps in lockstep and swap the tables between them (see wh_score_big.hip).
 // LOGSP: the fallback pass for pairs that left float32 range (wh_align_log.h).
-template <int Q, bool TREG, bool SPECG, bool SWAP, bool LOGSP = false>
-__global__ __launch_bounds__(SWAP ? 256 : 512) void align_kernel(AlignArgs a) {
+template <int Q, bool TREG, bool SPECG, bool SWAP, bool LOGSP = false WH_PP(, bool PP = true)>
+__global__ __launch_bounds__(SWAP ? 256 : 512) void align_kernel(KArgs a) {
   // all LDS in ONE 16-byte aligned dynamic array: a static __shared__ object in front of it
   // would shift the base by 4 bytes and split every ds_read_b128 (measured: 13x LDS time)
   extern __shared__ __attribute__((aligned(16))) float smem_raw[];
@@ -563,7 +609,9 @@ __global__ __launch_bounds__(SWAP ? 256 : 512) void align_kernel(AlignArgs a) {
       const int64_t off = a.offsets[qi];
       const int L = active ? (int)(a.offsets[qi + 1] - off) : 0;
       int32_t *cols = a.cols + (active ? a.col_offsets[pair] : 0);
+      WH_PP(const PPOut pp(a.pp, a.pp64, active ? a.col_offsets[pair] : 0);)
       for (int t = lane; t < L; t += kWave) cols[t] = -1;
+      WH_PP(for (int t = lane; t < L; t += kWave) pp.put(t, 0.f);)              // a pair returned without a path keeps 0
       if (L <= 0 || L > a.Lcap) active = false;
       for (int t = lane; active && t < L; t += kWave) {
         int c = a.residues[off + t];
@@ -616,10 +664,10 @@ __global__ __launch_bounds__(SWAP ? 256 : 512) void align_kernel(AlignArgs a) {
             if (wcyc && lane == 0) atomicAdd(wcyc, (unsigned long long)(__builtin_readcyclecounter() - t_pair));
             if (nodes <= 4 * kWave) {
               tried = 1;
-              done = align_window<4, Q, SPECG>(c, cols, L, M, min((63 - hi) * Q, kWave * (Q - 4)), a.Lcap, Klds, cu, invZ, wcyc);
+              done = align_window<4, Q, SPECG>(c, cols, WH_PP(pp,) L, M, min((63 - hi) * Q, kWave * (Q - 4)), a.Lcap, Klds, cu, invZ, wcyc);
             } else if (Q % 8 == 0 && Q > 8 && nodes <= 8 * kWave) {
               tried = 1;
-              done = align_window<(Q % 8 == 0 ? 8 : 4), Q, SPECG>(c, cols, L, M, min((63 - hi) * Q, kWave * (Q - 8)), a.Lcap, Klds, cu, invZ, wcyc);
+              done = align_window<(Q % 8 == 0 ? 8 : 4), Q, SPECG>(c, cols, WH_PP(pp,) L, M, min((63 - hi) * Q, kWave * (Q - 8)), a.Lcap, Klds, cu, invZ, wcyc);
             }
           }
           if (a.wstat && lane == 0) atomicAdd(a.wstat + (done ? (nodes_w > 4 * kWave ? 3 : 0) : tried ? 1 : 2), 1);
@@ -826,24 +874,30 @@ __global__ __launch_bounds__(SWAP ? 256 : 512) void align_kernel(AlignArgs a) {
           }
           s1 = estate_argmax<Q>(om, odd, lane * Q, M, k) ? 3 : 5;   // stM : stD
         };
+#if WH_ALIGN_PP
+        auto post = [&](int row, int st, int k) -> float { return cell_load<Q>(slabA, row, 2, st, k); };   // slab A still holds the posteriors
+        oa_traceback<SPECG, AL_PN, AL_PJ, AL_PC>(spec, SP, L, M, lane, cols, pp, tNl, tNm, tEJ, tEC, oa, tab, estate, post);
+#else
         oa_traceback<SPECG, AL_PJ, AL_PC>(spec, SP, L, M, lane, cols, tNl, tNm, tEJ, tEC, oa, tab, estate);
+#endif
       }
     }
   }
 }
 
 template <int Q, bool TREG, bool SPECG, bool SWAP, bool LOGSP = false>
-static hipError_t launch_one(const AlignArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
+static hipError_t launch_one(const AlignArgsPP &a, int blocks, int threads, size_t lds, hipStream_t s) {
   hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&align_kernel<Q, TREG, SPECG, SWAP, LOGSP>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL((align_kernel<Q, TREG, SPECG, SWAP, LOGSP>), dim3(blocks), dim3(threads), lds, s, a);
+  hipLaunchKernelGGL((align_kernel<Q, TREG, SPECG, SWAP, LOGSP>), dim3(blocks), dim3(threads), lds, s, static_cast<const KArgs &>(a));
   return hipGetLastError();
 }
 
+#if !WH_ALIGN_PP
 // log-space pass
 template <bool SPECG>
-static hipError_t launch_align_log_q(int Q, const AlignArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
+static hipError_t launch_align_log_q(int Q, const AlignArgsPP &a, int blocks, int threads, size_t lds, hipStream_t s) {
   switch (Q) {
     case 4:  return launch_one<4, false, SPECG, false, true>(a, blocks, threads, lds, s);
     case 8:  return launch_one<8, false, SPECG, false, true>(a, blocks, threads, lds, s);
@@ -861,9 +915,10 @@ static hipError_t launch_align_log_q(int Q, const AlignArgs &a, int blocks, int 
     default: return hipErrorInvalidValue;
   }
 }
+#endif
 
 template <bool SPECG>
-static hipError_t launch_align_q(int Q, const AlignArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
+static hipError_t launch_align_q(int Q, const AlignArgsPP &a, int blocks, int threads, size_t lds, hipStream_t s) {
   switch (Q) {
     case 4:  return launch_one<4, false, SPECG, false>(a, blocks, threads, lds, s);
     case 8:  return launch_one<8, false, SPECG, false>(a, blocks, threads, lds, s);
@@ -884,11 +939,13 @@ static hipError_t launch_align_q(int Q, const AlignArgs &a, int blocks, int thre
 
 // protein models of 20/24 cells per lane do not fit both orientations beside 20 emission rows:
 // they run the pass-synchronous variant too (16 cells per lane: with a query that leaves no wave beside the tables)
-static hipError_t launch_align_swap_mid(int Q, const AlignArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
+static hipError_t launch_align_swap_mid(int Q, const AlignArgsPP &a, int blocks, int threads, size_t lds, hipStream_t s) {
   if (a.logsp) {
+#if !WH_ALIGN_PP
     if (Q == 16) return launch_one<16, false, true, true, true>(a, blocks, threads, lds, s);
     if (Q == 20) return launch_one<20, false, true, true, true>(a, blocks, threads, lds, s);
     if (Q == 24) return launch_one<24, false, true, true, true>(a, blocks, threads, lds, s);
+#endif
   } else {
     if (Q == 16) return launch_one<16, false, true, true>(a, blocks, threads, lds, s);
     if (Q == 20) return launch_one<20, false, true, true>(a, blocks, threads, lds, s);
@@ -897,9 +954,18 @@ static hipError_t launch_align_swap_mid(int Q, const AlignArgs &a, int blocks, i
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_align(int Q, const AlignArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
+#if WH_ALIGN_PP
+hipError_t launch_align_pp(int Q, const AlignArgsPP &a, int blocks, int threads, size_t lds, hipStream_t s) {
+  if (!a.pp == !a.pp64 || a.logsp) return hipErrorInvalidValue;   // (no log-space pass with PP: see the top of the file)
+#else
+hipError_t launch_align_pp(int Q, const AlignArgsPP &a, int blocks, int threads, size_t lds, hipStream_t s);   // wh_align_pp.o
+hipError_t launch_align(int Q, const AlignArgsPP &a, int blocks, int threads, size_t lds, hipStream_t s) {
+  if (a.pp || a.pp64) return launch_align_pp(Q, a, blocks, threads, lds, s);
+#endif
   if (a.swap && Q <= 24) return launch_align_swap_mid(Q, a, blocks, threads, lds, s);
+#if !WH_ALIGN_PP
   if (a.logsp) return a.spec_scratch ? launch_align_log_q<true>(Q, a, blocks, threads, lds, s) : launch_align_log_q<false>(Q, a, blocks, threads, lds, s);
+#endif
   return a.spec_scratch ? launch_align_q<true>(Q, a, blocks, threads, lds, s) : launch_align_q<false>(Q, a, blocks, threads, lds, s);
 }
 

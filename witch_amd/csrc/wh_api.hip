@@ -56,7 +56,7 @@ void wh_ehmm_free(wh_ehmm *e) {
   if (!e) return;
   for (DevBuf *b : {&e->d_tlist, &e->d_rext, &e->d_biglist, &e->d_bigsegs, &e->d_longlist, &e->d_lqlist, &e->d_gtab, &e->d_rrecs, &e->d_rmx, &e->d_rsegs, &e->d_hmms, &e->d_tables, &e->d_nseq, &e->d_index, &e->d_lists, &e->d_counter, &e->d_scratch, &e->d_ascratch, &e->d_wscratch,
                     &e->s_res, &e->s_off, &e->s_deci, &e->s_flags, &e->s_fwd, &e->s_det, &e->s_idx, &e->s_w,
-                    &e->s_nk, &e->s_nu, &e->s_pq, &e->s_ph, &e->s_co, &e->s_cols, &e->s_pos, &e->d_rkeys, &e->d_rorder, &e->d_rchunks, &e->d_qorder, &e->d_order, &e->d_items, &e->d_recs, &e->d_spec, &e->d_back, &e->d_cwj, &e->d_cwv, &e->d_cwn, &e->d_crow,
+                    &e->s_nk, &e->s_nu, &e->s_pq, &e->s_ph, &e->s_co, &e->s_cols, &e->s_pp, &e->s_pos, &e->d_rkeys, &e->d_rorder, &e->d_rchunks, &e->d_qorder, &e->d_order, &e->d_items, &e->d_recs, &e->d_spec, &e->d_back, &e->d_cwj, &e->d_cwv, &e->d_cwn, &e->d_crow,
                     &e->c_buf[0], &e->c_buf[1], &e->c_buf[2], &e->c_buf[3], &e->c_buf[4], &e->c_buf[5], &e->c_buf[6],
                     &e->c_buf[7], &e->c_buf[8], &e->c_buf[9],
                     &e->d_p2bak, &e->d_st_pairs, &e->d_st_p1spec, &e->d_st_units, &e->d_st_p3spec, &e->d_st_slabs, &e->d_st_cnt})
@@ -530,6 +530,25 @@ int wh_topk(wh_ehmm *e, const int32_t *decibits, const uint8_t *flags, int64_t n
 
 int wh_align(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
              const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols) {
+  return wh_align_pp(e, residues, offsets, nq, pair_q, pair_h, npairs, col_offsets, cols, nullptr);
+}
+
+static int align_host(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
+                      const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols, void *pp, bool pp_is64);
+
+int wh_align_pp(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
+                const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols, float *pp) {
+  return align_host(e, residues, offsets, nq, pair_q, pair_h, npairs, col_offsets, cols, pp, false);
+}
+
+int wh_align_pp64(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
+                  const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols, double *pp) {
+  return align_host(e, residues, offsets, nq, pair_q, pair_h, npairs, col_offsets, cols, pp, true);
+}
+
+static int align_host(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
+                      const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols, void *pp, bool pp_is64) {
+  const size_t ppw = pp_is64 ? sizeof(double) : sizeof(float);
   if (!e || !residues || !offsets || !pair_q || !pair_h || !col_offsets || !cols || nq < 0 || npairs < 0) {
     set_error("wh_align: bad argument");
     return WH_EINVAL;
@@ -544,19 +563,26 @@ int wh_align(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_
   const int64_t ncols = col_offsets[npairs];
   if (e->s_res.ensure((size_t)total + 16) || e->s_off.ensure(sizeof(int64_t) * (size_t)(nq + 1)) ||
       e->s_pq.ensure(sizeof(int64_t) * (size_t)npairs) || e->s_ph.ensure(sizeof(int32_t) * (size_t)npairs) ||
-      e->s_co.ensure(sizeof(int64_t) * (size_t)(npairs + 1)) || e->s_cols.ensure(sizeof(int32_t) * (size_t)ncols + 16))
+      e->s_co.ensure(sizeof(int64_t) * (size_t)(npairs + 1)) || e->s_cols.ensure(sizeof(int32_t) * (size_t)ncols + 16) ||
+      (pp && e->s_pp.ensure(ppw * (size_t)ncols + 16)))
     return WH_ENOMEM;
   HIPCHK(hipMemcpy(e->s_res.p, residues, (size_t)total, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(e->s_off.p, offsets, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(e->s_pq.p, pair_q, sizeof(int64_t) * (size_t)npairs, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(e->s_ph.p, pair_h, sizeof(int32_t) * (size_t)npairs, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(e->s_co.p, col_offsets, sizeof(int64_t) * (size_t)(npairs + 1), hipMemcpyHostToDevice));
-  int rc = wh_align_dev(e, (const uint8_t *)e->s_res.p, (const int64_t *)e->s_off.p, nq, total, max_query_len(offsets, nq),
+  if (pp) HIPCHK(hipMemcpy(e->s_pp.p, pp, ppw * (size_t)ncols, hipMemcpyHostToDevice));   // what lies between the pairs' ranges comes back as given
+  int rc = pp_is64 && pp
+      ? wh_align_pp64_dev(e, (const uint8_t *)e->s_res.p, (const int64_t *)e->s_off.p, nq, total, max_query_len(offsets, nq),
+                          (const int64_t *)e->s_pq.p, (const int32_t *)e->s_ph.p, npairs, (const int64_t *)e->s_co.p,
+                          (int32_t *)e->s_cols.p, (double *)e->s_pp.p, nullptr)
+      : wh_align_pp_dev(e, (const uint8_t *)e->s_res.p, (const int64_t *)e->s_off.p, nq, total, max_query_len(offsets, nq),
                         (const int64_t *)e->s_pq.p, (const int32_t *)e->s_ph.p, npairs, (const int64_t *)e->s_co.p,
-                        (int32_t *)e->s_cols.p, nullptr);
+                        (int32_t *)e->s_cols.p, pp ? (float *)e->s_pp.p : nullptr, nullptr);
   if (rc) return rc;
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpy(cols, e->s_cols.p, sizeof(int32_t) * (size_t)ncols, hipMemcpyDeviceToHost));
+  if (pp) HIPCHK(hipMemcpy(pp, e->s_pp.p, ppw * (size_t)ncols, hipMemcpyDeviceToHost));
   return WH_OK;
 }
 

@@ -89,10 +89,12 @@ __device__ __forceinline__ void store4(double *base, int q0, int lane, const dou
 //           accM/accI[node] += F x B x scale per row (arrays of Q x 64 doubles, zeroed by the caller); returns the
 //           unnormalised flank factor sum_i P(N, J, C emit residue i).
 //   MODE 2: posteriors in place: row i of <fmx> gets (float)ppM / (float)ppI in its state slots 0 / 1, xs gets
-//           ppN, ppJ, ppC per row in slots 0..2.
-template <int MODE>
+//           ppN, ppJ, ppC per row in slots 0..2.  With <ppsave> (wh_align_pp) the UNROUNDED posteriors are kept too: ppM / ppI
+//           of row i in ppsave[i * 2SQ ..] (laid out like a row's state slots 0 / 1), ppN, ppJ, ppC in slots 3..5 of xs.
+template <int MODE, bool PP = false>
 __device__ double gbackward(const GModel &m, const uint8_t *seq, int L, GLen c, const GMx &fmx, double *brow0, double *brow1,
-                            double *xs, double fwdsc, double *accM, double *accI, int lane, double *bwd_out = nullptr) {
+                            double *xs, double fwdsc, double *accM, double *accI, int lane, double *bwd_out = nullptr,
+                            double *ppsave = nullptr) {
   const int Q = m.Q, M = m.M;
   const size_t SQ = (size_t)Q * 64;
   const double *tf = m.tf;
@@ -185,11 +187,13 @@ __device__ double gbackward(const GModel &m, const uint8_t *seq, int L, GLen c, 
           dnext = dv;
           xbsum += mv * oc[u] * te4[u];
           if (MODE == 1) { aM4[u] = aM4[u] + fM4[u] * mv * sc; aI4[u] = aI4[u] + fI4[u] * iv4[u] * sc; }
+          if (MODE == 2 && PP) { aM4[u] = fM4[u] * mv * sc; aI4[u] = fI4[u] * iv4[u] * sc; }
           if (MODE == 2) { fM4[u] = (double)(float)(fM4[u] * mv * sc); fI4[u] = (double)(float)(fI4[u] * iv4[u] * sc); }
         }
         store4(cr, q0, lane, oM4); store4(cr + 2 * SQ, q0, lane, oD4);
         if (MODE == 1) { store4(accM, q0, lane, aM4); store4(accI, q0, lane, aI4); }
         if (MODE == 2) { double *fw = const_cast<double *>(fr); store4(fw, q0, lane, fM4); store4(fw + SQ, q0, lane, fI4); }
+        if (MODE == 2 && PP) { double *sv = ppsave + (size_t)i * 2 * SQ; store4(sv, q0, lane, aM4); store4(sv + SQ, q0, lane, aI4); }
       }
       xbsum_prev = xbsum;
       if (MODE != 0) {
@@ -201,6 +205,7 @@ __device__ double gbackward(const GModel &m, const uint8_t *seq, int L, GLen c, 
         const double pc = __builtin_nontemporal_load(fp + xC) * xCv * c.loop * sc2;
         if (MODE == 1) { xfactor += pn; xfactor += pj; xfactor += pc; }
         if (MODE == 2 && lane == 0) { double *t = xs + (size_t)i * xNSPEC; t[0] = (double)(float)pn; t[1] = (double)(float)pj; t[2] = (double)(float)pc; }
+        if (MODE == 2 && PP && lane == 0) { double *t = xs + (size_t)i * xNSPEC; t[3] = pn; t[4] = pj; t[5] = pc; }
       }
     }
     if (MODE == 0 && lane == 0) { double *t = xs + (size_t)i * xNSPEC; t[xN] = xNv; t[xB] = xBv; t[xE] = xEv; t[xJ] = xJv; t[xC] = xCv; t[xCLS] = ls; }
@@ -291,8 +296,9 @@ __device__ double gforward_log(const GModel &m, const uint8_t *seq, int L, GLen 
 }
 
 // Backward against the kept log Forward rows; posteriors in place like gbackward<2>.  Returns log Z of Backward.
+template <bool PP>
 __device__ double gbackward_log(const GModel &m, const uint8_t *seq, int L, GLen c, const GMx &fmx, double *brow0, double *brow1,
-                                double *xs, double fwd, int lane) {
+                                double *xs, double fwd, int lane, double *ppsave = nullptr) {
   const int Q = m.Q, M = m.M;
   const size_t SQ = (size_t)Q * 64;
   const double *tf = m.tf;
@@ -353,8 +359,10 @@ __device__ double gbackward_log(const GModel &m, const uint8_t *seq, int L, GLen
         dnext = dv;
         xb = lse2(xb, mv + llog(odc[o]) + llog(tf[gE * SQ + o]));
         const double iv = __builtin_nontemporal_load(cr + SQ + o);
-        const float pm = (float)exp(__builtin_nontemporal_load(fr + o) + mv - fwd), pi = (float)exp(__builtin_nontemporal_load(fr + SQ + o) + iv - fwd);
+        const double pmd = exp(__builtin_nontemporal_load(fr + o) + mv - fwd), pid = exp(__builtin_nontemporal_load(fr + SQ + o) + iv - fwd);
+        const float pm = (float)pmd, pi = (float)pid;
         fr[o] = (double)pm; fr[SQ + o] = (double)pi;
+        if (PP) { double *sv = ppsave + (size_t)i * 2 * SQ; sv[o] = pmd; sv[SQ + o] = pid; }
       }
       xb_prev = xb;
       const double *fp = fmx.row(i - 1) + 3 * SQ;
@@ -362,6 +370,7 @@ __device__ double gbackward_log(const GModel &m, const uint8_t *seq, int L, GLen
       const double pj = exp(__builtin_nontemporal_load(fp + xJ) + xJv + lloop - fwd);
       const double pc = exp(__builtin_nontemporal_load(fp + xC) + xCv + lloop - fwd);
       if (lane == 0) { double *t = xs + (size_t)i * xNSPEC; t[0] = (double)(float)pn; t[1] = (double)(float)pj; t[2] = (double)(float)pc; }
+      if (PP && lane == 0) { double *t = xs + (size_t)i * xNSPEC; t[3] = pn; t[4] = pj; t[5] = pc; }
     }
     nN = xNv; nJ = xJv; nC = xCv;
     if (i == 0) bwd = xNv;
@@ -388,6 +397,7 @@ size_t generic_front_doubles(int Lcap, int Qmax) {
 size_t generic_align_doubles(int Lcap, int Qmax) {
   return (size_t)(Lcap + 4) * generic_rowlen(Qmax) + 2 * (size_t)(Lcap + 2) * xNSPEC + 8;
 }
+size_t generic_align_pp_doubles(int Lcap, int Qmax) { return (size_t)(Lcap + 2) * 2 * Qmax * 64; }
 size_t generic_seq_doubles(int Lcap) { return seq_doubles(Lcap); }
 size_t generic_lds_bytes(int Lcap) { return (size_t)(Lcap + 16) + 64 * 4 + kRextInts * WH_MAX_ENVELOPES * 4 + 64; }
 #endif
@@ -603,6 +613,9 @@ __device__ __forceinline__ float gatef(double t, float v) { return t > 0.0 ? v :
 __device__ __forceinline__ float ldf(const double *p) { return (float)__builtin_nontemporal_load(p); }
 }  // namespace
 
+// PP: the instantiation with the per-residue posterior output (GenericAlignArgs::pp); the one without is the kernel a
+// build without the feature has
+template <bool PP>
 __global__ __launch_bounds__(64, 3) void WH_GENERIC_ALIGN(GenericAlignArgs a) {
   extern __shared__ __attribute__((aligned(16))) int lds_raw[];
   const int lane = threadIdx.x;
@@ -632,7 +645,11 @@ __global__ __launch_bounds__(64, 3) void WH_GENERIC_ALIGN(GenericAlignArgs a) {
     const int64_t off = a.offsets[qi];
     const int L = (int)(a.offsets[qi + 1] - off);
     int32_t *cols = a.cols + a.col_off[p];
+    PPOut ppo;                                                               // (a double array is filled without rounding to float)
+    if constexpr (PP) ppo = PPOut(a.pp, a.pp64, a.col_off[p]);
+    double *ppsave = PP ? slab + a.pp_off : nullptr;                        // unrounded ppM / ppI per row: the OA fill below overwrites the rows
     for (int t = lane; t < L; t += 64) cols[t] = -1;
+    if (PP) for (int t = lane; t < L; t += 64) ppo.put(t, 0.0);                 // a pair returned without a path (status 1, 2) keeps 0
     if (L <= 0 || L > a.Lcap) continue;
     for (int t = lane; t < L; t += 64) { const int r = a.residues[off + t]; seq[t] = (uint8_t)(r < a.Kp ? r : a.Kp - 1); }
     if constexpr (LONGQ) wave_mem_sync(); else __builtin_amdgcn_wave_barrier();
@@ -640,13 +657,13 @@ __global__ __launch_bounds__(64, 3) void WH_GENERIC_ALIGN(GenericAlignArgs a) {
     const double fwd = gforward<true>(m, seq, L, c, mx, lane);
     if (!isfinite(fwd)) { if (lane == 0 && a.status) a.status[p] = 1; continue; }
     double bwd = 0.0;
-    (void)gbackward<2>(m, seq, L, c, mx, mx.row(a.Lcap + 2), mx.row(a.Lcap + 3), pps, fwd, nullptr, nullptr, lane, &bwd);
+    (void)gbackward<2, PP>(m, seq, L, c, mx, mx.row(a.Lcap + 2), mx.row(a.Lcap + 3), pps, fwd, nullptr, nullptr, lane, &bwd, ppsave);
     // Two hits thousands of bits apart in ONE unihit alignment leave the range of a scaled double (the flank state
     // that carries the weaker hit underflows against the row's scale): Forward and Backward then disagree, and the
     // pair is redone in log space, as hmmalign does.
     if (!(fabs(fwd - bwd) <= 1e-6 * fabs(fwd) + 1e-3)) {
       const double lf = gforward_log(m, seq, L, c, mx, lane);
-      const double lb = gbackward_log(m, seq, L, c, mx, mx.row(a.Lcap + 2), mx.row(a.Lcap + 3), pps, lf, lane);
+      const double lb = gbackward_log<PP>(m, seq, L, c, mx, mx.row(a.Lcap + 2), mx.row(a.Lcap + 3), pps, lf, lane, ppsave);
       // (3: the two log-space scores disagree as well - never seen.  hmmalign makes no such comparison: it decodes with
       // the Forward score and aligns, and so does this kernel; the class is counted and reported, nothing is dropped)
       if (lane == 0 && a.status) a.status[p] = (fabs(lf - lb) <= 1e-6 * fabs(lf) + 1e-3) ? 4 : 3;
@@ -782,7 +799,12 @@ __global__ __launch_bounds__(64, 3) void WH_GENERIC_ALIGN(GenericAlignArgs a) {
               }
             }
             bestM = wave_max_i(bestM); bestD = wave_min_i(bestD);
-            if (mxv == -INFINITY || (bestM < 0 && bestD == 0x7FFFFFFF)) { guard = 0; s1 = tS; if (lane == 0 && a.status) a.status[p] = 2; break; }
+            if (mxv == -INFINITY || (bestM < 0 && bestD == 0x7FFFFFFF)) {
+              guard = 0; s1 = tS;
+              if (lane == 0 && a.status) a.status[p] = 2;
+              if (PP) { wave_mem_sync(); for (int t = lane; t < L; t += 64) ppo.put(t, 0.0); }   // no path: no PP either (flank residues were written on the way)
+              break;
+            }
             if (bestM >= 0) { k = (bestM & 3) * Qs + (bestM >> 3) + 1; s1 = tM; }
             else { const int pd = bestD - 4; k = (pd & 3) * Qs + (pd >> 3) + 1; s1 = tD; }
             break;
@@ -797,7 +819,7 @@ __global__ __launch_bounds__(64, 3) void WH_GENERIC_ALIGN(GenericAlignArgs a) {
             int best = 0;
             for (int u = 1; u < 4; u++) if (path[u] > path[best]) best = u;
             s1 = best == 0 ? tB : best == 1 ? tM : best == 2 ? tI : tD;
-            if (lane == 0) cols[i - 1] = k - 1;
+            if (lane == 0) { cols[i - 1] = k - 1; if (PP) ppo.put(i - 1, __builtin_nontemporal_load(ppsave + (size_t)i * 2 * SQ + o)); }
             k--; i--;
             break;
           }
@@ -812,6 +834,7 @@ __global__ __launch_bounds__(64, 3) void WH_GENERIC_ALIGN(GenericAlignArgs a) {
             const size_t o = m.at(0, k);
             const float av = gatef(tf[gMI * SQ + o], cell(i - 1, k, 0)), bv = gatef(tf[gII * SQ + o], cell(i - 1, k, 1));
             s1 = bv > av ? tI : tM;
+            if (PP && lane == 0 && i >= 1) ppo.put(i - 1, __builtin_nontemporal_load(ppsave + (size_t)i * 2 * SQ + SQ + o));   // residue i sits in I_k
             i--;
             break;
           }
@@ -824,7 +847,10 @@ __global__ __launch_bounds__(64, 3) void WH_GENERIC_ALIGN(GenericAlignArgs a) {
           default: s1 = tS; break;
         }
         s1 = __builtin_amdgcn_readfirstlane(s1);
-        if ((s1 == tN || s1 == tJ || s1 == tC) && s1 == s0) i--;
+        if ((s1 == tN || s1 == tJ || s1 == tC) && s1 == s0) {
+          if (PP && lane == 0 && i >= 1) ppo.put(i - 1, __builtin_nontemporal_load(pps + (size_t)i * xNSPEC + (s1 == tN ? 3 : s1 == tJ ? 4 : 5)));   // a flank residue
+          i--;
+        }
         s0 = s1;
         if (i < 0 || k < 0 || k > M) break;
       }
@@ -840,11 +866,15 @@ hipError_t launch_generic_front_long(const GenericArgs &a, int blocks, size_t ld
   hipLaunchKernelGGL(generic_front_long_kernel, dim3(blocks), dim3(64), lds, s, a);
   return hipGetLastError();
 }
-hipError_t launch_generic_align_long(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s) {
-  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&generic_align_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+template <bool PP>
+static hipError_t launch_generic_align_long_t(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s) {
+  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&generic_align_long_kernel<PP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(generic_align_long_kernel, dim3(blocks), dim3(64), lds, s, a);
+  hipLaunchKernelGGL(generic_align_long_kernel<PP>, dim3(blocks), dim3(64), lds, s, a);
   return hipGetLastError();
+}
+hipError_t launch_generic_align_long(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s) {
+  return (a.pp || a.pp64) ? launch_generic_align_long_t<true>(a, blocks, lds, s) : launch_generic_align_long_t<false>(a, blocks, lds, s);
 }
 #else
 hipError_t launch_generic_front_long(const GenericArgs &a, int blocks, size_t lds, hipStream_t s);
@@ -923,10 +953,14 @@ hipError_t launch_trunc_list(const uint8_t *flags, int64_t npairs, int *count, i
 
 hipError_t launch_generic_align(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s, bool longq) {
   if (longq ? a.slab_stride < generic_align_doubles(a.Lcap, a.Qmax) + generic_seq_doubles(a.Lcap) : lds < (size_t)a.Lcap) return hipErrorInvalidValue;
+  const bool pp = a.pp || a.pp64;
+  if (pp && a.slab_stride < a.pp_off + generic_align_pp_doubles(a.Lcap, a.Qmax) + (longq ? generic_seq_doubles(a.Lcap) : 0)) return hipErrorInvalidValue;
   if (longq) return launch_generic_align_long(a, blocks, lds, s);
-  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&generic_align_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const void *fn = pp ? reinterpret_cast<const void *>(&generic_align_kernel<true>) : reinterpret_cast<const void *>(&generic_align_kernel<false>);
+  hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL(generic_align_kernel, dim3(blocks), dim3(64), lds, s, a);
+  if (pp) hipLaunchKernelGGL(generic_align_kernel<true>, dim3(blocks), dim3(64), lds, s, a);
+  else hipLaunchKernelGGL(generic_align_kernel<false>, dim3(blocks), dim3(64), lds, s, a);
   return hipGetLastError();
 }
 #endif

@@ -162,7 +162,7 @@ struct wh_ehmm {
   uint16_t *path_buf16 = nullptr;           // wh_set_path_buffer16: the 16-bit record (its address reaches the ScoreArgs kernels that write it
                                             // through the spare slot of the path counters: kPathRecSlot, wh_launch.h)
   // staging for the host-pointer entry points
-  DevBuf s_res, s_off, s_deci, s_flags, s_fwd, s_det, s_idx, s_w, s_nk, s_nu, s_pq, s_ph, s_co, s_cols, s_pos;
+  DevBuf s_res, s_off, s_deci, s_flags, s_fwd, s_det, s_idx, s_w, s_nk, s_nu, s_pq, s_ph, s_co, s_cols, s_pp, s_pos;
   DevBuf d_rkeys, d_rorder, d_rchunks, d_qorder, d_order, d_items, d_recs, d_spec, d_back, d_cwj, d_cwv, d_cwn, d_crow, c_buf[10];
   uint32_t degen[32];
   bool timing = false;

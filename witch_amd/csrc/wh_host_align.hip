@@ -8,6 +8,8 @@ struct AlignCall {
   hipStream_t s;
   const uint8_t *d_residues; const int64_t *d_offsets; const int64_t *d_pair_q; const int32_t *d_pair_h; int64_t npairs;
   const int64_t *d_col_offsets; int32_t *d_cols;
+  float *d_pp;                   // per-residue posterior probabilities, CSR like d_cols (wh_align_pp_dev), or NULL
+  double *d_pp64;                // ... or as doubles (wh_align_pp64_dev); at most one of the two
   int32_t max_len; int Lc;
   int Lm;                        // length cap of the class launches (= Lc unless a class cannot plan the call's longest query: the longer queries' pairs go to the float64 kernel)
   int64_t n_long;                // such pairs of this call
@@ -84,7 +86,7 @@ static int align_pass(AlignCall &c, const std::vector<int32_t> &order, const std
   }
   if (e->d_ascratch.ensure(need_scratch) || (need_spec && e->d_spec.ensure(need_spec))) return WH_ENOMEM;
   for (const AlignClassPlan &p : plans) {
-    AlignArgs a;
+    AlignArgsPP a;
     memset(&a, 0, sizeof a);
     a.hmms = (const DevHMM *)e->d_hmms.p; a.tables = (const float *)e->d_tables.p;
     a.residues = c.d_residues; a.offsets = c.d_offsets; a.pair_q = c.d_pair_q;
@@ -93,7 +95,7 @@ static int align_pass(AlignCall &c, const std::vector<int32_t> &order, const std
     a.item_start = (const int32_t *)e->d_items.p + nit + p.first;
     a.item_count = (const int32_t *)e->d_items.p + 2 * nit + p.first;
     a.n_items = p.n_items;
-    a.col_offsets = c.d_col_offsets; a.cols = c.d_cols;
+    a.col_offsets = c.d_col_offsets; a.cols = c.d_cols; a.pp = c.d_pp; a.pp64 = c.d_pp64;
     a.counter = e->counter(kSlotLaunch0 + c.launches);
     a.Lcap = c.Lm; a.SP = p.SP; a.wave_lds = p.wave_lds;
     a.K = e->K; a.Kp = e->Kp; a.Klds = p.Klds; a.swap = p.swap ? 1 : 0;
@@ -117,8 +119,11 @@ static int align_pass(AlignCall &c, const std::vector<int32_t> &order, const std
   return WH_OK;
 }
 
-// the log-space pass: the pairs the float32 pass queued, grouped by model again
-static int align_logspace_pass(AlignCall &c, const std::vector<int32_t> &ph, int *n_redo) {
+// the log-space pass: the pairs the float32 pass queued, grouped by model again.  A call that asks for PP does not run it:
+// float32 logarithms of thousands of nats give posteriors good to percents (measured: up to 0.03 off, and above 1), which is
+// no confidence value - the queued pairs are returned in <pp_redo> and aligned by the float64 any-size kernel, whose own
+// log-space code is float64 (the hand-over the several-waves kernel makes through <status>)
+static int align_logspace_pass(AlignCall &c, const std::vector<int32_t> &ph, int *n_redo, std::vector<int32_t> *pp_redo) {
   wh_ehmm *e = c.e;
   *n_redo = 0;
   if (!c.want_redo) return WH_OK;
@@ -129,6 +134,11 @@ static int align_logspace_pass(AlignCall &c, const std::vector<int32_t> &ph, int
   HIPCHK(hipMemcpyAsync(redo.data(), c.d_redo_list, sizeof(int32_t) * redo.size(), hipMemcpyDeviceToHost, c.s));
   HIPCHK(hipStreamSynchronize(c.s));
   std::sort(redo.begin(), redo.end());
+  if (c.d_pp || c.d_pp64) {
+    if (e->knobs.trace) fprintf(stderr, "[wh] align: %d of %lld pairs left float32 range, handed to the float64 kernel (PP)\n", *n_redo, (long long)c.npairs);
+    *pp_redo = redo;
+    return WH_OK;
+  }
   group_by_model(redo.data(), *n_redo, ph, (int)e->hmms.size(), order2, cnt2);
   if (e->knobs.trace) fprintf(stderr, "[wh] align: %d of %lld pairs left float32 range, redone in log space\n", *n_redo, (long long)c.npairs);
   return align_pass(c, order2, cnt2, true);
@@ -177,7 +187,7 @@ static int align_wide(AlignCall &c, const std::map<int, std::vector<int32_t>> &w
     wa.residues = c.d_residues; wa.offsets = c.d_offsets;
     wa.items = (const int32_t *)e->d_order.p + ooff; wa.n_items = (int)kv.second.size();
     ooff += kv.second.size();
-    wa.pair_q = c.d_pair_q; wa.pair_h = c.d_pair_h; wa.col_off = c.d_col_offsets; wa.cols = c.d_cols;
+    wa.pair_q = c.d_pair_q; wa.pair_h = c.d_pair_h; wa.col_off = c.d_col_offsets; wa.cols = c.d_cols; wa.pp = c.d_pp; wa.pp64 = c.d_pp64;
     wa.status = (int32_t *)e->d_recs.p;
     if (wclass >= kWideAlignClasses) { set_error("too many classes of long models"); return WH_ERANGE; }
     wa.counter = e->counter(kSlotWideAlign + wclass++);
@@ -210,10 +220,14 @@ static int align_wide(AlignCall &c, const std::map<int, std::vector<int32_t>> &w
 // (wh_generic.hip), one wavefront per pair
 // doubles of one wave's slab of the any-size kernel for this call.  <longq>: a query beyond the LDS block (or, with pairs of
 // the long-query pass, WH_LONGQ_FORCE) - the residues behind the wave's slab
-static size_t align_float64_stride(const AlignCall &c, bool *longq) {
+// A call that asks for PP keeps the unrounded posterior rows between the two (<pp_off>: where); without PP the slab is
+// what it was.
+static size_t align_float64_stride(const AlignCall &c, bool *longq, size_t *pp_off = nullptr) {
   const wh_ehmm *e = c.e;
   *longq = (size_t)c.Lc + 64 > kLdsBudget ? !e->knobs.no_long_score : e->knobs.longq_force && c.n_long > 0;
-  return ((generic_align_doubles(c.Lc, e->max_Q) + 1) & ~(size_t)1) + (*longq ? generic_seq_doubles(c.Lc) : 0);
+  const size_t base = (generic_align_doubles(c.Lc, e->max_Q) + 1) & ~(size_t)1;
+  if (pp_off) *pp_off = base;
+  return base + ((c.d_pp || c.d_pp64) ? generic_align_pp_doubles(c.Lc, e->max_Q) : 0) + (*longq ? generic_seq_doubles(c.Lc) : 0);
 }
 
 static int align_float64(AlignCall &c, const std::vector<int32_t> &gitems) {
@@ -226,14 +240,14 @@ static int align_float64(AlignCall &c, const std::vector<int32_t> &gitems) {
   g.residues = c.d_residues; g.offsets = c.d_offsets;
   HIPCHK(hipMemcpyAsync(e->d_order.p, gitems.data(), sizeof(int32_t) * gitems.size(), hipMemcpyHostToDevice, s));
   g.items = (const int32_t *)e->d_order.p; g.n_items = (int)gitems.size();
-  g.pair_q = c.d_pair_q; g.pair_h = c.d_pair_h; g.col_off = c.d_col_offsets; g.cols = c.d_cols;
+  g.pair_q = c.d_pair_q; g.pair_h = c.d_pair_h; g.col_off = c.d_col_offsets; g.cols = c.d_cols; g.pp = c.d_pp; g.pp64 = c.d_pp64;
   if (e->d_recs.ensure(sizeof(int32_t) * ((size_t)c.npairs + 4))) return WH_ENOMEM;
   HIPCHK(hipMemsetAsync(e->d_recs.p, 0, sizeof(int32_t) * (size_t)c.npairs, s));
   g.status = (int32_t *)e->d_recs.p;
   g.counter = e->counter(kSlotGenericAlign);
   g.Lcap = Lc; g.Qmax = e->max_Q; g.Kp = e->Kp;
   bool longq = false;
-  g.slab_stride = align_float64_stride(c, &longq);
+  g.slab_stride = align_float64_stride(c, &longq, &g.pp_off);
   const size_t glds = longq ? 64 : (size_t)Lc + 64;
   if (glds > kLdsBudget) { set_error("query length %d does not fit the any-size kernel's LDS", c.max_len); return WH_ERANGE; }
   int blocks = (int)std::min<size_t>(gitems.size(), (size_t)e->cu_count * std::min<size_t>(12, kLdsBudget / glds));
@@ -263,12 +277,35 @@ static int align_float64(AlignCall &c, const std::vector<int32_t> &gitems) {
 extern "C" int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
                             int32_t max_len, const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
                             const int64_t *d_col_offsets, int32_t *d_cols, void *stream) {
+  return wh_align_pp_dev(e, d_residues, d_offsets, nq, total_residues, max_len, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, nullptr, stream);
+}
+
+// both PP entry points: <d_pp> floats, or <d_pp64> doubles, or neither
+static int align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
+                     int32_t max_len, const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
+                     const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, double *d_pp64, void *stream);
+
+extern "C" int wh_align_pp_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
+                               int32_t max_len, const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
+                               const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, void *stream) {
+  return align_dev(e, d_residues, d_offsets, nq, total_residues, max_len, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, d_pp, nullptr, stream);
+}
+
+extern "C" int wh_align_pp64_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
+                                 int32_t max_len, const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
+                                 const int64_t *d_col_offsets, int32_t *d_cols, double *d_pp64, void *stream) {
+  return align_dev(e, d_residues, d_offsets, nq, total_residues, max_len, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, nullptr, d_pp64, stream);
+}
+
+static int align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
+                     int32_t max_len, const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
+                     const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, double *d_pp64, void *stream) {
   (void)nq; (void)total_residues;
   if (!e || !d_residues || !d_offsets || !d_pair_q || !d_pair_h || !d_col_offsets || !d_cols || npairs < 0 || max_len < 0) {
     set_error("wh_align_dev: bad argument");
     return WH_EINVAL;
   }
-  AlignCall c = {e, (hipStream_t)stream, d_residues, d_offsets, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, max_len, std::max(max_len, 1)};
+  AlignCall c = {e, (hipStream_t)stream, d_residues, d_offsets, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, d_pp, d_pp64, max_len, std::max(max_len, 1)};
   hipStream_t s = c.s;
   HIPCHK(hipSetDevice(e->device));
   if (npairs == 0) { e->timers[2].launches = 0; e->timers[2].ms = 0; return WH_OK; }
@@ -322,19 +359,21 @@ extern "C" int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t
   HIPCHK(hipMemsetAsync(e->counter(kSlotAlignStat), 0, kAlignStatInts * sizeof(int), s));
   if (timer_begin(e, 2, s)) return WH_EHIP;
   int n_redo = 0;
+  std::vector<int32_t> pp_redo;
   if (!order.empty()) {          // (empty: every pair of the call is the long-query pass's)
     if (int rc = align_pass(c, order, cnt, false)) return rc;
-    if (int rc = align_logspace_pass(c, ph, &n_redo)) return rc;
+    if (int rc = align_logspace_pass(c, ph, &n_redo, &pp_redo)) return rc;
   }
   if (int rc = read_align_stats(c)) return rc;
   e->last_align_redo = n_redo;
   e->last_align_unaligned = 0;
   e->last_unaligned_pairs.clear();
-  if (!e->generic.empty() || e->force_wide || c.n_long > 0) {
+  if (!e->generic.empty() || e->force_wide || c.n_long > 0 || !pp_redo.empty()) {
     // models of 3 073 - 12 288 nodes go to the wide kernel; pairs that leave float32 range there, longer queries and
     // larger models (the 48-cell scoring class included) to the float64 kernel
     const bool use_wide = wide_align_lds_bytes(c.Lc) <= kLdsBudget && !e->wide_by_w.empty() && !e->knobs.no_wide_align;
     std::vector<int32_t> gitems(long_pairs);
+    gitems.insert(gitems.end(), pp_redo.begin(), pp_redo.end());
     std::map<int, std::vector<int32_t>> witems;
     std::vector<char> is_long(c.n_long > 0 ? (size_t)npairs : 0, 0);
     for (int32_t p : long_pairs) is_long[(size_t)p] = 1;

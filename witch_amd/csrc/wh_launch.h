@@ -250,6 +250,21 @@ struct WideArgs {
   int sparse;                  // envelope Forward rows: only the lanes above 2^-24 of the row's E are stored (+ masks behind the slab)
   uint16_t *paths16;           // optional [nq x H]: the 16-bit per-pair record (wh_set_path_buffer16), or NULL
 };
+// The PP output inside the PP kernels: a float array or a double array (wh_align_pp64) behind one word, bit 0 = "doubles".
+// A type of its own: nothing but put() can index it.
+struct PPOut {
+  uintptr_t u = 0;
+  PPOut() = default;
+#if defined(__HIPCC__)
+  __device__ __forceinline__ PPOut(float *p32, double *p64, int64_t off)
+      : u(p64 ? (reinterpret_cast<uintptr_t>(p64 + off) | 1) : reinterpret_cast<uintptr_t>(p32 + off)) {}
+  template <class T>
+  __device__ __forceinline__ void put(int64_t i, T v) const {
+    if (u & 1) reinterpret_cast<double *>(u & ~(uintptr_t)1)[i] = (double)v;
+    else reinterpret_cast<float *>(u)[i] = (float)v;
+  }
+#endif
+};
 struct WideAlignArgs {
   const DevHMM *hmms;
   const float *tables;
@@ -267,6 +282,9 @@ struct WideAlignArgs {
   float *scratch;              // per workgroup: Forward/posterior rows, then OA rows
   size_t scratch_stride;       // floats per workgroup
   int K, Kp;
+  // (last: the fields above keep the offsets they have without it)
+  float *pp;                   // optional, CSR like <cols>: posterior probability of each residue's state on the path (wh_align_pp), or NULL
+  double *pp64;                // ... or the same as doubles (wh_align_pp64); at most one of the two is set
 };
 size_t wide_align_lds_bytes(int Lcap);
 hipError_t launch_align_wide(int Q, const WideAlignArgs &a, int blocks, int waves, size_t lds, hipStream_t s);
@@ -322,6 +340,10 @@ struct GenericAlignArgs {
   int Lcap, Qmax, Kp;
   double *slab;
   size_t slab_stride;
+  // (last: the fields above keep the offsets they have without them)
+  float *pp;                   // optional, CSR like <cols>: posterior probability of each residue's state on the path (wh_align_pp), or NULL
+  double *pp64;                // ... or the same as doubles (wh_align_pp64); at most one of the two is set
+  size_t pp_off;               // with <pp>: where in the wave's slab the unrounded ppM / ppI rows are kept (generic_align_pp_doubles of them)
 };
 // <longq>: the instantiations that read the residues from the wave's slab in HBM, for queries beyond generic_lds_bytes: the
 // copy takes the last generic_seq_doubles(Lcap) doubles of the slab (slab_stride covers them), the LDS block is
@@ -330,6 +352,7 @@ hipError_t launch_generic_front(const GenericArgs &a, int blocks, size_t lds, hi
 hipError_t launch_generic_align(const GenericAlignArgs &a, int blocks, size_t lds, hipStream_t s, bool longq = false);
 size_t generic_front_doubles(int Lcap, int Qmax);
 size_t generic_align_doubles(int Lcap, int Qmax);
+size_t generic_align_pp_doubles(int Lcap, int Qmax);   // the extra rows of a call that asks for PP
 size_t generic_lds_bytes(int Lcap);
 size_t generic_seq_doubles(int Lcap);
 // the long-query scoring pass: queries longer than <Lmain> (count2: their number, the longest), their pairs on every model,
@@ -401,7 +424,13 @@ struct AlignArgs {
   int *wstat;                  // NULL or 4 counters: pairs aligned on a 256-node window, window rejected, window not tried, 512-node window
   unsigned long long *wcyc;    // NULL or 4 wave-cycle sums of the window pairs: Forward, Backward + posteriors, OA fill, traceback
 };
-hipError_t launch_align(int Q, const AlignArgs &a, int blocks, int threads, size_t lds, hipStream_t s);
+// what the host fills in; the kernels without the PP output take the core alone (the kernel arguments a build without the
+// feature has), the ones with it the whole
+struct AlignArgsPP : AlignArgs {
+  float *pp;                   // optional, CSR like <cols>: posterior probability of each residue's state on the path (wh_align_pp), or NULL
+  double *pp64;                // ... or the same as doubles (wh_align_pp64); at most one of the two is set
+};
+hipError_t launch_align(int Q, const AlignArgsPP &a, int blocks, int threads, size_t lds, hipStream_t s);
 
 struct ConsArgs {
   const int64_t *offsets;

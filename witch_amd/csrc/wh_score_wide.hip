@@ -24,6 +24,12 @@
 #include "wh_device.h"
 #include "wh_launch.h"
 
+// The file is compiled twice (Makefile): wh_score_wide.o without the alignment's PP output, wh_score_wide_pp.o
+// (WH_ALIGN_PP=1) with the alignment kernel alone, PP output compiled in; launched when WideAlignArgs::pp is set.
+#ifndef WH_ALIGN_PP
+#define WH_ALIGN_PP 0
+#endif
+
 namespace wh {
 
 // floats in front of the LDS emission copy of the TR scoring kernels (= the whole block of the others), 16-byte aligned
@@ -895,7 +901,7 @@ __device__ __forceinline__ float scan_apply_max_w(const ScanC &c, float B) {
 }
 __device__ __forceinline__ int wave_max_i32_w(int x) { for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(x, m); x = o > x ? o : x; } return x; }
 
-template <int Q, int NLT, bool TR>
+template <int Q, int NLT, bool TR, bool PP>
 __global__ __launch_bounds__(512) void align_wide_kernel(WideAlignArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), W = blockDim.x >> 6;
@@ -933,7 +939,10 @@ __global__ __launch_bounds__(512) void align_wide_kernel(WideAlignArgs a) {
     const int64_t off = a.offsets[qi];
     const int L = (int)(a.offsets[qi + 1] - off);
     int32_t *cols = a.cols + a.col_off[pair];
+    PPOut pp;
+    if constexpr (PP) pp = PPOut(a.pp, a.pp64, a.col_off[pair]);
     for (int t = threadIdx.x; t < L; t += blockDim.x) cols[t] = -1;
+    if constexpr (PP) { for (int t = threadIdx.x; t < L; t += blockDim.x) pp.put(t, 0.f); }     // a pair handed over or without a path keeps 0
     bool active = L > 0 && L <= a.Lcap;
     for (int t = threadIdx.x; active && t < L; t += blockDim.x) { const int r = a.residues[off + t]; seq[t] = (uint8_t)(r < a.Kp ? r : a.Kp - 1); }
     __syncthreads();
@@ -1130,6 +1139,13 @@ __global__ __launch_bounds__(512) void align_wide_kernel(WideAlignArgs a) {
         const int pos = k - 1, ln = pos / Q, q = pos % Q;
         return fwG[(((size_t)arr * Q4 + q / 4) * NL + ln) * 4 + (q % 4)];
       };
+      // the posterior of M_k / I_k (st 0 / 1) of a row: slab A still holds them ([row][2][Q4][NL]); the load does not
+      // depend on the OA cells of the step, so it rides along with their round trip
+      const float *sA = reinterpret_cast<const float *>((const void *)slabA);
+      auto postA = [&](int row, int st, int k) -> float {
+        const int pos = k - 1, ln = pos / Q, q = pos % Q;
+        return __builtin_nontemporal_load(sA + (((size_t)(row * 2 + st) * Q4 + q / 4) * NL + ln) * 4 + (q % 4));
+      };
       enum { stS, stN, stB, stM, stI, stD, stE, stJ, stC };
       int s0 = stC, s1 = stS, i = L, k = 0;
       int guard = 4 * (L + M) + 16;
@@ -1191,7 +1207,7 @@ __global__ __launch_bounds__(512) void align_wide_kernel(WideAlignArgs a) {
             if (path[2] > path[best]) best = 2;
             if (path[3] > path[best]) best = 3;
             s1 = best == 0 ? stB : best == 1 ? stM : best == 2 ? stI : stD;
-            if (lane == 0) cols[i - 1] = k - 1;
+            if (lane == 0) { cols[i - 1] = k - 1; if constexpr (PP) pp.put(i - 1, postA(i, 0, k)); }
             k--; i--;
             break;
           }
@@ -1207,6 +1223,7 @@ __global__ __launch_bounds__(512) void align_wide_kernel(WideAlignArgs a) {
             const float piv = i > 1 ? cellB(i - 1, 1, k) : -INFINITY;
             const float av = gate_w(tabF(FW_MI, k), pmv), bv = gate_w(tabF(FW_II, k), piv);
             s1 = bv > av ? stI : stM;
+            if constexpr (PP) { if (lane == 0 && i >= 1) pp.put(i - 1, postA(i, 1, k)); }     // residue i sits in I_k
             i--;
             break;
           }
@@ -1218,7 +1235,10 @@ __global__ __launch_bounds__(512) void align_wide_kernel(WideAlignArgs a) {
           case stN: s1 = i == 0 ? stS : stN; break;
           default: s1 = stS; break;
         }
-        if ((s1 == stN || s1 == stJ || s1 == stC) && s1 == s0) i--;
+        if ((s1 == stN || s1 == stJ || s1 == stC) && s1 == s0) {
+          if constexpr (PP) { if (lane == 0 && i >= 1) pp.put(i - 1, spec[(s1 == stN ? WA_PN : s1 == stJ ? WA_PJ : WA_PC) * SP + i]); }   // a flank residue
+          i--;
+        }
         if (i < 0 || k < 0 || (s1 == stM && (k < 1 || i < 1)) || ((s1 == stC || s1 == stJ) && i < 1)) break;   // defensive
         s0 = s1;
       }
@@ -1229,20 +1249,29 @@ __global__ __launch_bounds__(512) void align_wide_kernel(WideAlignArgs a) {
 
 }  // namespace wide
 
+#if !WH_ALIGN_PP
 size_t wide_align_lds_bytes(int Lcap) {
   const int SP = (Lcap + 1 + 3) / 4 * 4;
   return (size_t)(4 + wide::WA_NARR * SP + 8 * wide::X_N) * sizeof(float) + (size_t)(Lcap + 16);
 }
+#endif
 
 template <int Q, int NLT, bool TR = false>
 static hipError_t launch_walign_t(const WideAlignArgs &a, int blocks, int waves, size_t lds, hipStream_t s) {
-  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&wide::align_wide_kernel<Q, NLT, TR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(&wide::align_wide_kernel<Q, NLT, TR, WH_ALIGN_PP != 0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (err != hipSuccess) return err;
-  hipLaunchKernelGGL((wide::align_wide_kernel<Q, NLT, TR>), dim3(blocks), dim3(waves * 64), lds, s, a);
+  hipLaunchKernelGGL((wide::align_wide_kernel<Q, NLT, TR, WH_ALIGN_PP != 0>), dim3(blocks), dim3(waves * 64), lds, s, a);
   return hipGetLastError();
 }
 
+#if WH_ALIGN_PP
+hipError_t launch_align_wide_pp(int Q, const WideAlignArgs &a, int blocks, int waves, size_t lds, hipStream_t s) {
+  if (!a.pp == !a.pp64) return hipErrorInvalidValue;
+#else
+hipError_t launch_align_wide_pp(int Q, const WideAlignArgs &a, int blocks, int waves, size_t lds, hipStream_t s);   // wh_score_wide_pp.o
 hipError_t launch_align_wide(int Q, const WideAlignArgs &a, int blocks, int waves, size_t lds, hipStream_t s) {
+  if (a.pp || a.pp64) return launch_align_wide_pp(Q, a, blocks, waves, lds, s);
+#endif
   if (waves < 1 || waves > kWideWavesMax) return hipErrorInvalidValue;
   if (Q == 4) return launch_walign_t<4, 0>(a, blocks, waves, lds, s);
   if (Q == kWideQReg) {
@@ -1273,6 +1302,7 @@ hipError_t launch_align_wide(int Q, const WideAlignArgs &a, int blocks, int wave
   }
 }
 
+#if !WH_ALIGN_PP
 size_t wide_lds_bytes(int Lcap, size_t em_floats) {
   return (size_t)wide_em_lds_offset_floats(Lcap) * sizeof(float) + em_floats * sizeof(float);
 }
@@ -1327,5 +1357,6 @@ hipError_t launch_score_wide(int Q, const WideArgs &a, int blocks, int waves, si
     default: return launch_wide_t<kWideQ, 0, false>(a, blocks, waves, lds, s);   // 1, 2 waves: WH_FORCE_WIDE=24 on small models
   }
 }
+#endif
 
 }  // namespace wh

@@ -221,8 +221,10 @@ class EHMM:
                             w.ctypes.data, nk.ctypes.data, nu.ctypes.data), "wh_topk")
         return idx, w, nk, nu
 
-    def align(self, residues, offsets, pair_q, pair_h):
-        """cols (CSR over the residues of each pair) and col_offsets."""
+    def align(self, residues, offsets, pair_q, pair_h, want_pp=False):
+        """cols (CSR over the residues of each pair) and col_offsets; with want_pp also pp (float32, CSR like cols): the
+        posterior probability of each residue's state on the returned path (include/witch_hip.h: wh_align_pp);
+        want_pp="float64": as float64 (wh_align_pp64), which the any-size float64 kernel fills unrounded."""
         residues = np.ascontiguousarray(residues, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         pair_q = np.ascontiguousarray(pair_q, dtype=np.int64)
@@ -231,11 +233,19 @@ class EHMM:
         co = np.zeros(len(pair_q) + 1, dtype=np.int64)
         co[1:] = np.cumsum(lens)
         cols = np.full(int(co[-1]), -1, dtype=np.int32)
+        if not want_pp:
+            if len(pair_q):
+                check(lib().wh_align(self._h, residues.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
+                                     pair_q.ctypes.data, pair_h.ctypes.data, len(pair_q), co.ctypes.data,
+                                     cols.ctypes.data), "wh_align")
+            return cols, co
+        wide = want_pp == "float64"
+        pp = np.zeros(int(co[-1]), dtype=np.float64 if wide else np.float32)
         if len(pair_q):
-            check(lib().wh_align(self._h, residues.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
-                                 pair_q.ctypes.data, pair_h.ctypes.data, len(pair_q), co.ctypes.data,
-                                 cols.ctypes.data), "wh_align")
-        return cols, co
+            check((lib().wh_align_pp64 if wide else lib().wh_align_pp)(self._h, residues.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
+                                    pair_q.ctypes.data, pair_h.ctypes.data, len(pair_q), co.ctypes.data,
+                                    cols.ctypes.data, pp.ctypes.data), "wh_align_pp")
+        return cols, co, pp
 
     def last_align_status(self):
         """(pairs redone in log space, pair numbers the last align call returned UNALIGNED - all columns -1 -
@@ -316,16 +326,24 @@ class EHMM:
                                 w.data_ptr(), nk.data_ptr(), nu.data_ptr(), self._stream()), "wh_topk_dev")
         return idx, w, nk, nu
 
-    def align_t(self, residues_t, offsets_t, max_len: int, pair_q_t, pair_h_t, col_offsets_t, total_cols: int):
+    def align_t(self, residues_t, offsets_t, max_len: int, pair_q_t, pair_h_t, col_offsets_t, total_cols: int,
+                want_pp=False):
+        """cols on the device; with want_pp (cols, pp) - pp float32, CSR like cols (wh_align_pp_dev)."""
         import torch
         cols = torch.full((int(total_cols),), -1, dtype=torch.int32, device=residues_t.device)
+        pp = torch.zeros((int(total_cols),), dtype=torch.float32, device=residues_t.device) if want_pp else None
         npairs = pair_q_t.numel()
-        if npairs:
+        if npairs and not want_pp:
             check(lib().wh_align_dev(self._h, residues_t.data_ptr(), offsets_t.data_ptr(), offsets_t.numel() - 1,
                                      residues_t.numel(), int(max_len), pair_q_t.data_ptr(), pair_h_t.data_ptr(),
                                      npairs, col_offsets_t.data_ptr(), cols.data_ptr(), self._stream()),
                   "wh_align_dev")
-        return cols
+        elif npairs:
+            check(lib().wh_align_pp_dev(self._h, residues_t.data_ptr(), offsets_t.data_ptr(), offsets_t.numel() - 1,
+                                        residues_t.numel(), int(max_len), pair_q_t.data_ptr(), pair_h_t.data_ptr(),
+                                        npairs, col_offsets_t.data_ptr(), cols.data_ptr(), pp.data_ptr(),
+                                        self._stream()), "wh_align_pp_dev")
+        return (cols, pp) if want_pp else cols
 
     def consensus_t(self, offsets_t, max_len: int, qpair_off_t, pair_h_t, pair_w_t, col_offsets_t, cols_t,
                     ret_off_t, retained_t, nongaps_t, backbone_length: int, max_pairs_per_query: int):

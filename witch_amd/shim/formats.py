@@ -95,12 +95,15 @@ def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets):
     return "\n".join(out) + "\n"
 
 
-def stockholm_row(seq_text, cols, M):
+def stockholm_row(seq_text, cols, M, flank_at_end=False):
     """One hmmalign row: match columns 0..M-1 in order (uppercase residue or '-'), residues that
-    are not in a match column (cols == -1: flanks and inserts) lowercase where they occur."""
+    are not in a match column (cols == -1: flanks and inserts) lowercase where they occur.  With
+    flank_at_end the residues behind the last match state (the C flank) follow the model's last column,
+    where hmmalign itself writes them; the decoded columns are the same either way."""
     parts, c = [], 0
-    for ch, col in zip(seq_text, cols):
-        col = int(col)
+    cols = [int(x) for x in cols]
+    last = max([i for i, col in enumerate(cols) if col >= 0], default=len(cols) - 1) if flank_at_end else len(cols) - 1
+    for ch, col in zip(seq_text[:last + 1], cols[:last + 1]):
         if col >= 0:
             if col > c:
                 parts.append("-" * (col - c))
@@ -110,16 +113,75 @@ def stockholm_row(seq_text, cols, M):
             parts.append(ch.lower())
     if M > c:
         parts.append("-" * (M - c))
+    if flank_at_end:
+        parts.append(seq_text[last + 1:len(cols)].lower())
     return "".join(parts)
 
 
-def format_stockholm(name, row, width=200):
-    """Interleaved Stockholm blocks of <width> columns like hmmalign writes."""
+def pp_char(p):
+    """hmmalign's character for a posterior probability (HMMER's p7_alidisplay_EncodePostProb): '0'..'9' for
+    p + 0.05 in [0.0, 0.1) .. [0.9, 1.0), '*' from 0.95 up."""
+    p = float(p) + 0.05
+    return "*" if p >= 1.0 else chr(ord("0") + int(p * 10.0))
+
+
+def hmm_has_rf(path):
+    """True when the model file's header says "RF yes" (hmmalign then copies the model's own reference line)."""
+    opener = open
+    if str(path).endswith(".gz"):
+        import gzip
+        opener = gzip.open
+    with opener(path, "rt") as f:
+        for line in f:
+            w = line.split()
+            if w and w[0] == "RF":
+                return len(w) > 1 and w[1].lower() == "yes"
+            if w and w[0] == "HMM":
+                break
+    return False
+
+
+def stockholm_pp_lines(row, pp, rf=True):
+    """The annotation lines of one hmmalign row (stockholm_row) from the per-residue posteriors <pp> (or their
+    characters): (PP, PP_cons, RF).  PP: the residue's character, '.' in a gap.  PP_cons of a single sequence: the same
+    character in match columns that hold a residue, '.' elsewhere.  RF: 'x' at match columns, '.' at insert columns
+    (models without a reference line of their own); None with rf=False."""
+    gr, cons, rfl, r = [], [], [], 0
+    for ch in row:
+        if ch == "-":
+            gr.append("."); cons.append("."); rfl.append("x")
+        else:
+            d = pp[r] if isinstance(pp[r], str) else pp_char(pp[r])
+            r += 1
+            gr.append(d)
+            cons.append(d if ch.isupper() else ".")
+            rfl.append("x" if ch.isupper() else ".")
+    return "".join(gr), "".join(cons), "".join(rfl) if rf else None
+
+
+def format_stockholm(name, row, width=200, pp=None, rf=True):
+    """Interleaved Stockholm blocks of <width> columns like hmmalign writes.  With <pp> (one posterior probability, or
+    its character, per residue of the row) also hmmalign's "#=GR <name> PP", "#=GC PP_cons" and (rf) "#=GC RF" lines,
+    the sequence name padded to the longest tag; without it the sequence lines alone."""
     out = ["# STOCKHOLM 1.0", ""]
-    namew = max(len(name), 1)
-    for a in range(0, max(len(row), 1), width):
-        out.append("%-*s %s" % (namew, name, row[a:a + width]))
-        out.append("")
+    if pp is None:
+        namew = max(len(name), 1)
+        for a in range(0, max(len(row), 1), width):
+            out.append("%-*s %s" % (namew, name, row[a:a + width]))
+            out.append("")
+        out.append("//")
+        return "\n".join(out) + "\n"
+    gr, cons, rfl = stockholm_pp_lines(row, pp, rf)
+    tagw = len("#=GR %s PP" % name)
+    blocks = list(range(0, max(len(row), 1), width))
+    for a in blocks:
+        out.append("%-*s %s" % (tagw, name, row[a:a + width]))
+        out.append("%-*s %s" % (tagw, "#=GR %s PP" % name, gr[a:a + width]))
+        out.append("%-*s %s" % (tagw, "#=GC PP_cons", cons[a:a + width]))
+        if rfl is not None:
+            out.append("%-*s %s" % (tagw, "#=GC RF", rfl[a:a + width]))
+        if a != blocks[-1]:
+            out.append("")
     out.append("//")
     return "\n".join(out) + "\n"
 

@@ -161,7 +161,8 @@ class GpuBackend:
         return hdr, rows
 
     def align(self, jobs):
-        """jobs: [(hmm_path, name, text)] -> [(M, cols)]; one launch per distinct model."""
+        """jobs: [(hmm_path, name, text)] -> [(M, cols, pp)]; one launch per distinct model.  pp: the posterior
+        probability of each residue's state on the path (wh_align_pp), hmmalign's PP line."""
         from witch_amd.ehmm import pack_queries
         out = [None] * len(jobs)
         by_model = {}
@@ -172,9 +173,9 @@ class GpuBackend:
                 e, hdr = self.model(hp)
                 seqs = [e.digitize(jobs[j][2].upper()) for j in idxs]
                 res, offs = pack_queries(seqs)
-                cols, co = e.align(res, offs, np.arange(len(idxs)), np.zeros(len(idxs), dtype=np.int32))
+                cols, co, pp = e.align(res, offs, np.arange(len(idxs)), np.zeros(len(idxs), dtype=np.int32), want_pp=True)
                 for n, j in enumerate(idxs):
-                    out[j] = (int(e.M[0]), cols[co[n]:co[n + 1]].copy())
+                    out[j] = (int(e.M[0]), cols[co[n]:co[n + 1]].copy(), pp[co[n]:co[n + 1]].copy())
         return out
 
 
@@ -259,8 +260,15 @@ class Server:
             # needs the shared insert columns hmmalign computes, which this shim does not emit
             raise ArgError("witch-hip hmmalign shim: exactly one sequence per call (got %d)" % len(records))
         name, text = records[0]
-        M, cols = self.batcher.submit((hmm, name, text))
-        sto = formats.format_stockholm(name, formats.stockholm_row(text, cols, M))
+        res = self.batcher.submit((hmm, name, text))
+        if len(res) > 2 and res[2] is not None:
+            # hmmalign's own layout: PP, PP_cons and RF lines, the C flank behind the model's last column
+            M, cols, pp = res[:3]
+            sto = formats.format_stockholm(name, formats.stockholm_row(text, cols, M, flank_at_end=True), pp=pp,
+                                           rf=not formats.hmm_has_rf(hmm))
+        else:                                             # a backend without posteriors: the sequence line alone
+            M, cols = res[:2]
+            sto = formats.format_stockholm(name, formats.stockholm_row(text, cols, M))
         if "-o" in opts:
             with open(os.path.join(cwd, opts["-o"]), "w") as f:
                 f.write(sto)
