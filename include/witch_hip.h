@@ -15,6 +15,9 @@
  *                     and the 0.999 cumulative-weight cut   witch_msa/gcmm/aligner.py:58-63
  *   wh_align*      <- getBackbones running "hmmalign -o OUT HMM QUERY" per chosen HMM
  *                     and decoding the Stockholm row witch_msa/gcmm/aligner.py:96-142
+ *   wh_domains*    <- hmmsearch's "Domain annotation for each sequence" section and its --domtblout file; NO reference
+ *                     code reads either (evalHMMSearchOutput parses the per-sequence table only): they are here for the
+ *                     users of the hmmsearch program the library replaces
  *
  * Conventions: plain pointers and sizes; the caller owns every input and output
  * buffer; the library owns wh_ehmm handles and its device workspace.  Functions
@@ -211,6 +214,66 @@ int wh_align_pp64_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_of
                       const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
                       const int64_t *d_col_offsets, int32_t *d_cols, double *d_pp, void *stream);
 
+/* ---- per-domain results (hmmsearch's "Domain annotation for each sequence" section and --domtblout; no reference code
+ * calls either - witch_msa reads the per-sequence table alone) -------------------------------------------------------
+ * A DOMAIN is an envelope of a reported pair, as wh_score lists it in the pair's wh_pair_detail record.  Its ALIGNMENT is
+ * wh_align_pp's alignment of the envelope's residues env_i..env_j against the pair's model - hmmalign's optimal-accuracy
+ * alignment under the unihit length model of Ld = env_j - env_i + 1 residues.  On domains that HMMER prints with an
+ * accuracy of 0.95 or more that is hmmsearch's own alignment, coordinate for coordinate; on weaker ones hmmsearch usually
+ * prints the same alignment with columns trimmed at an end (the agreement per stratum).
+ * bits, bias_bits and lnP follow HMMER's float32 arithmetic (L: the query's length):
+ *   bits = (envsc + (L - Ld) ln(L / (L + 3)) - nullsc - dombias) / ln 2,  nullsc = L ln(L / (L + 1)) + ln(1 / (L + 1)),
+ *   dombias = logsum(0, ln(1 / 256) + domcorr),  bias_bits = dombias / ln 2,  lnP = min(0, -lambda (bits - tau))
+ * with tau, lambda from the model's STATS LOCAL FORWARD line (wh_ehmm_evparams).  The E-values are the caller's:
+ * i-Evalue = exp(lnP) Z (Z: number of targets), c-Evalue = exp(lnP) domZ (domZ: number of reported targets). */
+typedef struct wh_domain {
+  int64_t pair;            /* q * H + h                                                        */
+  int32_t index, of;       /* 0-based among the pair's envelopes; the pair's envelope count as far as the detail record tells
+                              it (HMMER's "#" - 1 and "of"): see wh_domain_counts for its two limits                       */
+  int32_t env_i, env_j;    /* 1-based, as in wh_pair_detail                                     */
+  int32_t ali_i, ali_j;    /* first / last residue of the query in a match state; 0, 0: no path */
+  int32_t hmm_i, hmm_j;    /* their nodes, 1-based                                              */
+  float   bits, bias_bits; /* HMMER's per-domain score and bias                                 */
+  float   oasc;            /* sum of the path's posteriors over the envelope; acc = oasc / Ld   */
+  float   lnP;             /* min(0, -lambda (bits - tau)); NaN for a model without a STATS LOCAL FORWARD line */
+} wh_domain;
+
+/* Domains per pair, from the flags and detail records of a wh_score call over nq queries: counts[nq x H] =
+ * min(nenv, WH_MAX_ENVELOPES) for a pair with WH_FLAG_REPORTED, else 0.  The caller turns the counts into the CSR
+ * dom_off[nq x H + 1].  n_unlisted[nq x H] (optional) and a record's "of" say what the detail record lets them say about the
+ * envelopes beyond its list, which entered the pair's score and which no domain record describes.  The scoring kernels cap
+ * nenv at WH_MAX_ENVELOPES and export the full count of REGIONS only (nregions), so there are two limits:
+ *  - a pair of the long-list pass (nregions > WH_MAX_ENVELOPES): of = nregions, n_unlisted = nregions - WH_MAX_ENVELOPES -
+ *    regions, not envelopes: exact when each region of the pair is one envelope, a lower bound otherwise;
+ *  - a pair with at most WH_MAX_ENVELOPES regions but more envelopes than that (one multidomain region that the resolver
+ *    splits many times, such as a tandem repeat of 17 or more copies): of = WH_MAX_ENVELOPES and n_unlisted = 0 although
+ *    envelopes are missing from the list - the records cannot tell such a pair from one with exactly 16 envelopes.
+ * Every other pair: of = nenv, n_unlisted = 0. */
+int wh_domain_counts(wh_ehmm *e, const uint8_t *flags, const wh_pair_detail *detail, int64_t nq,
+                     int32_t *counts, int32_t *n_unlisted);
+int wh_domain_counts_dev(wh_ehmm *e, const uint8_t *d_flags, const wh_pair_detail *d_detail, int64_t nq,
+                         int32_t *d_counts, int32_t *d_n_unlisted, void *stream);
+/* The domain records of a scoring call: the same residues / offsets / nq, its flags and detail records, and dom_off
+ * [nq x H + 1], the exclusive prefix sums of wh_domain_counts' counts (checked against the records: WH_EINVAL otherwise, as
+ * for an envelope outside its query).  out[dom_off[nq x H]]: the domains of pair p at dom_off[p] .. dom_off[p + 1], in envelope
+ * order.  Three kernels around one wh_align_pp_dev call on the packed envelopes (envelopes of one pair may overlap, so they are
+ * copied): the launch planning, node windows, log-space and any-size hand-overs of that call serve as they are, and
+ * wh_last_align_status / _paths / wh_last_kernel_ms(2) then describe the domains' alignments.  The _dev variant reads
+ * dom_off's last entry and the envelope lengths back (it waits for the stream twice before the alignment, which waits itself,
+ * as wh_align_dev does); max_len: the longest query, which no envelope may exceed (WH_EINVAL); total_residues is not read. */
+int wh_domains(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq,
+               const uint8_t *flags, const wh_pair_detail *detail, const int64_t *dom_off, wh_domain *out);
+int wh_domains_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq,
+                   int64_t total_residues, int32_t max_len,
+                   const uint8_t *d_flags, const wh_pair_detail *d_detail, const int64_t *d_dom_off, wh_domain *d_out,
+                   void *stream);
+/* The Forward E-value parameters of every model, from its "STATS LOCAL FORWARD tau lambda" line (hmmbuild writes it, as
+ * does wh_hmmbuild2 / wh_hmmbuild_batch with WH_BUILD_STATS): tau[H], lambda[H], present[H] (each optional); a model without
+ * the line loads as before and has present = 0, tau = lambda = NaN.  Needs no device. */
+int wh_ehmm_evparams(const wh_ehmm *e, float *tau, float *lambda, int32_t *present);
+/* The same for one model file, through the same parser, without a handle (wh_ehmm_load needs a device, this does not). */
+int wh_hmm_evparams(const char *hmm_path, float *tau, float *lambda, int32_t *present);
+
 /* Outcome classes of the last wh_align / wh_align_dev call on this handle (the call itself returns WH_OK for
  * them): n_logspace = pairs that left the float range and were redone in log space (same columns as hmmalign's
  * own log-space fallback); n_unaligned = pairs returned with ALL columns -1 where hmmalign (aligner.py:96-142) would
@@ -313,7 +376,8 @@ int wh_consensus_dev(wh_ehmm *e, const int64_t *d_offsets, int64_t nq, int32_t m
 
 /* Duration (ms) and launch count of the kernels of the last *_dev/plain call, measured
  * with HIP events on the stream the kernels ran on: which = 0 scoring kernels, 1 topk, 2 align, 3 consensus,
- * 4 multidomain resolver (the second part of wh_score: stage time of scoring = 0 + 4). */
+ * 4 multidomain resolver (the second part of wh_score: stage time of scoring = 0 + 4), 5 the domain stage (wh_domains: its
+ * gather and summary kernels and the alignment launches between them; which = 2 then holds the alignment launches alone). */
 int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches);
 /* Timing mode only: the scoring launches of the last wh_score[_dev] call, in launch order - the cells-per-lane class of the
  * launch's models (16 = models of 961..1024 nodes ...), the kernel family (0 phase-call wh::k7::score_kernel7, 1

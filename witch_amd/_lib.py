@@ -34,6 +34,20 @@ class PairDetail(C.Structure):
     ]
 
 
+class Domain(C.Structure):
+    """wh_domain (include/witch_hip.h); DOMAIN_DTYPE is the same layout for numpy."""
+    _fields_ = [
+        ("pair", C.c_int64), ("index", C.c_int32), ("of", C.c_int32), ("env_i", C.c_int32), ("env_j", C.c_int32),
+        ("ali_i", C.c_int32), ("ali_j", C.c_int32), ("hmm_i", C.c_int32), ("hmm_j", C.c_int32),
+        ("bits", C.c_float), ("bias_bits", C.c_float), ("oasc", C.c_float), ("lnP", C.c_float),
+    ]
+
+
+DOMAIN_FIELDS = [("pair", "<i8"), ("index", "<i4"), ("of", "<i4"), ("env_i", "<i4"), ("env_j", "<i4"), ("ali_i", "<i4"),
+                 ("ali_j", "<i4"), ("hmm_i", "<i4"), ("hmm_j", "<i4"), ("bits", "<f4"), ("bias_bits", "<f4"), ("oasc", "<f4"),
+                 ("lnP", "<f4")]
+
+
 # every symbol include/witch_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -72,6 +86,12 @@ SYMBOLS = {
     "wh_align_pp_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "wh_align_pp64": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),
     "wh_align_pp64_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "wh_domain_counts": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
+    "wh_domain_counts_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
+    "wh_domains": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "wh_domains_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
+    "wh_ehmm_evparams": (C.c_int, [_P, _P, _P, _P]),
+    "wh_hmm_evparams": (C.c_int, [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "wh_consensus": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),
     "wh_consensus_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "wh_last_align_status": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P, C.c_int64]),

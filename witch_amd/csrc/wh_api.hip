@@ -1,6 +1,7 @@
 // C ABI of libwitch_hip.so (declared in include/witch_hip.h): handle management, options, getters of the last call's
 // figures, the host-pointer entry points, top-k, consensus and the final merge.  wh_score_dev is in wh_host_score.hip
-// (its resolver stage in wh_host_resolve.hip), wh_align_dev in wh_host_align.hip; what they share is in wh_host.h.
+// (its resolver stage in wh_host_resolve.hip), wh_align_dev in wh_host_align.hip, the per-domain results (wh_domains*,
+// wh_ehmm_evparams) in wh_host_domains.hip; what they share is in wh_host.h.
 #include <atomic>
 #include <chrono>
 #include <memory>
@@ -59,6 +60,7 @@ void wh_ehmm_free(wh_ehmm *e) {
                     &e->s_nk, &e->s_nu, &e->s_pq, &e->s_ph, &e->s_co, &e->s_cols, &e->s_pp, &e->s_pos, &e->d_rkeys, &e->d_rorder, &e->d_rchunks, &e->d_qorder, &e->d_order, &e->d_items, &e->d_recs, &e->d_spec, &e->d_back, &e->d_cwj, &e->d_cwv, &e->d_cwn, &e->d_crow,
                     &e->c_buf[0], &e->c_buf[1], &e->c_buf[2], &e->c_buf[3], &e->c_buf[4], &e->c_buf[5], &e->c_buf[6],
                     &e->c_buf[7], &e->c_buf[8], &e->c_buf[9],
+                    &e->d_evp, &e->d_dom_pair, &e->d_dom_len, &e->d_env_res, &e->d_env_off, &e->d_dom_q, &e->d_dom_h, &e->d_dom_cols, &e->d_dom_pp, &e->s_dcnt, &e->s_dunl, &e->s_doff, &e->s_dom,
                     &e->d_p2bak, &e->d_st_pairs, &e->d_st_p1spec, &e->d_st_units, &e->d_st_p3spec, &e->d_st_slabs, &e->d_st_cnt})
     b->release();
   for (hipEvent_t ev : e->cls_ev) (void)hipEventDestroy(ev);
@@ -365,7 +367,7 @@ int wh_last_score_launches(wh_ehmm *e, int32_t *cells_per_lane, int32_t *kind, d
 }
 
 int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches) {
-  if (!e || which < 0 || which > 4) return WH_EINVAL;
+  if (!e || which < 0 || which > 5) return WH_EINVAL;
   KernelTimer &t = e->timers[which];
   if (t.pending) {
     HIPCHK(hipEventSynchronize(t.e1));

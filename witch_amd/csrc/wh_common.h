@@ -31,6 +31,8 @@ struct HostHMM {
   std::vector<double> t;      // [(M+1)*7]  MM MI MD IM II DM DD, as in the file (node 0..M)
   std::vector<double> mat;    // [(M+1)*K]
   std::vector<int32_t> map;   // [M+1]
+  bool has_fstats = false;    // the file has a "STATS LOCAL FORWARD tau lambda" line (per-domain E-values: wh_ehmm_evparams)
+  float ftau = 0.f, flambda = 0.f;
   // configured profile
   std::vector<double> pt;     // [(M+1)*7], node 0 and node M zeroed
   std::vector<double> entry;  // [M+2]

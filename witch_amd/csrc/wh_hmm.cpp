@@ -114,6 +114,8 @@ int parse_hmm_file(const std::string &path, HostHMM &h) {
       else if (a == "rna") h.alphabet = WH_ALPH_RNA;
       else if (a == "amino") h.alphabet = WH_ALPH_AMINO;
       else { set_error("%s: unsupported alphabet %s", path.c_str(), tok[1].c_str()); return WH_EIO; }
+    } else if (key == "STATS" && tok.size() >= 5 && tok[1] == "LOCAL" && tok[2] == "FORWARD") {
+      h.has_fstats = true; h.ftau = (float)atof(tok[3].c_str()); h.flambda = (float)atof(tok[4].c_str());
     } else if (key == "HMM") { body = true; break; }
   }
   if (!body || h.M <= 0 || h.alphabet < 0) { set_error("%s: truncated header", path.c_str()); return WH_EIO; }

@@ -1,6 +1,6 @@
 // Internal header of the host side of libwitch_hip.so: what wh_api.hip (handles, options, getters, host-pointer entry
-// points), wh_host_score.hip (wh_score_dev), wh_host_resolve.hip (its resolver stage) and wh_host_align.hip (wh_align_dev)
-// share.  No kernel file includes it.
+// points), wh_host_score.hip (wh_score_dev), wh_host_resolve.hip (its resolver stage), wh_host_align.hip (wh_align_dev) and
+// wh_host_domains.hip (wh_domains_dev) share.  No kernel file includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -146,6 +146,11 @@ struct wh_ehmm {
   int64_t last_long_score[2] = {0, 0};      // long-query scoring pass of the last wh_score call: pairs scored by it, the longest query among them
   int64_t last_long_align[2] = {0, 0};      // ... and the same of the last wh_align call's long-query alignment pass
   DevBuf d_lqlist;                          // long-query scoring pass: the queries beyond the main length cap (their pairs: d_tlist)
+  // wh_domains_dev: Forward tau / lambda per model (NaN without the STATS line), per-domain pair and envelope length, the
+  // packed envelopes with their CSR, the alignment's pair lists, columns and posteriors; staging of the host entry points
+  std::vector<int64_t> h_env_off;           // ... host sources of asynchronous uploads: they outlive the call
+  std::vector<float> h_evp;
+  DevBuf d_evp, d_dom_pair, d_dom_len, d_env_res, d_env_off, d_dom_q, d_dom_h, d_dom_cols, d_dom_pp, s_dcnt, s_dunl, s_doff, s_dom;
   int64_t rq_cap = 0;                       // records the queue of the current scoring call holds
   double rq_rate = 0.0;                     // largest share of queued pairs any call on this handle has seen (sizes the next queue)
   int64_t rq_floor = 0;                     // ... at least this many (set when a call overflowed its estimate; the call then runs again)
@@ -166,7 +171,7 @@ struct wh_ehmm {
   DevBuf d_rkeys, d_rorder, d_rchunks, d_qorder, d_order, d_items, d_recs, d_spec, d_back, d_cwj, d_cwv, d_cwn, d_crow, c_buf[10];
   uint32_t degen[32];
   bool timing = false;
-  KernelTimer timers[5];
+  KernelTimer timers[6];                    // wh_last_kernel_ms: 0 scoring, 1 topk, 2 align, 3 consensus, 4 resolver, 5 domain stage
   int max_M = 0;
   int max_Q = 4;                              // largest cells-per-lane of any model (sizes the float64 slabs)
   int last_align_redo = 0;          // pairs of the last wh_align call that went through the log-space pass

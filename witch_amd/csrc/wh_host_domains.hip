@@ -1,0 +1,179 @@
+// Host side of the per-domain results (include/witch_hip.h: wh_domain_counts, wh_domains, wh_ehmm_evparams): the kernels of
+// wh_domains.hip around one wh_align_pp_dev call on the packed envelopes.
+#include <limits>
+
+#include "wh_host.h"
+
+static int max_query_len(const int64_t *offsets, int64_t nq) {
+  int64_t m = 0;
+  for (int64_t i = 0; i < nq; i++) m = std::max(m, offsets[i + 1] - offsets[i]);
+  return (int)m;
+}
+
+extern "C" {
+
+int wh_ehmm_evparams(const wh_ehmm *e, float *tau, float *lambda, int32_t *present) {
+  if (!e) { set_error("wh_ehmm_evparams: null handle"); return WH_EINVAL; }
+  const float nan = std::numeric_limits<float>::quiet_NaN();
+  for (size_t i = 0; i < e->hmms.size(); i++) {
+    const HostHMM &h = e->hmms[i];
+    if (tau) tau[i] = h.has_fstats ? h.ftau : nan;
+    if (lambda) lambda[i] = h.has_fstats ? h.flambda : nan;
+    if (present) present[i] = h.has_fstats ? 1 : 0;
+  }
+  return WH_OK;
+}
+
+int wh_hmm_evparams(const char *hmm_path, float *tau, float *lambda, int32_t *present) {
+  if (!hmm_path) { set_error("wh_hmm_evparams: bad argument"); return WH_EINVAL; }
+  HostHMM h;
+  if (int rc = parse_hmm_file(hmm_path, h)) return rc;
+  const float nan = std::numeric_limits<float>::quiet_NaN();
+  if (tau) *tau = h.has_fstats ? h.ftau : nan;
+  if (lambda) *lambda = h.has_fstats ? h.flambda : nan;
+  if (present) *present = h.has_fstats ? 1 : 0;
+  return WH_OK;
+}
+
+int wh_domain_counts_dev(wh_ehmm *e, const uint8_t *d_flags, const wh_pair_detail *d_detail, int64_t nq,
+                         int32_t *d_counts, int32_t *d_n_unlisted, void *stream) {
+  if (!e || !d_flags || !d_detail || !d_counts || nq < 0) { set_error("wh_domain_counts_dev: bad argument"); return WH_EINVAL; }
+  HIPCHK(hipSetDevice(e->device));
+  DomainArgs a;
+  memset(&a, 0, sizeof a);
+  a.flags = d_flags; a.detail = d_detail; a.H = (int)e->hmms.size(); a.npairs = nq * a.H;
+  a.counts = d_counts; a.n_unlisted = d_n_unlisted;
+  if (a.npairs > 0x7FFFFFFF) { set_error("too many pairs"); return WH_ERANGE; }
+  hipError_t err = launch_domain_count(a, (hipStream_t)stream);
+  if (err != hipSuccess) { set_error("domain count kernel launch failed: %s", hipGetErrorString(err)); return WH_EHIP; }
+  return WH_OK;
+}
+
+int wh_domains_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
+                   int32_t max_len, const uint8_t *d_flags, const wh_pair_detail *d_detail, const int64_t *d_dom_off,
+                   wh_domain *d_out, void *stream) {
+  (void)total_residues;          // (as in wh_align_dev: the residues are read through the offsets)
+  if (!e || !d_residues || !d_offsets || !d_flags || !d_detail || !d_dom_off || nq < 0 || max_len < 0) { set_error("wh_domains_dev: bad argument"); return WH_EINVAL; }
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipSetDevice(e->device));
+  const int H = (int)e->hmms.size();
+  const int64_t npairs = nq * H;
+  if (npairs > 0x7FFFFFFF) { set_error("too many pairs"); return WH_ERANGE; }
+  e->timers[5].launches = 0; e->timers[5].ms = 0; e->timers[5].pending = false;
+  if (npairs == 0) return WH_OK;
+  int64_t ndom = 0;
+  HIPCHK(hipMemcpyAsync(&ndom, d_dom_off + npairs, sizeof ndom, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (ndom < 0 || ndom > npairs * WH_MAX_ENVELOPES || ndom > 0x7FFFFFFF) { set_error("wh_domains_dev: dom_off ends at %lld for %lld pairs", (long long)ndom, (long long)npairs); return WH_EINVAL; }
+  if (ndom > 0 && !d_out) { set_error("wh_domains_dev: bad argument"); return WH_EINVAL; }
+  // Forward tau / lambda per model, uploaded once per handle, on the call's stream, from a vector the handle keeps
+  if (!e->d_evp.p) {
+    e->h_evp.assign((size_t)2 * H, std::numeric_limits<float>::quiet_NaN());
+    for (int h = 0; h < H; h++) {
+      const HostHMM &m = e->hmms[(size_t)h];
+      if (m.has_fstats) { e->h_evp[(size_t)2 * h] = m.ftau; e->h_evp[(size_t)2 * h + 1] = m.flambda; }
+    }
+    if (e->d_evp.ensure(sizeof(float) * e->h_evp.size())) return WH_ENOMEM;
+    HIPCHK(hipMemcpyAsync(e->d_evp.p, e->h_evp.data(), sizeof(float) * e->h_evp.size(), hipMemcpyHostToDevice, s));
+  }
+  // (dom_len: ndom lengths, then the word the list kernel sets when dom_off does not match the records)
+  if (e->d_dom_pair.ensure(sizeof(int64_t) * (size_t)ndom + 8) || e->d_dom_len.ensure(sizeof(int32_t) * ((size_t)ndom + 1)) ||
+      e->d_env_off.ensure(sizeof(int64_t) * ((size_t)ndom + 1)) || e->d_dom_q.ensure(sizeof(int64_t) * (size_t)ndom + 8) ||
+      e->d_dom_h.ensure(sizeof(int32_t) * (size_t)ndom + 8))
+    return WH_ENOMEM;
+  if (timer_begin(e, 5, s)) return WH_EHIP;
+  DomainArgs a;
+  memset(&a, 0, sizeof a);
+  a.flags = d_flags; a.detail = d_detail; a.npairs = npairs; a.H = H;
+  a.dom_off = d_dom_off; a.ndom = ndom;
+  a.dom_pair = (int64_t *)e->d_dom_pair.p; a.dom_len = (int32_t *)e->d_dom_len.p; a.bad = (int *)e->d_dom_len.p + ndom;
+  a.residues = d_residues; a.offsets = d_offsets;
+  // every length starts as -1 (a slot the list kernel does not reach is refused like a malformed envelope), the word as 0
+  if (ndom > 0) HIPCHK(hipMemsetAsync(a.dom_len, 0xFF, sizeof(int32_t) * (size_t)ndom, s));
+  HIPCHK(hipMemsetAsync(a.bad, 0, sizeof(int), s));
+  hipError_t err = launch_domain_list(a, s);
+  if (err != hipSuccess) { set_error("domain list kernel launch failed: %s", hipGetErrorString(err)); return WH_EHIP; }
+  std::vector<int32_t> len((size_t)ndom + 1);
+  HIPCHK(hipMemcpyAsync(len.data(), a.dom_len, sizeof(int32_t) * len.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (len[(size_t)ndom] != 0) { set_error("wh_domains_dev: dom_off is not the prefix sum of wh_domain_counts over these flags and detail records"); return WH_EINVAL; }
+  std::vector<int64_t> &env_off = e->h_env_off;      // (the handle's: the upload below needs it beyond this function's return)
+  env_off.assign((size_t)ndom + 1, 0);
+  int32_t max_env = 0;
+  for (int64_t d = 0; d < ndom; d++) {
+    if (len[(size_t)d] < 1) { set_error("wh_domains_dev: domain %lld has an envelope outside its query (or dom_off skips it)", (long long)d); return WH_EINVAL; }
+    env_off[(size_t)d + 1] = env_off[(size_t)d] + len[(size_t)d];
+    max_env = std::max(max_env, len[(size_t)d]);
+  }
+  if (max_env > max_len) { set_error("wh_domains_dev: an envelope of %d residues, but max_len is %d", max_env, max_len); return WH_EINVAL; }
+  const int64_t total_env = env_off[(size_t)ndom];
+  int launches = 1;
+  if (ndom > 0) {
+    if (e->d_env_res.ensure((size_t)total_env + 16) || e->d_dom_cols.ensure(sizeof(int32_t) * (size_t)total_env + 16) ||
+        e->d_dom_pp.ensure(sizeof(float) * (size_t)total_env + 16))
+      return WH_ENOMEM;
+    HIPCHK(hipMemcpyAsync(e->d_env_off.p, env_off.data(), sizeof(int64_t) * env_off.size(), hipMemcpyHostToDevice, s));
+    a.env_off = (const int64_t *)e->d_env_off.p; a.env_res = (uint8_t *)e->d_env_res.p;
+    a.dom_q = (int64_t *)e->d_dom_q.p; a.dom_h = (int32_t *)e->d_dom_h.p;
+    err = launch_envelope_gather(a, s);
+    if (err != hipSuccess) { set_error("envelope gather kernel launch failed: %s", hipGetErrorString(err)); return WH_EHIP; }
+    // the alignment: "query" d is envelope d, its model the pair's; one pair per envelope, so its columns share the CSR
+    int rc = wh_align_pp_dev(e, a.env_res, a.env_off, ndom, total_env, max_env, a.dom_q, a.dom_h, ndom, a.env_off,
+                             (int32_t *)e->d_dom_cols.p, (float *)e->d_dom_pp.p, s);
+    if (rc) return rc;
+    a.cols = (const int32_t *)e->d_dom_cols.p; a.pp = (const float *)e->d_dom_pp.p; a.evp = (const float *)e->d_evp.p; a.out = d_out;
+    err = launch_domain_summary(a, s);
+    if (err != hipSuccess) { set_error("domain summary kernel launch failed: %s", hipGetErrorString(err)); return WH_EHIP; }
+    launches = 3 + e->timers[2].launches;
+  }
+  if (timer_end(e, 5, s, launches)) return WH_EHIP;
+  return WH_OK;
+}
+
+int wh_domain_counts(wh_ehmm *e, const uint8_t *flags, const wh_pair_detail *detail, int64_t nq, int32_t *counts, int32_t *n_unlisted) {
+  if (!e || !flags || !detail || !counts || nq < 0) { set_error("wh_domain_counts: bad argument"); return WH_EINVAL; }
+  if (nq == 0) return WH_OK;
+  HIPCHK(hipSetDevice(e->device));
+  const size_t np = (size_t)nq * e->hmms.size();
+  if (e->s_flags.ensure(np) || e->s_det.ensure(sizeof(wh_pair_detail) * np) || e->s_dcnt.ensure(sizeof(int32_t) * np) ||
+      (n_unlisted && e->s_dunl.ensure(sizeof(int32_t) * np)))
+    return WH_ENOMEM;
+  HIPCHK(hipMemcpy(e->s_flags.p, flags, np, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->s_det.p, detail, sizeof(wh_pair_detail) * np, hipMemcpyHostToDevice));
+  int rc = wh_domain_counts_dev(e, (const uint8_t *)e->s_flags.p, (const wh_pair_detail *)e->s_det.p, nq, (int32_t *)e->s_dcnt.p,
+                                n_unlisted ? (int32_t *)e->s_dunl.p : nullptr, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(counts, e->s_dcnt.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
+  if (n_unlisted) HIPCHK(hipMemcpy(n_unlisted, e->s_dunl.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
+  return WH_OK;
+}
+
+int wh_domains(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const uint8_t *flags,
+               const wh_pair_detail *detail, const int64_t *dom_off, wh_domain *out) {
+  if (!e || !residues || !offsets || !flags || !detail || !dom_off || nq < 0) { set_error("wh_domains: bad argument"); return WH_EINVAL; }
+  if (nq == 0) return WH_OK;
+  HIPCHK(hipSetDevice(e->device));
+  const size_t np = (size_t)nq * e->hmms.size();
+  const int64_t total = offsets[nq], ndom = dom_off[np];
+  if (ndom < 0 || (ndom > 0 && !out)) { set_error("wh_domains: bad argument"); return WH_EINVAL; }
+  for (int64_t i = 0; i < total; i++)
+    if (residues[i] >= e->Kp) { set_error("residue code %d at position %lld is not in the alphabet", residues[i], (long long)i); return WH_EINVAL; }
+  if (e->s_res.ensure((size_t)total + 16) || e->s_off.ensure(sizeof(int64_t) * (size_t)(nq + 1)) || e->s_flags.ensure(np) ||
+      e->s_det.ensure(sizeof(wh_pair_detail) * np) || e->s_doff.ensure(sizeof(int64_t) * (np + 1)) || e->s_dom.ensure(sizeof(wh_domain) * (size_t)ndom + 16))
+    return WH_ENOMEM;
+  HIPCHK(hipMemcpy(e->s_res.p, residues, (size_t)total, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->s_off.p, offsets, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->s_flags.p, flags, np, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->s_det.p, detail, sizeof(wh_pair_detail) * np, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(e->s_doff.p, dom_off, sizeof(int64_t) * (np + 1), hipMemcpyHostToDevice));
+  int rc = wh_domains_dev(e, (const uint8_t *)e->s_res.p, (const int64_t *)e->s_off.p, nq, total, max_query_len(offsets, nq),
+                          (const uint8_t *)e->s_flags.p, (const wh_pair_detail *)e->s_det.p, (const int64_t *)e->s_doff.p,
+                          (wh_domain *)e->s_dom.p, nullptr);
+  if (rc) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  if (ndom > 0) HIPCHK(hipMemcpy(out, e->s_dom.p, sizeof(wh_domain) * (size_t)ndom, hipMemcpyDeviceToHost));
+  return WH_OK;
+}
+
+}  // extern "C"

@@ -394,6 +394,36 @@ struct TopkArgs {
 };
 hipError_t launch_topk(const TopkArgs &a, hipStream_t s);
 
+// wh_domains_dev (wh_domains.hip): the kernels around the alignment of the packed envelopes.  Each launcher reads the
+// fields its kernel needs; <npairs> = nq x H.
+struct DomainArgs {
+  const uint8_t *flags;        // [npairs]
+  const wh_pair_detail *detail;
+  int64_t npairs;
+  int H;
+  int32_t *counts;             // count kernel: [npairs] domains a pair lists ...
+  int32_t *n_unlisted;         // ... and (optional) its envelopes beyond them
+  const int64_t *dom_off;      // [npairs + 1]
+  int64_t ndom;
+  int64_t *dom_pair;           // [ndom] list kernel: the domain's pair ...
+  int32_t *dom_len;            // ... and its envelope's length; -1: an envelope outside its query
+  int *bad;                    // ... set when dom_off does not match the records
+  const uint8_t *residues;
+  const int64_t *offsets;      // [nq + 1]
+  const int64_t *env_off;      // [ndom + 1] CSR of the packed envelopes (and of their columns and posteriors)
+  uint8_t *env_res;            // gather kernel: the packed envelopes ...
+  int64_t *dom_q;              // ... and the alignment's pair lists: envelope d against model dom_h[d]
+  int32_t *dom_h;
+  const int32_t *cols;         // summary kernel: the alignment's columns and posteriors
+  const float *pp;
+  const float *evp;            // [H][2] Forward tau, lambda (NaN: no STATS line)
+  wh_domain *out;
+};
+hipError_t launch_domain_count(const DomainArgs &a, hipStream_t s);
+hipError_t launch_domain_list(const DomainArgs &a, hipStream_t s);
+hipError_t launch_envelope_gather(const DomainArgs &a, hipStream_t s);
+hipError_t launch_domain_summary(const DomainArgs &a, hipStream_t s);
+
 constexpr int kAlignSpecArrays = 14;   // special-state rows per wave of the alignment kernel (AL_NARR)
 struct AlignArgs {
   const DevHMM *hmms;

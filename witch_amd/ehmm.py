@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import PairDetail, WitchHipError, check, lib
+from ._lib import DOMAIN_FIELDS, PairDetail, WitchHipError, check, lib
 
 
 def pack_queries(seqs):
@@ -247,6 +247,46 @@ class EHMM:
                                     cols.ctypes.data, pp.ctypes.data), "wh_align_pp")
         return cols, co, pp
 
+    def evparams(self):
+        """(tau float32 [H], lambda float32 [H], present bool [H]): the models' "STATS LOCAL FORWARD" parameters, NaN where a
+        model file has no such line (include/witch_hip.h: wh_ehmm_evparams)."""
+        tau = np.zeros(self.H, dtype=np.float32)
+        lam = np.zeros(self.H, dtype=np.float32)
+        present = np.zeros(self.H, dtype=np.int32)
+        check(lib().wh_ehmm_evparams(self._h, tau.ctypes.data, lam.ctypes.data, present.ctypes.data), "wh_ehmm_evparams")
+        return tau, lam, present.astype(bool)
+
+    def domain_counts(self, flags, detail):
+        """(counts int32 [nq, H], n_unlisted int32 [nq, H]) from the flags and detail records of score(want_detail=True)
+        (include/witch_hip.h: wh_domain_counts)."""
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        nq = flags.size // self.H
+        counts = np.zeros((nq, self.H), dtype=np.int32)
+        unl = np.zeros((nq, self.H), dtype=np.int32)
+        if nq:
+            check(lib().wh_domain_counts(self._h, flags.ctypes.data, C.addressof(detail), nq, counts.ctypes.data,
+                                         unl.ctypes.data), "wh_domain_counts")
+        return counts, unl
+
+    def domains(self, residues, offsets, flags, detail, want_unlisted=False):
+        """The per-domain records of a scoring call: (records, dom_off) - a numpy structured array with the fields of
+        wh_domain (pair, index, of, env_i, env_j, ali_i, ali_j, hmm_i, hmm_j, bits, bias_bits, oasc, lnP) and the CSR
+        dom_off int64 [nq * H + 1]: pair q * H + h owns records dom_off[p] .. dom_off[p + 1].  flags, detail: what
+        score(residues, offsets, want_detail=True) returned.  want_unlisted: also n_unlisted int32 [nq, H]
+        (include/witch_hip.h: wh_domain_counts, wh_domains)."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        nq = len(offsets) - 1
+        counts, unl = self.domain_counts(flags, detail)
+        dom_off = np.zeros(nq * self.H + 1, dtype=np.int64)
+        np.cumsum(counts.reshape(-1), out=dom_off[1:])
+        out = np.zeros(int(dom_off[-1]), dtype=np.dtype(DOMAIN_FIELDS))
+        if nq:
+            check(lib().wh_domains(self._h, residues.ctypes.data, offsets.ctypes.data, nq, flags.ctypes.data,
+                                   C.addressof(detail), dom_off.ctypes.data, out.ctypes.data), "wh_domains")
+        return (out, dom_off, unl) if want_unlisted else (out, dom_off)
+
     def last_align_status(self):
         """(pairs redone in log space, pair numbers the last align call returned UNALIGNED - all columns -1 -
         because the any-size kernel could not align them; include/witch_hip.h: wh_last_align_status)."""
@@ -344,6 +384,29 @@ class EHMM:
                                         npairs, col_offsets_t.data_ptr(), cols.data_ptr(), pp.data_ptr(),
                                         self._stream()), "wh_align_pp_dev")
         return (cols, pp) if want_pp else cols
+
+    def domains_dev(self, residues_t, offsets_t, max_len: int, flags_t, detail_t):
+        """domains() on torch tensors resident on the device (wh_domain_counts_dev, wh_domains_dev on torch's current
+        stream): detail_t is a uint8 tensor holding the nq * H wh_pair_detail records of wh_score_dev.  Returns (records as
+        a uint8 tensor [n, 56] - view it on the host with numpy's DOMAIN_FIELDS dtype -, dom_off int64 [nq * H + 1],
+        n_unlisted int32 [nq, H])."""
+        import torch
+        nq = offsets_t.numel() - 1
+        dev = residues_t.device
+        counts = torch.empty((nq, self.H), dtype=torch.int32, device=dev)
+        unl = torch.empty((nq, self.H), dtype=torch.int32, device=dev)
+        dom_off = torch.zeros(nq * self.H + 1, dtype=torch.int64, device=dev)
+        if nq:
+            check(lib().wh_domain_counts_dev(self._h, flags_t.data_ptr(), detail_t.data_ptr(), nq, counts.data_ptr(),
+                                             unl.data_ptr(), self._stream()), "wh_domain_counts_dev")
+            dom_off[1:] = torch.cumsum(counts.reshape(-1), 0)
+        n = int(dom_off[-1].item())
+        out = torch.zeros((n, np.dtype(DOMAIN_FIELDS).itemsize), dtype=torch.uint8, device=dev)
+        if nq:
+            check(lib().wh_domains_dev(self._h, residues_t.data_ptr(), offsets_t.data_ptr(), nq, residues_t.numel(),
+                                       int(max_len), flags_t.data_ptr(), detail_t.data_ptr(), dom_off.data_ptr(),
+                                       out.data_ptr(), self._stream()), "wh_domains_dev")
+        return out, dom_off, unl
 
     def consensus_t(self, offsets_t, max_len: int, qpair_off_t, pair_h_t, pair_w_t, col_offsets_t, cols_t,
                     ret_off_t, retained_t, nongaps_t, backbone_length: int, max_pairs_per_query: int):

@@ -58,11 +58,8 @@ def _g(x):
     return "%9.2g" % x
 
 
-def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets):
-    """rows: [(name, bits, bias_bits, n_domains)] of the REPORTED sequences.  The table is what
-    evalHMMSearchOutput reads: a line starting with 'E-value', then >= 9 whitespace-separated
-    fields per row (E-value, score, bias, best-domain E-value/score/bias, exp, N, name), a blank
-    line to end.  The best-domain columns repeat the full-sequence values (not computed)."""
+def _hmmsearch_head(hmm_path, fasta_path, hdr, rows):
+    """(lines up to the per-sequence table's rule, width of its name column): shared by both forms of the main output."""
     namew = max([8] + [len(r[0]) for r in rows])
     out = []
     out.append("# hmmsearch :: search profile(s) against a sequence database")
@@ -80,10 +77,11 @@ def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets):
     if not rows:
         out.append("")
         out.append("   [No hits detected that satisfy reporting thresholds]")
-    for name, bits, bias, ndom in sorted(rows, key=lambda r: -r[1]):
-        ev = forward_evalue(bits, n_targets, hdr["ftau"], hdr["flambda"])
-        out.append("  %s %6.1f %5.1f  %s %6.1f %5.1f  %5.1f %2d  %-*s " %
-                   (_g(ev), bits, bias, _g(ev), bits, bias, float(max(ndom, 1)), max(ndom, 1), namew, name))
+    return out, namew
+
+
+def _hmmsearch_tail(out, hdr, n_targets):
+    """The pipeline summary that ends the main output; returns the text."""
     out.append("")
     out.append("")
     out.append("Internal pipeline statistics summary:")
@@ -93,6 +91,167 @@ def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets):
     out.append("//")
     out.append("[ok]")
     return "\n".join(out) + "\n"
+
+
+def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets, domains=None, lengths=None, Z=None, domZ=None, domE=10.0,
+                     incE=0.01, incdomE=0.01):
+    """rows: [(name, bits, bias_bits, n_domains)] of the REPORTED sequences.  The table is what
+    evalHMMSearchOutput reads: a line starting with 'E-value', then >= 9 whitespace-separated
+    fields per row (E-value, score, bias, best-domain E-value/score/bias, exp, N, name), a blank
+    line to end.  Without <domains> the best-domain columns repeat the full-sequence values (not computed).
+    With <domains> ({name: [domain records]}, see domain_entries; lengths: {name: residues}; a row may carry the
+    unrounded score as a fifth element, for the E-values) they hold the
+    i-Evalue, score and bias of the pair's best domain (the highest envelope score), N is the number of reportable
+    domains (incE / incdomE decide the '!' marks), and HMMER's "Domain annotation for each sequence" section (its ">> name" tables, as under --noali) follows."""
+    if domains is not None:
+        return _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE)
+    out, namew = _hmmsearch_head(hmm_path, fasta_path, hdr, rows)
+    for name, bits, bias, ndom in sorted(rows, key=lambda r: -r[1]):
+        ev = forward_evalue(bits, n_targets, hdr["ftau"], hdr["flambda"])
+        out.append("  %s %6.1f %5.1f  %s %6.1f %5.1f  %5.1f %2d  %-*s " %
+                   (_g(ev), bits, bias, _g(ev), bits, bias, float(max(ndom, 1)), max(ndom, 1), namew, name))
+    return _hmmsearch_tail(out, hdr, n_targets)
+
+
+# ------------------------------------------------------------------------------------------------ per-domain output
+DOMTBL_COLUMNS = ["target", "tacc", "tlen", "query", "qacc", "qlen", "evalue", "score", "bias", "num", "of", "c_evalue",
+                  "i_evalue", "dom_score", "dom_bias", "hmm_from", "hmm_to", "ali_from", "ali_to", "env_from", "env_to", "acc"]
+
+
+def ln_survival(bits, ftau, flambda):
+    """ln P(score >= bits) under HMMER's exponential tail for Forward scores: min(0, -lambda (bits - tau))."""
+    return 0.0 if bits < ftau else -flambda * (bits - ftau)
+
+
+def _exact(row):
+    """A row's score for E-values and ordering: its fifth element (the unrounded float32 score) when it has one, else the
+    printed one."""
+    return row[4] if len(row) > 4 else row[1]
+
+
+def hit_order(rows, hdr):
+    """The reported sequences in HMMER's order: by E-value, ties (all the scores below tau have P = 1) by name."""
+    if hdr.get("ftau") is None or hdr.get("flambda") is None:
+        return sorted(rows, key=lambda r: (-_exact(r), r[0]))
+    return sorted(rows, key=lambda r: (ln_survival(_exact(r), hdr["ftau"], hdr["flambda"]), r[0]))
+
+
+def domain_entries(hdr, rows, lengths, domains, n_targets, Z=None, domZ=None, domE=10.0, incE=0.01, incdomE=0.01):
+    """One dict per domain of every reported sequence, in HMMER's output order, with the 22 columns of a --domtblout
+    line as numbers (DOMTBL_COLUMNS) plus "reportable" (c-Evalue <= domE) and "included" (the '!' of a domain table: the
+    sequence's E-value <= incE and the domain's c-Evalue <= incdomE, hmmsearch's --incE / --incdomE, default 0.01).
+    domains: {name: [records]}, a record having index, of, env_i, env_j, ali_i, ali_j, hmm_i, hmm_j, bits, bias_bits, oasc,
+    lnP (the fields of wh_domain).  Z defaults to the number of targets, domZ to the number of reported sequences; "#" and
+    "of" count all the pair's domains."""
+    Z = float(n_targets if Z is None else Z)
+    domZ = float(len(rows) if domZ is None else domZ)
+    out = []
+    for row in hit_order(rows, hdr):
+        name, bits, bias = row[:3]
+        ev = forward_evalue(_exact(row), Z, hdr["ftau"], hdr["flambda"])
+        for d in domains.get(name, []):
+            p = math.exp(max(-745.0, float(d["lnP"]))) if d["lnP"] == d["lnP"] else 0.0
+            Ld = int(d["env_j"]) - int(d["env_i"]) + 1
+            out.append({"target": name, "tacc": "-", "tlen": int(lengths[name]), "query": hdr["name"], "qacc": "-",
+                        "qlen": int(hdr["M"]), "evalue": ev, "score": float(bits), "bias": float(bias),
+                        "num": int(d["index"]) + 1, "of": int(d["of"]), "c_evalue": p * domZ, "i_evalue": p * Z,
+                        "dom_score": float(d["bits"]), "dom_bias": float(d["bias_bits"]),
+                        "hmm_from": int(d["hmm_i"]), "hmm_to": int(d["hmm_j"]), "ali_from": int(d["ali_i"]),
+                        "ali_to": int(d["ali_j"]), "env_from": int(d["env_i"]), "env_to": int(d["env_j"]),
+                        "acc": float(d["oasc"]) / Ld, "reportable": p * domZ <= domE,
+                        "included": ev <= incE and p * domZ <= incdomE})
+    return out
+
+
+def _domtbl_widths(entries):
+    return (max([20] + [len(e["target"]) for e in entries]), max([20] + [len(e["query"]) for e in entries]),
+            max([10] + [len(e["tacc"]) for e in entries]), max([10] + [len(e["qacc"]) for e in entries]))
+
+
+def format_domtblout_lines(entries, widths=None):
+    """HMMER 3.1b2's --domtblout line for each entry (DOMTBL_COLUMNS as numbers; description "-")."""
+    tw, qw, taw, qaw = widths or _domtbl_widths(entries)
+    return ["%-*s %-*s %5d %-*s %-*s %5d %9.2g %6.1f %5.1f %3d %3d %9.2g %9.2g %6.1f %5.1f %5d %5d %5d %5d %5d %5d %4.2f %s" %
+            (tw, e["target"], taw, e["tacc"], e["tlen"], qw, e["query"], qaw, e["qacc"], e["qlen"], e["evalue"], e["score"],
+             e["bias"], e["num"], e["of"], e["c_evalue"], e["i_evalue"], e["dom_score"], e["dom_bias"], e["hmm_from"],
+             e["hmm_to"], e["ali_from"], e["ali_to"], e["env_from"], e["env_to"], e["acc"], "-") for e in entries]
+
+
+def format_domtblout_header(widths):
+    tw, qw, taw, qaw = widths
+    return ["#%*s %22s %40s %11s %11s %11s" % (tw + qw - 1 + 15 + taw + qaw, "", "--- full sequence ---",
+                                                  "-------------- this domain -------------", "hmm coord", "ali coord", "env coord"),
+            "#%-*s %-*s %5s %-*s %-*s %5s %9s %6s %5s %3s %3s %9s %9s %6s %5s %5s %5s %5s %5s %5s %5s %4s %s" %
+            (tw - 1, " target name", taw, "accession", "tlen", qw, "query name", qaw, "accession", "qlen", "E-value", "score",
+             "bias", "#", "of", "c-Evalue", "i-Evalue", "score", "bias", "from", "to", "from", "to", "from", "to", "acc",
+             "description of target"),
+            "#%s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s" %
+            ("-" * (tw - 1), "-" * taw, "-----", "-" * qw, "-" * qaw, "-----", "---------", "------", "-----", "---", "---",
+             "---------", "---------", "------", "-----", "-----", "-----", "-----", "-----", "-----", "-----", "----",
+             "---------------------")]
+
+
+def format_domtblout(hmm_path, fasta_path, hdr, rows, lengths, domains, n_targets, Z=None, domZ=None, domE=10.0):
+    """The --domtblout file in HMMER 3.1b2's layout: three header lines, one line per reportable domain, the trailer's
+    comment lines (program, version, pipeline mode, the two files, [ok])."""
+    entries = [e for e in domain_entries(hdr, rows, lengths, domains, n_targets, Z, domZ, domE) if e["reportable"]]
+    widths = _domtbl_widths(entries) if entries else (20, max(20, len(hdr["name"])), 10, 10)
+    out = format_domtblout_header(widths) + format_domtblout_lines(entries, widths)
+    out += ["#", "# Program:         hmmsearch", "# Version:         3.1b2 (February 2015)", "# Pipeline mode:   SEARCH",
+            "# Query file:      %s" % hmm_path, "# Target file:     %s" % fasta_path, "# [ok]"]
+    return "\n".join(out) + "\n"
+
+
+def format_domain_table(name, entries, M, L):
+    """HMMER's ">> name" section of one reported sequence (as printed under --noali): its reportable domains."""
+    out = [">> %s  " % name]
+    shown = [e for e in entries if e["reportable"]]
+    if not shown:
+        out.append("   [No individual domains that satisfy reporting thresholds (although complete target did)]")
+        out.append("")
+        return out
+    out.append(" %3s   %6s %5s %9s %9s %7s %7s %2s %7s %7s %2s %7s %7s %2s %4s" %
+               ("#", "score", "bias", "c-Evalue", "i-Evalue", "hmmfrom", "hmm to", "  ", "alifrom", "ali to", "  ", "envfrom", "env to",
+                "  ", "acc"))
+    out.append(" %3s   %6s %5s %9s %9s %7s %7s %2s %7s %7s %2s %7s %7s %2s %4s" %
+               ("---", "------", "-----", "---------", "---------", "-------", "-------", "  ", "-------", "-------", "  ", "-------",
+                "-------", "  ", "----"))
+    for e in shown:
+        out.append(" %3d %c %6.1f %5.1f %9.2g %9.2g %7d %7d %c%c %7d %7d %c%c %7d %7d %c%c %4.2f" %
+                   (e["num"], "!" if e["included"] else "?", e["dom_score"], e["dom_bias"], e["c_evalue"], e["i_evalue"],
+                    e["hmm_from"], e["hmm_to"], "[" if e["hmm_from"] == 1 else ".", "]" if e["hmm_to"] == M else ".",
+                    e["ali_from"], e["ali_to"], "[" if e["ali_from"] == 1 else ".", "]" if e["ali_to"] == L else ".",
+                    e["env_from"], e["env_to"], "[" if e["env_from"] == 1 else ".", "]" if e["env_to"] == L else ".", e["acc"]))
+    out.append("")
+    return out
+
+
+def _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE):
+    entries = domain_entries(hdr, rows, lengths, domains, n_targets, Z, domZ, domE, incE, incdomE)
+    by_name = {}
+    for e in entries:
+        by_name.setdefault(e["target"], []).append(e)
+    order = hit_order(rows, hdr)
+    out, namew = _hmmsearch_head(hmm_path, fasta_path, hdr, rows)
+    for row in order:
+        name, bits, bias, ndom = row[:4]
+        ev = forward_evalue(_exact(row), float(n_targets if Z is None else Z), hdr["ftau"], hdr["flambda"])
+        doms = by_name.get(name, [])
+        nrep = sum(1 for e in doms if e["reportable"])
+        if doms:
+            recs = domains[name]
+            best = doms[max(range(len(doms)), key=lambda t: float(recs[t]["envsc"]) if "envsc" in recs[t] else doms[t]["dom_score"])]
+            bev, bsc, bbias = best["i_evalue"], best["dom_score"], best["dom_bias"]
+        else:
+            bev, bsc, bbias = ev, bits, bias
+        out.append("  %s %6.1f %5.1f  %s %6.1f %5.1f  %5.1f %2d  %-*s " %
+                   (_g(ev), bits, bias, _g(bev), bsc, bbias, float(max(ndom, 1)), nrep, namew, name))
+    out.append("")
+    out.append("")
+    out.append("Domain annotation for each sequence:")
+    for row in order:
+        out.extend(format_domain_table(row[0], by_name.get(row[0], []), hdr["M"], lengths[row[0]]))
+    return _hmmsearch_tail(out, hdr, n_targets)
 
 
 def stockholm_row(seq_text, cols, M, flank_at_end=False):

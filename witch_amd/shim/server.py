@@ -73,7 +73,12 @@ def check_hmmsearch_options(opts):
     """The GPU path computes what WITCH's own command line asks for (algorithm.py:526-532):
     `--max` (no filters) with a reporting threshold that lets every hit through.  Anything that would
     change the reported set in HMMER (filters on, a real E-value / score cut-off, no null2) is refused
-    with exit status 1 instead of being silently ignored."""
+    with exit status 1 instead of being silently ignored.
+    --domtblout FILE is written (per-domain records of wh_domains; --domE, -Z and --domZ apply to it and to the
+    domain tables of the main output, whose '!' / '?' marks follow --incE and --incdomE; without --domtblout none of
+    these five is read - -Z and --domZ are then not even checked, as before).  Two things stay unimplemented and are accepted as no-ops: --tblout (its exp,
+    clu and ov columns need counts the scoring kernels do not export) and the alignment display (the output is always
+    that of --noali)."""
     if "--max" not in opts:
         raise ArgError("witch-hip hmmsearch shim: only the unfiltered search (--max) is implemented; "
                        "WITCH passes --max unless its filters are switched on")
@@ -86,9 +91,19 @@ def check_hmmsearch_options(opts):
                 v = float(opts[o])
             except ValueError:
                 raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
+            if o == "--domE" and not v >= 0:
+                raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
             if o == "-E" and v < 1e6:
                 raise ArgError("witch-hip hmmsearch shim: -E %s would drop hits; only E >= 1e6 (WITCH: 99999999) "
                                "is supported, every sequence with a domain is reported" % opts[o])
+    for o in (("-Z", "--domZ") if "--domtblout" in opts else ()):      # (read only for the per-domain output; else ignored as before)
+        if o in opts:
+            try:
+                ok = float(opts[o]) > 0
+            except ValueError:
+                ok = False
+            if not ok:
+                raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
 
 
 def parse_hmmalign_argv(argv):
@@ -144,21 +159,34 @@ class GpuBackend:
             self.cache.move_to_end(rp)
         return hit[1], hit[2]
 
-    def search(self, hmm_path, records):
-        """records: [(name, text)] -> [(name, bits, bias_bits, n_domains)] of reported sequences."""
+    def search(self, hmm_path, records, want_domains=False):
+        """records: [(name, text)] -> (header, [(name, bits, bias_bits, n_domains)] of reported sequences); with
+        want_domains also {name: [domain records]}: the fields of wh_domain (EHMM.domains) and the envelope's envsc.
+        The domains cost an alignment per envelope: only a caller that prints them asks for them."""
         from witch_amd.ehmm import pack_queries
+        domains = {}
         with self.lock:
             e, hdr = self.model(hmm_path)
             seqs = [e.digitize(t.upper()) for _, t in records]     # alignment_tools.py:730-731 upper-cases
             res, offs = pack_queries(seqs)
             deci, flags, det = e.score(res, offs, want_detail=True)
+            if want_domains:
+                recs, dom_off = e.domains(res, offs, flags, det)
+                for i, (name, _) in enumerate(records):
+                    lst = []
+                    for r in recs[dom_off[i]:dom_off[i + 1]]:
+                        d = {k: r[k].item() for k in recs.dtype.names}
+                        d["envsc"] = float(det[i].envsc[d["index"]])
+                        lst.append(d)
+                    if lst:
+                        domains[name] = lst
         rows = []
         for i, (name, _) in enumerate(records):
             if flags[i, 0] & 1:
                 d = det[i]
                 bias = max(0.0, float(d.pre_score) - float(d.seq_score))
-                rows.append((name, deci[i, 0] / 10.0, bias, int(d.nenv)))
-        return hdr, rows
+                rows.append((name, deci[i, 0] / 10.0, bias, int(d.nenv)) + ((float(d.seq_score),) if want_domains else ()))
+        return (hdr, rows, domains) if want_domains else (hdr, rows)
 
     def align(self, jobs):
         """jobs: [(hmm_path, name, text)] -> [(M, cols, pp)]; one launch per distinct model.  pp: the posterior
@@ -239,8 +267,18 @@ class Server:
             raise ArgError("Error: Failed to open sequence file %s for reading" % fa)
         check_hmmsearch_options(opts)
         records = formats.read_fasta(fa)
-        hdr, rows = self.backend.search(hmm, records)
-        text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records))
+        if "--domtblout" in opts:
+            hdr, rows, domains = self.backend.search(hmm, records, want_domains=True)
+            lengths = {n: len(t) for n, t in records}
+            kw = {"Z": float(opts["-Z"]) if "-Z" in opts else None, "domZ": float(opts["--domZ"]) if "--domZ" in opts else None,
+                  "domE": float(opts.get("--domE", 10.0))}
+            inc = {"incE": float(opts.get("--incE", 0.01)), "incdomE": float(opts.get("--incdomE", 0.01))}
+            text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records), domains=domains, lengths=lengths, **kw, **inc)
+            with open(os.path.join(cwd, opts["--domtblout"]), "w") as f:
+                f.write(formats.format_domtblout(hmm, fa, hdr, rows, lengths, domains, len(records), **kw))
+        else:
+            hdr, rows = self.backend.search(hmm, records)
+            text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records))
         if "-o" in opts:
             with open(os.path.join(cwd, opts["-o"]), "w") as f:
                 f.write(text)
