@@ -61,6 +61,7 @@ extern "C" {
 #define WH_FLAG_OVERRIDE  4   /* reconstruction score overrode the Forward score         */
 #define WH_FLAG_TRUNC     8   /* part of the pair was left out of its score (never for a well-formed call: see below) */
 #define WH_FLAG_EXACT    16   /* an envelope failed the sparse-spill certificate and was redone dense */
+#define WH_FLAG_FILTERED 32   /* wh_score_filtered only: an acceleration filter rejected the pair (never with REPORTED) */
 
 /* Envelopes a wh_pair_detail record LISTS.  The SCORE of a pair has no such limit (hmmsearch has none: SURVEY A.4, called at
  * witch_msa/gcmm/algorithm.py:526-532): a pair with more regions than the scoring kernels' list holds is scored a second
@@ -273,6 +274,51 @@ int wh_domains_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offse
 int wh_ehmm_evparams(const wh_ehmm *e, float *tau, float *lambda, int32_t *present);
 /* The same for one model file, through the same parser, without a handle (wh_ehmm_load needs a device, this does not). */
 int wh_hmm_evparams(const char *hmm_path, float *tau, float *lambda, int32_t *present);
+
+/* ---- hmmsearch's acceleration filters (hmmsearch WITHOUT --max: MSV filter -> bias filter -> Viterbi filter -> Forward) ----
+ * Per (query of length L, model), as HMMER 3.1b2's pipeline decides, with null1 = L ln(L / (L + 1)) + ln(1 / (L + 1)):
+ *   1. MSV      P = gumbel_surv((usc - null1) / ln 2; mu_MSV, lambda)        rejected where P > F1; a filter overflow passes
+ *   2. bias     NOT IMPLEMENTED (its definition could not be pinned on the reference's binary): the pipeline runs as
+ *               "hmmsearch --nobias" does, filtersc = null1, and a call with nobias = 0 is refused with WH_EINVAL
+ *   3. Viterbi  only where the last P > F2:  P = gumbel_surv((vfsc - filtersc) / ln 2; mu_VIT, lambda), rejected where P > F2
+ *   4. Forward  P = exp_surv((fwdsc - filtersc) / ln 2; tau, lambda), rejected where P > F3 (wh_score_filtered only)
+ * mu, tau, lambda: the model's three "STATS LOCAL" lines; a model without them cannot be filtered (WH_EINVAL, the message
+ * names it).  The two filters are integer dynamic programmes (8-bit, 16-bit): the device's raw scores are the host's and
+ * HMMER's to the bit, and every decision is a comparison of float32 scores that both sides compute with correctly
+ * rounded operations alone - wh_filter and wh_filter_host agree bit for bit.
+ * opts == NULL: HMMER's defaults, F1 = 0.02, F2 = 1e-3, F3 = 1e-5, nobias = 0 (so: refused until the bias filter exists; pass
+ * nobias = 1).  F >= 1 switches a stage off.
+ * stage[nq x H], in the scoring calls' pair order: bit 0 passed MSV, 1 passed bias, 2 passed Viterbi (also set where the
+ * sweep was skipped because the pair was below F2 already), 3 the Viterbi sweep ran, 4 passed Forward (wh_score_filtered
+ * only).  An empty query fails every stage.  filter_bias_nats (optional) = filtersc - null1: 0 without a bias filter.
+ * msv_raw / vit_raw (optional): the filters' raw integer results - MSV xJ (-1: overflow), Viterbi xC (32768: overflow,
+ * -32768: no path, -32769: the sweep did not run). */
+typedef struct wh_filter_opts { double F1, F2, F3; int32_t nobias; } wh_filter_opts;
+int wh_filter(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const wh_filter_opts *opts,
+              uint8_t *stage, float *filter_bias_nats, int32_t *msv_raw, int32_t *vit_raw);
+/* max_len: the longest query (a longer one gets stage 128 and nothing else); total_residues is not read */
+int wh_filter_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues, int32_t max_len,
+                  const wh_filter_opts *opts, uint8_t *d_stage, float *d_filter_bias_nats, int32_t *d_msv_raw, int32_t *d_vit_raw,
+                  void *stream);
+/* The same pipeline as plain scalar code over the n model files: no handle (wh_ehmm_load needs a device) and no HIP call - the
+ * reference of the kernels, for a build without a GPU.  counts4 (optional): pairs, passed MSV, passed bias, passed Viterbi. */
+int wh_filter_host(const char *const *hmm_paths, int n, const uint8_t *residues, const int64_t *offsets, int64_t nq,
+                   const wh_filter_opts *opts, uint8_t *stage, float *filter_bias_nats, int32_t *msv_raw, int32_t *vit_raw,
+                   int64_t *counts4);
+/* wh_score behind the filters: the filters run on every pair, the queries with at least one pair past stage 3 are compacted
+ * on the device and scored by the EXISTING scoring path (all H models of such a query: correct, partial savings; with one
+ * model only survivors are scored), the results are scattered back and stage 4 is applied from fwd_bits.  A pair past all
+ * four stages carries exactly wh_score's decibits, flags, fwd_bits and detail.  A pair that a stage rejected: flags =
+ * WH_FLAG_FILTERED alone, decibits = 0, detail zeroed (fwd_bits: its value where the pair was scored, else 0).  stage is
+ * optional.  The _dev variant waits for the stream once (it reads the surviving queries back), then as wh_score_dev does. */
+int wh_score_filtered(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const wh_filter_opts *opts,
+                      int32_t *decibits, uint8_t *flags, float *fwd_bits, wh_pair_detail *detail, uint8_t *stage);
+int wh_score_filtered_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
+                          int32_t max_len, const wh_filter_opts *opts, int32_t *d_decibits, uint8_t *d_flags, float *d_fwd_bits,
+                          wh_pair_detail *d_detail, uint8_t *d_stage, void *stream);
+/* The last wh_filter / wh_score_filtered call on the handle: out[0] = pairs, [1] passed MSV, [2] passed bias, [3] passed
+ * Viterbi, [4] passed Forward, [5] pairs handed to the scoring kernels ([4], [5]: 0 after wh_filter).  Waits for the device. */
+int wh_last_filter_counts(wh_ehmm *e, int64_t out[6]);
 
 /* Outcome classes of the last wh_align / wh_align_dev call on this handle (the call itself returns WH_OK for
  * them): n_logspace = pairs that left the float range and were redone in log space (same columns as hmmalign's

@@ -15,6 +15,9 @@ CSRC = os.path.join(_HERE, "csrc")
 
 WH_MAX_ENVELOPES = 16
 FLAG_REPORTED, FLAG_MULTI, FLAG_OVERRIDE, FLAG_TRUNC, FLAG_EXACT = 1, 2, 4, 8, 16
+FLAG_FILTERED = 32
+STAGE_MSV, STAGE_BIAS, STAGE_VIT, STAGE_VIT_RAN, STAGE_FWD = 1, 2, 4, 8, 16      # stage byte of wh_filter / wh_score_filtered
+VIT_NOT_RUN, VIT_OVERFLOW, MSV_OVERFLOW = -32769, 32768, -1
 ALPH_DNA, ALPH_RNA, ALPH_AMINO = 0, 1, 2
 WH_OK, WH_EINVAL, WH_EIO, WH_ENODEV, WH_EHIP, WH_ERANGE, WH_ENOMEM = 0, -1, -2, -3, -4, -5, -6      # include/witch_hip.h
 WH_BUILD_STATS, WH_BUILD_CALIB_NO_LDS = 1, 4
@@ -41,6 +44,11 @@ class Domain(C.Structure):
         ("ali_i", C.c_int32), ("ali_j", C.c_int32), ("hmm_i", C.c_int32), ("hmm_j", C.c_int32),
         ("bits", C.c_float), ("bias_bits", C.c_float), ("oasc", C.c_float), ("lnP", C.c_float),
     ]
+
+
+class FilterOpts(C.Structure):
+    """wh_filter_opts (include/witch_hip.h): HMMER's thresholds F1, F2, F3 and --nobias."""
+    _fields_ = [("F1", C.c_double), ("F2", C.c_double), ("F3", C.c_double), ("nobias", C.c_int32)]
 
 
 DOMAIN_FIELDS = [("pair", "<i8"), ("index", "<i4"), ("of", "<i4"), ("env_i", "<i4"), ("env_j", "<i4"), ("ali_i", "<i4"),
@@ -90,6 +98,12 @@ SYMBOLS = {
     "wh_domain_counts_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
     "wh_domains": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "wh_domains_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
+    "wh_filter": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    "wh_filter_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "wh_filter_host": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "wh_score_filtered": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "wh_score_filtered_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "wh_last_filter_counts": (C.c_int, [_P, _P]),
     "wh_ehmm_evparams": (C.c_int, [_P, _P, _P, _P]),
     "wh_hmm_evparams": (C.c_int, [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "wh_consensus": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),

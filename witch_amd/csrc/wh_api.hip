@@ -63,6 +63,7 @@ void wh_ehmm_free(wh_ehmm *e) {
                     &e->d_evp, &e->d_dom_pair, &e->d_dom_len, &e->d_env_res, &e->d_env_off, &e->d_dom_q, &e->d_dom_h, &e->d_dom_cols, &e->d_dom_pp, &e->s_dcnt, &e->s_dunl, &e->s_doff, &e->s_dom,
                     &e->d_p2bak, &e->d_st_pairs, &e->d_st_p1spec, &e->d_st_units, &e->d_st_p3spec, &e->d_st_slabs, &e->d_st_cnt})
     b->release();
+  filter_release(e);
   for (hipEvent_t ev : e->cls_ev) (void)hipEventDestroy(ev);
   for (auto &t : e->timers) {
     if (t.e0) (void)hipEventDestroy(t.e0);

@@ -38,6 +38,7 @@
 
 #include "../../include/witch_hip.h"
 #include "wh_calibrate.h"
+#include "wh_common.h"
 
 namespace wh {
 void set_error(const char *fmt, ...);
@@ -61,10 +62,6 @@ struct Alphabet {
   float cons_thresh = 0.f;
 };
 
-const double kAminoBgD[20] = {0.0787945, 0.0151600, 0.0535222, 0.0668298, 0.0397062, 0.0695071, 0.0229198,
-                              0.0590092, 0.0594422, 0.0963728, 0.0237718, 0.0414386, 0.0482904, 0.0395639,
-                              0.0540978, 0.0683364, 0.0540687, 0.0673417, 0.0114135, 0.0304133};
-
 bool make_alphabet(const char *mol, Alphabet &a) {
   memset(a.code, 255, sizeof a.code);
   memset(a.degen, 0, sizeof a.degen);
@@ -87,7 +84,7 @@ bool make_alphabet(const char *mol, Alphabet &a) {
     a.syms = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~"; a.name = "amino";
     a.K = 20; degen = aa_d; nd = 6;
     syn = "_-.-";
-    for (int x = 0; x < 20; x++) a.bg[x] = (float)kAminoBgD[x];
+    for (int x = 0; x < 20; x++) a.bg[x] = (float)wh::kAminoBg[x];
     a.cons_thresh = 0.5f;
   } else return false;
   a.Kp = (int)strlen(a.syms);

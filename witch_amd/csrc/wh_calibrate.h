@@ -163,7 +163,8 @@ struct CalibMSV {
   uint8_t base, bias, tbm, tec, tjb;
   std::vector<uint8_t> rb;   // [K][M+1] biased match costs
   uint8_t unbiased(float sc) const { sc = -1.0f * roundf(scale * sc); return sc > 255.f ? 255 : (uint8_t)sc; }
-  uint8_t biased(float sc) const { sc = -1.0f * roundf(scale * sc); return sc > (float)(255 - bias) ? 255 : (uint8_t)((uint8_t)sc + bias); }
+  // (a positive score is a negative cost: through int, so that the wrap-around HMMER's byte arithmetic relies on is defined)
+  uint8_t biased(float sc) const { sc = -1.0f * roundf(scale * sc); return sc > (float)(255 - bias) ? 255 : (uint8_t)((uint8_t)(int)sc + bias); }
 };
 
 inline void calib_msv_convert(const CalibProfile &gm, CalibMSV &om) {

@@ -24,6 +24,12 @@ constexpr int kRegsInts = 5 * WH_MAX_ENVELOPES;
 
 void set_error(const char *fmt, ...);
 
+// Easel's amino acid background frequencies (ACDEFGHIKLMNPQRSTVWY): one table for the profile configuration, hmmbuild,
+// the calibration and the filters
+constexpr double kAminoBg[20] = {0.0787945, 0.0151600, 0.0535222, 0.0668298, 0.0397062, 0.0695071, 0.0229198,
+                                 0.0590092, 0.0594422, 0.0963728, 0.0237718, 0.0414386, 0.0482904, 0.0395639,
+                                 0.0540978, 0.0683364, 0.0540687, 0.0673417, 0.0114135, 0.0304133};
+
 // ---- one parsed HMMER3/f model + its configured local profile (host, float64) ----
 struct HostHMM {
   int M = 0, K = 0, Kp = 0, alphabet = -1, nseq = 0, index = 0;
@@ -33,6 +39,11 @@ struct HostHMM {
   std::vector<int32_t> map;   // [M+1]
   bool has_fstats = false;    // the file has a "STATS LOCAL FORWARD tau lambda" line (per-domain E-values: wh_ehmm_evparams)
   float ftau = 0.f, flambda = 0.f;
+  // what the acceleration filters need (wh_filter.h): the probabilities in float32 as HMMER's parser holds them
+  // (expf(-x) of the printed field), and the MSV / VITERBI lines of STATS LOCAL (mu, lambda each)
+  std::vector<float> tf, matf;             // [(M+1)*7], [(M+1)*K]
+  bool has_mstats = false, has_vstats = false;
+  float mmu = 0.f, mlambda = 0.f, vmu = 0.f, vlambda = 0.f;
   // configured profile
   std::vector<double> pt;     // [(M+1)*7], node 0 and node M zeroed
   std::vector<double> entry;  // [M+2]

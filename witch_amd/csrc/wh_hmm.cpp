@@ -30,11 +30,6 @@ const char *last_error() { return g_err; }
 static const char *kDnaSym = "ACGT-RYMKSWHBVDN*~";
 static const char *kAminoSym = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~";
 
-static const double kAminoBg[20] = {
-    0.0787945, 0.0151600, 0.0535222, 0.0668298, 0.0397062, 0.0695071, 0.0229198,
-    0.0590092, 0.0594422, 0.0963728, 0.0237718, 0.0414386, 0.0482904, 0.0395639,
-    0.0540978, 0.0683364, 0.0540687, 0.0673417, 0.0114135, 0.0304133};
-
 int alphabet_sizes(int alphabet, int *K, int *Kp) {
   if (alphabet == WH_ALPH_AMINO) { *K = 20; *Kp = 29; return 0; }
   if (alphabet == WH_ALPH_DNA || alphabet == WH_ALPH_RNA) { *K = 4; *Kp = 18; return 0; }
@@ -90,6 +85,8 @@ static bool next_tokens(std::ifstream &f, std::vector<std::string> &tok) {
 }
 
 static double tok_prob(const std::string &s) { return s[0] == '*' ? 0.0 : std::exp(-atof(s.c_str())); }
+// the same field as HMMER's own parser stores it: float32, expf of the negated field
+static float tok_probf(const std::string &s) { return s[0] == '*' ? 0.0f : expf((float)(-1.0 * atof(s.c_str()))); }
 
 int parse_hmm_file(const std::string &path, HostHMM &h) {
   std::ifstream f(path);
@@ -116,6 +113,10 @@ int parse_hmm_file(const std::string &path, HostHMM &h) {
       else { set_error("%s: unsupported alphabet %s", path.c_str(), tok[1].c_str()); return WH_EIO; }
     } else if (key == "STATS" && tok.size() >= 5 && tok[1] == "LOCAL" && tok[2] == "FORWARD") {
       h.has_fstats = true; h.ftau = (float)atof(tok[3].c_str()); h.flambda = (float)atof(tok[4].c_str());
+    } else if (key == "STATS" && tok.size() >= 5 && tok[1] == "LOCAL" && tok[2] == "MSV") {
+      h.has_mstats = true; h.mmu = (float)atof(tok[3].c_str()); h.mlambda = (float)atof(tok[4].c_str());
+    } else if (key == "STATS" && tok.size() >= 5 && tok[1] == "LOCAL" && tok[2] == "VITERBI") {
+      h.has_vstats = true; h.vmu = (float)atof(tok[3].c_str()); h.vlambda = (float)atof(tok[4].c_str());
     } else if (key == "HMM") { body = true; break; }
   }
   if (!body || h.M <= 0 || h.alphabet < 0) { set_error("%s: truncated header", path.c_str()); return WH_EIO; }
@@ -124,6 +125,8 @@ int parse_hmm_file(const std::string &path, HostHMM &h) {
   h.t.assign((size_t)(M + 1) * 7, 0.0);
   h.mat.assign((size_t)(M + 1) * K, 0.0);
   h.map.assign((size_t)M + 1, 0);
+  h.tf.assign((size_t)(M + 1) * 7, 0.f);
+  h.matf.assign((size_t)(M + 1) * K, 0.f);
   auto bad = [&](const char *what, int k) {
     set_error("%s: malformed %s at node %d", path.c_str(), what, k);
     return WH_EIO;
@@ -133,14 +136,14 @@ int parse_hmm_file(const std::string &path, HostHMM &h) {
   if (!tok.empty() && tok[0] == "COMPO") { if (!next_tokens(f, tok)) return bad("node 0", 0); }
   // tok = node-0 insert emissions (insert odds are hardwired to 1 by the profile: ignored)
   if (!next_tokens(f, tok) || tok.size() < 7) return bad("node-0 transitions", 0);
-  for (int x = 0; x < 7; x++) h.t[x] = tok_prob(tok[x]);
+  for (int x = 0; x < 7; x++) { h.t[x] = tok_prob(tok[x]); h.tf[x] = tok_probf(tok[x]); }
   for (int k = 1; k <= M; k++) {
     if (!next_tokens(f, tok) || (int)tok.size() < K + 1 || atoi(tok[0].c_str()) != k) return bad("match line", k);
-    for (int x = 0; x < K; x++) h.mat[(size_t)k * K + x] = tok_prob(tok[1 + x]);
+    for (int x = 0; x < K; x++) { h.mat[(size_t)k * K + x] = tok_prob(tok[1 + x]); h.matf[(size_t)k * K + x] = tok_probf(tok[1 + x]); }
     if ((int)tok.size() > K + 1 && tok[K + 1][0] != '-') h.map[k] = atoi(tok[K + 1].c_str());
     if (!next_tokens(f, tok)) return bad("insert line", k);
     if (!next_tokens(f, tok) || tok.size() < 7) return bad("transition line", k);
-    for (int x = 0; x < 7; x++) h.t[(size_t)k * 7 + x] = tok_prob(tok[x]);
+    for (int x = 0; x < 7; x++) { h.t[(size_t)k * 7 + x] = tok_prob(tok[x]); h.tf[(size_t)k * 7 + x] = tok_probf(tok[x]); }
   }
   configure_profile(h);
   return WH_OK;

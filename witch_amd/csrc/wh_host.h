@@ -170,6 +170,7 @@ struct wh_ehmm {
   DevBuf s_res, s_off, s_deci, s_flags, s_fwd, s_det, s_idx, s_w, s_nk, s_nu, s_pq, s_ph, s_co, s_cols, s_pp, s_pos;
   DevBuf d_rkeys, d_rorder, d_rchunks, d_qorder, d_order, d_items, d_recs, d_spec, d_back, d_cwj, d_cwv, d_cwn, d_crow, c_buf[10];
   uint32_t degen[32];
+  struct FilterState *filter = nullptr;     // acceleration filters (wh_host_filter.hip): tables, per-length settings, last counts; made by the first wh_filter call
   bool timing = false;
   KernelTimer timers[6];                    // wh_last_kernel_ms: 0 scoring, 1 topk, 2 align, 3 consensus, 4 resolver, 5 domain stage
   int max_M = 0;
@@ -186,6 +187,9 @@ struct wh_ehmm {
   int *counter(int slot) const { return (int *)d_counter.p + slot; }      // a slot of the table above
   ResolveFeedback *d_feedback() const { return (ResolveFeedback *)counter(kSlotResolveFeedback); }
 };
+
+// wh_host_filter.hip: releases e->filter (wh_ehmm_free)
+void filter_release(wh_ehmm *e);
 
 // one event per scoring launch (timing mode only); events are created once and reused
 static inline int class_mark(wh_ehmm *e, hipStream_t s, int Q, int kind) {

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DOMAIN_FIELDS, PairDetail, WitchHipError, check, lib
+from ._lib import DOMAIN_FIELDS, FilterOpts, PairDetail, WitchHipError, check, lib
 
 
 def pack_queries(seqs):
@@ -191,7 +191,43 @@ class EHMM:
         check(min(n, 0), "wh_last_queue_reruns")
         return int(n)
 
-    def score(self, residues, offsets, want_fwd=False, want_detail=False):
+    @staticmethod
+    def filter_opts(filters=True, nobias=False) -> FilterOpts:
+        """wh_filter_opts from filters = True (HMMER's defaults F1 = 0.02, F2 = 1e-3, F3 = 1e-5) or (F1, F2, F3)."""
+        F = (0.02, 1e-3, 1e-5) if filters is True else tuple(float(x) for x in filters)
+        if len(F) != 3:
+            raise ValueError("filters: True or (F1, F2, F3)")
+        return FilterOpts(F[0], F[1], F[2], 1 if nobias else 0)
+
+    def filter(self, residues, offsets, filters=True, nobias=False, want_raw=False):
+        """hmmsearch's acceleration filters over every (query, model) pair (include/witch_hip.h: wh_filter): stage uint8
+        [nq, H] (bit 0 passed MSV, 1 passed bias, 2 passed Viterbi, 3 the Viterbi sweep ran) and filter_bias_nats float32
+        [nq, H]; with want_raw also the two filters' raw integer scores, int32 [nq, H] each.  The bias filter is not
+        implemented: nobias=False is refused (WitchHipError), as hmmsearch without --nobias is by the level-0 program."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        nq = len(offsets) - 1
+        o = self.filter_opts(filters, nobias)
+        stage = np.zeros((nq, self.H), dtype=np.uint8)
+        bias = np.zeros((nq, self.H), dtype=np.float32)
+        msv = np.zeros((nq, self.H), dtype=np.int32) if want_raw else None
+        vit = np.zeros((nq, self.H), dtype=np.int32) if want_raw else None
+        check(lib().wh_filter(self._h, residues.ctypes.data, offsets.ctypes.data, nq, C.byref(o), stage.ctypes.data,
+                              bias.ctypes.data, None if msv is None else msv.ctypes.data,
+                              None if vit is None else vit.ctypes.data), "wh_filter")
+        return (stage, bias, msv, vit) if want_raw else (stage, bias)
+
+    def last_filter_counts(self):
+        """The last filter / filtered score call: {"pairs", "msv", "bias", "vit", "fwd", "scored"} - pairs, pairs past each
+        of the four stages, pairs handed to the scoring kernels (include/witch_hip.h: wh_last_filter_counts)."""
+        c = np.zeros(6, dtype=np.int64)
+        check(lib().wh_last_filter_counts(self._h, c.ctypes.data), "wh_last_filter_counts")
+        return dict(zip(("pairs", "msv", "bias", "vit", "fwd", "scored"), (int(v) for v in c)))
+
+    def score(self, residues, offsets, want_fwd=False, want_detail=False, filters=None, nobias=False, want_stage=False):
+        """filters=None: hmmsearch --max, as ever.  filters=True or (F1, F2, F3): behind hmmsearch's acceleration filters
+        (wh_score_filtered): a pair that a stage rejects comes back with FLAG_FILTERED and without FLAG_REPORTED;
+        want_stage appends the stage bytes [nq, H]."""
         residues = np.ascontiguousarray(residues, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         nq = len(offsets) - 1
@@ -199,14 +235,26 @@ class EHMM:
         flags = np.zeros((nq, self.H), dtype=np.uint8)
         fwd = np.zeros((nq, self.H), dtype=np.float32) if want_fwd else None
         det = (PairDetail * (nq * self.H))() if want_detail else None
-        check(lib().wh_score(self._h, residues.ctypes.data, offsets.ctypes.data, nq, deci.ctypes.data,
-                             flags.ctypes.data, None if fwd is None else fwd.ctypes.data,
-                             None if det is None else C.addressof(det)), "wh_score")
+        stage = np.zeros((nq, self.H), dtype=np.uint8) if want_stage else None
+        if filters is None or filters is False:
+            if nobias or want_stage:
+                raise ValueError("nobias / want_stage belong to a filtered call (filters=True or (F1, F2, F3))")
+            check(lib().wh_score(self._h, residues.ctypes.data, offsets.ctypes.data, nq, deci.ctypes.data,
+                                 flags.ctypes.data, None if fwd is None else fwd.ctypes.data,
+                                 None if det is None else C.addressof(det)), "wh_score")
+        else:
+            o = self.filter_opts(filters, nobias)
+            check(lib().wh_score_filtered(self._h, residues.ctypes.data, offsets.ctypes.data, nq, C.byref(o), deci.ctypes.data,
+                                          flags.ctypes.data, None if fwd is None else fwd.ctypes.data,
+                                          None if det is None else C.addressof(det),
+                                          None if stage is None else stage.ctypes.data), "wh_score_filtered")
         out = [deci, flags]
         if want_fwd:
             out.append(fwd)
         if want_detail:
             out.append(det)
+        if want_stage:
+            out.append(stage)
         return tuple(out)
 
     def topk(self, decibits, flags, k: int):

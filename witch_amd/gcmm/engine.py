@@ -65,6 +65,7 @@ class QueryAlignmentEngine:
         self.long_query_pairs = 0     # pairs of queries beyond the resolver's LDS block, resolved by the long-query pass
         self.long_score_pairs = 0     # pairs of queries beyond a scoring class's LDS plan, scored by the long-query scoring pass
         self.unaligned_pairs = []     # (taxon, hmm label) the alignment stage returned unaligned
+        self.filter_counts = {}       # run(filters=...): pairs, pairs past the MSV / bias / Viterbi / Forward stage, pairs scored
         self.query_text = None        # uint8: the local queries' characters (upper-cased on read), concatenated like query_offsets
         self.device = 0
         # multi-GPU (one process per GPU): this rank scored, aligned and merged the
@@ -77,7 +78,8 @@ class QueryAlignmentEngine:
     @classmethod
     def run(cls, index_to_hmm, unaligned, num_hmms: int, device: int = 0, multidomain_policy: str = "resolve",
             subset_to_retained_columns=None, subset_to_nongaps_per_column=None, backbone_length=None,
-            world: int = 1, rank: int = 0, group=None, chunk: int = 20000, keep_scores: bool = True):
+            world: int = 1, rank: int = 0, group=None, chunk: int = 20000, keep_scores: bool = True, filters=False,
+            nobias: bool = False):
         """Score, weight and align every query of ``unaligned`` ({taxon: sequence text} or a list of
         (taxon, text)) against every HMM of ``index_to_hmm``.
 
@@ -90,7 +92,15 @@ class QueryAlignmentEngine:
 
         ``chunk``: queries per pass (default 20 000, the reference's own hmmsearch chunk, algorithm.py:209; 0 = all at
         once).  ``keep_scores=False`` drops the nq x H deci-bit / flag tables once a chunk's top-k is formed - the host
-        then holds top-k records, aligned columns and consensus codes only (rankBitscores / ranked() need the tables)."""
+        then holds top-k records, aligned columns and consensus codes only (rankBitscores / ranked() need the tables).
+
+        ``filters``: the reference's ``self.filters`` (algorithm.py:526-532: hmmsearch without --max).  False: every pair
+        is scored, as hmmsearch --max does.  True or (F1, F2, F3): hmmsearch's MSV, Viterbi and Forward filters run in
+        front of the scoring kernels (EHMM.score(filters=...)); a pair a stage rejects is not reported, as it has no line
+        in hmmsearch's table.  HMMER's bias filter is not implemented, and a filtered run never drops the stage silently:
+        the caller says ``nobias=True`` (the run is then that of hmmsearch --nobias, NOT of the reference's filtered
+        command line, which keeps the bias stage); without it a filtered run is refused (WitchHipError), like EHMM.score.
+        ``self.filter_counts`` sums the stage counts of the chunks."""
         import time
         import warnings
         if multidomain_policy not in ("resolve", "drop", "envelope"):
@@ -145,7 +155,12 @@ class QueryAlignmentEngine:
             coffs = offs[c0:c1 + 1] - offs[c0]
             cres = res[offs[c0]:offs[c1]]
             t0 = time.time()
-            deci, flags = e.score(cres, coffs)
+            if filters is False or filters is None:
+                deci, flags = e.score(cres, coffs)
+            else:
+                deci, flags = e.score(cres, coffs, filters=filters, nobias=nobias)
+                for k_, v_ in e.last_filter_counts().items():
+                    self.filter_counts[k_] = self.filter_counts.get(k_, 0) + v_
             self.long_list_pairs += e.last_long_list_pairs()
             self.big_region_pairs += e.last_region_overflow()["pairs"]
             self.long_query_pairs += e.last_long_queries()[0]

@@ -80,21 +80,27 @@ def _hmmsearch_head(hmm_path, fasta_path, hdr, rows):
     return out, namew
 
 
-def _hmmsearch_tail(out, hdr, n_targets):
-    """The pipeline summary that ends the main output; returns the text."""
+def _hmmsearch_tail(out, hdr, n_targets, passed=None):
+    """The pipeline summary that ends the main output; returns the text.  passed: None (a search with --max, as ever), or
+    ((n MSV, n bias, n Vit, n Fwd), (F1, F2, F3)) of a filtered search: HMMER's four "Passed ... filter:" lines."""
     out.append("")
     out.append("")
     out.append("Internal pipeline statistics summary:")
     out.append("-------------------------------------")
     out.append("Query model(s):                            1  (%d nodes)" % hdr["M"])
     out.append("Target sequences:                   %8d" % n_targets)
+    if passed is not None:
+        (n1, nb, n2, n3), (F1, F2, F3) = passed
+        nt = float(max(n_targets, 1))
+        for label, n, F in (("MSV", n1, F1), ("bias", nb, F1), ("Vit", n2, F2), ("Fwd", n3, F3)):
+            out.append("%-28s%15d  (%.6g); expected %.1f (%.6g)" % ("Passed %s filter:" % label, n, n / nt, F * n_targets, F))
     out.append("//")
     out.append("[ok]")
     return "\n".join(out) + "\n"
 
 
 def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets, domains=None, lengths=None, Z=None, domZ=None, domE=10.0,
-                     incE=0.01, incdomE=0.01):
+                     incE=0.01, incdomE=0.01, passed=None):
     """rows: [(name, bits, bias_bits, n_domains)] of the REPORTED sequences.  The table is what
     evalHMMSearchOutput reads: a line starting with 'E-value', then >= 9 whitespace-separated
     fields per row (E-value, score, bias, best-domain E-value/score/bias, exp, N, name), a blank
@@ -102,15 +108,16 @@ def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets, domains=None, l
     With <domains> ({name: [domain records]}, see domain_entries; lengths: {name: residues}; a row may carry the
     unrounded score as a fifth element, for the E-values) they hold the
     i-Evalue, score and bias of the pair's best domain (the highest envelope score), N is the number of reportable
-    domains (incE / incdomE decide the '!' marks), and HMMER's "Domain annotation for each sequence" section (its ">> name" tables, as under --noali) follows."""
+    domains (incE / incdomE decide the '!' marks), and HMMER's "Domain annotation for each sequence" section (its ">> name" tables, as under --noali) follows.
+    passed: the stage counts and thresholds of a filtered search (_hmmsearch_tail); None under --max."""
     if domains is not None:
-        return _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE)
+        return _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE, passed)
     out, namew = _hmmsearch_head(hmm_path, fasta_path, hdr, rows)
     for name, bits, bias, ndom in sorted(rows, key=lambda r: -r[1]):
         ev = forward_evalue(bits, n_targets, hdr["ftau"], hdr["flambda"])
         out.append("  %s %6.1f %5.1f  %s %6.1f %5.1f  %5.1f %2d  %-*s " %
                    (_g(ev), bits, bias, _g(ev), bits, bias, float(max(ndom, 1)), max(ndom, 1), namew, name))
-    return _hmmsearch_tail(out, hdr, n_targets)
+    return _hmmsearch_tail(out, hdr, n_targets, passed)
 
 
 # ------------------------------------------------------------------------------------------------ per-domain output
@@ -226,7 +233,7 @@ def format_domain_table(name, entries, M, L):
     return out
 
 
-def _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE):
+def _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE, passed=None):
     entries = domain_entries(hdr, rows, lengths, domains, n_targets, Z, domZ, domE, incE, incdomE)
     by_name = {}
     for e in entries:
@@ -251,7 +258,7 @@ def _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domain
     out.append("Domain annotation for each sequence:")
     for row in order:
         out.extend(format_domain_table(row[0], by_name.get(row[0], []), hdr["M"], lengths[row[0]]))
-    return _hmmsearch_tail(out, hdr, n_targets)
+    return _hmmsearch_tail(out, hdr, n_targets, passed)
 
 
 def stockholm_row(seq_text, cols, M, flank_at_end=False):

@@ -69,20 +69,43 @@ def parse_hmmsearch_argv(argv):
     return opts, pos[0], pos[1]
 
 
+HMMER_F = (0.02, 1e-3, 1e-5)      # hmmsearch's default --F1 --F2 --F3
+
+
+def filter_thresholds(opts):
+    """None for a search with --max (--F1 --F2 --F3 --nobias are then ignored, as in HMMER), else (F1, F2, F3)."""
+    if "--max" in opts:
+        return None
+    F = []
+    for o, d in zip(("--F1", "--F2", "--F3"), HMMER_F):
+        try:
+            F.append(float(opts.get(o, d)))
+        except ValueError:
+            raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
+        if not F[-1] >= 0:
+            raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
+    return tuple(F)
+
+
 def check_hmmsearch_options(opts):
-    """The GPU path computes what WITCH's own command line asks for (algorithm.py:526-532):
-    `--max` (no filters) with a reporting threshold that lets every hit through.  Anything that would
-    change the reported set in HMMER (filters on, a real E-value / score cut-off, no null2) is refused
+    """The GPU path computes what WITCH's own command lines ask for (algorithm.py:526-532): a reporting threshold that
+    lets every hit through, and either `--max` (no filters) or the filtered search of WITCH's `filters` switch - the MSV,
+    Viterbi and Forward stages at --F1 --F2 --F3 (HMMER's defaults 0.02, 1e-3, 1e-5; wh_score_filtered).  ONE gap remains:
+    the bias filter is not implemented, so a filtered search must say --nobias; plain filtered search (no --max, no
+    --nobias) is refused with a message that says exactly this.  With --max the four options are ignored, as in HMMER.
+    Anything else that would change the reported set in HMMER (a real E-value / score cut-off, no null2) is refused
     with exit status 1 instead of being silently ignored.
     --domtblout FILE is written (per-domain records of wh_domains; --domE, -Z and --domZ apply to it and to the
     domain tables of the main output, whose '!' / '?' marks follow --incE and --incdomE; without --domtblout none of
     these five is read - -Z and --domZ are then not even checked, as before).  Two things stay unimplemented and are accepted as no-ops: --tblout (its exp,
     clu and ov columns need counts the scoring kernels do not export) and the alignment display (the output is always
     that of --noali)."""
-    if "--max" not in opts:
-        raise ArgError("witch-hip hmmsearch shim: only the unfiltered search (--max) is implemented; "
-                       "WITCH passes --max unless its filters are switched on")
-    for o in ("-T", "--incT", "--domT", "--incdomT", "--nonull2", "--nobias", "--cut_ga", "--cut_nc", "--cut_tc"):
+    if "--max" not in opts and "--nobias" not in opts:
+        raise ArgError("witch-hip hmmsearch shim: the filtered search is implemented without HMMER's bias filter only: "
+                       "pass --nobias (MSV, Viterbi and Forward filters at --F1 --F2 --F3), or --max (no filters; "
+                       "WITCH passes --max unless its filters are switched on)")
+    filter_thresholds(opts)
+    for o in ("-T", "--incT", "--domT", "--incdomT", "--nonull2", "--cut_ga", "--cut_nc", "--cut_tc"):
         if o in opts:
             raise ArgError("witch-hip hmmsearch shim: option %s is not supported" % o)
     for o in ("-E", "--incE", "--domE", "--incdomE"):
@@ -159,17 +182,24 @@ class GpuBackend:
             self.cache.move_to_end(rp)
         return hit[1], hit[2]
 
-    def search(self, hmm_path, records, want_domains=False):
+    def search(self, hmm_path, records, want_domains=False, filters=None):
         """records: [(name, text)] -> (header, [(name, bits, bias_bits, n_domains)] of reported sequences); with
         want_domains also {name: [domain records]}: the fields of wh_domain (EHMM.domains) and the envelope's envsc.
-        The domains cost an alignment per envelope: only a caller that prints them asks for them."""
+        The domains cost an alignment per envelope: only a caller that prints them asks for them.
+        filters=(F1, F2, F3): behind hmmsearch's acceleration filters (without the bias filter: --nobias); the stage
+        counts of the search are then in self.last_passed (n MSV, n bias, n Vit, n Fwd)."""
         from witch_amd.ehmm import pack_queries
         domains = {}
         with self.lock:
             e, hdr = self.model(hmm_path)
             seqs = [e.digitize(t.upper()) for _, t in records]     # alignment_tools.py:730-731 upper-cases
             res, offs = pack_queries(seqs)
-            deci, flags, det = e.score(res, offs, want_detail=True)
+            if filters is None:
+                deci, flags, det = e.score(res, offs, want_detail=True)
+            else:
+                deci, flags, det = e.score(res, offs, want_detail=True, filters=filters, nobias=True)
+                c = e.last_filter_counts()
+                self.last_passed = (c["msv"], c["bias"], c["vit"], c["fwd"])
             if want_domains:
                 recs, dom_off = e.domains(res, offs, flags, det)
                 for i, (name, _) in enumerate(records):
@@ -267,18 +297,21 @@ class Server:
             raise ArgError("Error: Failed to open sequence file %s for reading" % fa)
         check_hmmsearch_options(opts)
         records = formats.read_fasta(fa)
+        F = filter_thresholds(opts)
+        fkw = {} if F is None else {"filters": F}           # (a search with --max calls the backend as ever)
+        passed = lambda: None if F is None else (self.backend.last_passed, F)
         if "--domtblout" in opts:
-            hdr, rows, domains = self.backend.search(hmm, records, want_domains=True)
+            hdr, rows, domains = self.backend.search(hmm, records, want_domains=True, **fkw)
             lengths = {n: len(t) for n, t in records}
             kw = {"Z": float(opts["-Z"]) if "-Z" in opts else None, "domZ": float(opts["--domZ"]) if "--domZ" in opts else None,
                   "domE": float(opts.get("--domE", 10.0))}
             inc = {"incE": float(opts.get("--incE", 0.01)), "incdomE": float(opts.get("--incdomE", 0.01))}
-            text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records), domains=domains, lengths=lengths, **kw, **inc)
+            text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records), domains=domains, lengths=lengths, passed=passed(), **kw, **inc)
             with open(os.path.join(cwd, opts["--domtblout"]), "w") as f:
                 f.write(formats.format_domtblout(hmm, fa, hdr, rows, lengths, domains, len(records), **kw))
         else:
-            hdr, rows = self.backend.search(hmm, records)
-            text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records))
+            hdr, rows = self.backend.search(hmm, records, **fkw)
+            text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records), passed=passed())
         if "-o" in opts:
             with open(os.path.join(cwd, opts["-o"]), "w") as f:
                 f.write(text)
