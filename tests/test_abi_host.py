@@ -87,6 +87,21 @@ def test_error_codes_and_messages_without_a_device():
     assert b"wh_score" in L.wh_last_error()
 
 
+def test_knob_table_under_the_sanitizers(tmp_path):
+    """tools/knobs_check.cpp, compiled with the address and undefined-behaviour sanitizers and run as a program of its own (no
+    GPU, nothing loaded into Python): every development knob's default, set value, reset by "", clamps and ranges, the refusal
+    of an unknown name, and the 22 names that wh_ehmm_load reads from the environment."""
+    import subprocess
+    exe = str(tmp_path / "knobs_check")
+    cxx = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++", "/usr/bin/g++") if os.path.exists(c)), "c++")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-I", os.path.join(ROOT, "witch_amd", "csrc"), os.path.join(ROOT, "tools", "knobs_check.cpp"), "-o", exe]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-3000:]
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "knobs_check: ok" in r.stdout, r.stdout[-3000:]
+
+
 def test_sweep_context_is_register_passed(tmp_path):
     """The non-inlined sweeps of wh_score7.hip must receive their context struct in argument
     registers: when the aggregate stops flattening (a 17th dword, byte-sized members) the compiler

@@ -62,7 +62,7 @@ def test_new_symbols_are_declared_exported_and_bound():
     assert hasattr(EHMM, "last_long_score") and hasattr(EHMM, "last_long_align") and hasattr(EHMM, "max_query_len")
     assert QueryAlignmentEngine().long_score_pairs == 0
     for knob in ("WH_SCORE_LMAIN", "WH_NO_LONG_SCORE", "WH_LONGQ_FORCE"):
-        assert knob in header and knob in open(os.path.join(CSRC, "wh_api.hip")).read(), knob
+        assert knob in header and knob in open(os.path.join(CSRC, "wh_knobs.h")).read(), knob      # (the knobs' one table)
 
 
 @pytest.mark.parametrize("name", CASES)

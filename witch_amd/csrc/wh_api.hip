@@ -54,16 +54,7 @@ int wh_digitize(int alphabet, const char *text, int64_t n, uint8_t *out) {
 }
 
 void wh_ehmm_free(wh_ehmm *e) {
-  if (!e) return;
-  for (DevBuf *b : {&e->d_tlist, &e->d_rext, &e->d_biglist, &e->d_bigsegs, &e->d_longlist, &e->d_lqlist, &e->d_gtab, &e->d_rrecs, &e->d_rmx, &e->d_rsegs, &e->d_hmms, &e->d_tables, &e->d_nseq, &e->d_index, &e->d_lists, &e->d_counter, &e->d_scratch, &e->d_ascratch, &e->d_wscratch,
-                    &e->s_res, &e->s_off, &e->s_deci, &e->s_flags, &e->s_fwd, &e->s_det, &e->s_idx, &e->s_w,
-                    &e->s_nk, &e->s_nu, &e->s_pq, &e->s_ph, &e->s_co, &e->s_cols, &e->s_pp, &e->s_pos, &e->d_rkeys, &e->d_rorder, &e->d_rchunks, &e->d_qorder, &e->d_order, &e->d_items, &e->d_recs, &e->d_spec, &e->d_back, &e->d_cwj, &e->d_cwv, &e->d_cwn, &e->d_crow,
-                    &e->c_buf[0], &e->c_buf[1], &e->c_buf[2], &e->c_buf[3], &e->c_buf[4], &e->c_buf[5], &e->c_buf[6],
-                    &e->c_buf[7], &e->c_buf[8], &e->c_buf[9],
-                    &e->d_evp, &e->d_dom_pair, &e->d_dom_len, &e->d_env_res, &e->d_env_off, &e->d_dom_q, &e->d_dom_h, &e->d_dom_cols, &e->d_dom_pp, &e->s_dcnt, &e->s_dunl, &e->s_doff, &e->s_dom,
-                    &e->d_p2bak, &e->d_st_pairs, &e->d_st_p1spec, &e->d_st_units, &e->d_st_p3spec, &e->d_st_slabs, &e->d_st_cnt})
-    b->release();
-  filter_release(e);
+  if (!e) return;            // (a handle whose load failed half-way included: its buffers and the filter state free themselves)
   for (hipEvent_t ev : e->cls_ev) (void)hipEventDestroy(ev);
   for (auto &t : e->timers) {
     if (t.e0) (void)hipEventDestroy(t.e0);
@@ -230,42 +221,16 @@ int wh_ehmm_map(const wh_ehmm *e, int h, int32_t *map_cols) {
 
 int wh_set_option(wh_ehmm *e, const char *name, const char *value) {
   if (!e || !name) { set_error("wh_set_option: bad argument"); return WH_EINVAL; }
-  const char *v = value ? value : "";
-  const bool on = *v && strcmp(v, "0") != 0;
-  Knobs &k = e->knobs;
-  if (!strcmp(name, "WH_SCORE_KERNEL")) {
-    const int kv = *v ? atoi(v) : 7;
-    if (kv < 7 || kv > 12) { set_error("WH_SCORE_KERNEL=%s: this build has kernels 7 to 12", v); return WH_EINVAL; }
-    k.kernel = kv;
-  } else if (!strcmp(name, "WH_KEEP_LOG2")) k.keep_scale = *v ? ldexpf(1.0f, atoi(v)) : 0.f;
-  else if (!strcmp(name, "WH_SPILL_BAND")) k.spill_band = *v ? atoi(v) : 1;
-  else if (!strcmp(name, "WH_MAX_WAVES")) k.max_waves = *v ? std::max(1, std::min(16, atoi(v))) : 0;
-  else if (!strcmp(name, "WH_FORCE_SPECG")) k.force_specg = on;
-  else if (!strcmp(name, "WH_NO_LOGSPACE")) k.no_logspace = on;
-  else if (!strcmp(name, "WH_NO_RESOLVE")) k.no_resolve = on;
-  else if (!strcmp(name, "WH_NO_LONG_LIST")) k.no_long_list = on;
-  else if (!strcmp(name, "WH_NO_BIG_REGION")) k.no_big_region = on;
-  else if (!strcmp(name, "WH_NO_LONG_QUERY")) k.no_long_query = on;
-  else if (!strcmp(name, "WH_SCORE_LMAIN")) k.score_lmain = *v ? std::max(0, atoi(v)) : 0;
-  else if (!strcmp(name, "WH_NO_LONG_SCORE")) k.no_long_score = on;
-  else if (!strcmp(name, "WH_LONGQ_FORCE")) k.longq_force = on;
-  else if (!strcmp(name, "WH_NO_WINDOW")) k.no_window = on;
-  else if (!strcmp(name, "WH_NO_P2WIN")) k.no_p2win = on;
-  else if (!strcmp(name, "WH_RQUEUE_CAP")) k.rqueue_cap = *v ? std::max(1, atoi(v)) : 0;
-  else if (!strcmp(name, "WH_ITEM_G")) k.item_g = *v ? std::max(1, std::min(1024, atoi(v))) : 0;
-  else if (!strcmp(name, "WH_ST_UNITS")) k.st_units = *v ? std::max(16, atoi(v)) : 0;
-  else if (!strcmp(name, "WH_NO_WIDE_ALIGN")) k.no_wide_align = on;
-  else if (!strcmp(name, "WH_STATS")) k.stats = on;
-  else if (!strcmp(name, "WH_TRACE")) k.trace = on;
-  else if (!strcmp(name, "WH_DBG")) k.dbg = atoi(v);
-  else if (!strcmp(name, "WH_RDBG")) k.rdbg = atoi(v);
-  else { set_error("wh_set_option: unknown option %s", name); return WH_EINVAL; }
+  const int set = set_knob(e->knobs, name, value);
+  if (set < 0) { set_error("%s=%s: this build has kernels 7 to 12", name, value ? value : ""); return WH_EINVAL; }      // (WH_SCORE_KERNEL: the one knob with a range)
+  if (!set) { set_error("wh_set_option: unknown option %s", name); return WH_EINVAL; }
   return WH_OK;
 }
 
 static void knobs_from_env(wh_ehmm *e) {
-  for (const char *name : {"WH_SCORE_KERNEL", "WH_ITEM_G", "WH_ST_UNITS", "WH_KEEP_LOG2", "WH_MAX_WAVES", "WH_FORCE_SPECG", "WH_NO_LOGSPACE", "WH_NO_RESOLVE", "WH_NO_LONG_LIST", "WH_NO_BIG_REGION", "WH_NO_LONG_QUERY", "WH_SCORE_LMAIN", "WH_NO_LONG_SCORE", "WH_LONGQ_FORCE", "WH_NO_WINDOW", "WH_NO_P2WIN", "WH_RQUEUE_CAP", "WH_NO_WIDE_ALIGN", "WH_STATS", "WH_TRACE", "WH_DBG", "WH_RDBG"})
-    if (const char *v = getenv(name)) (void)wh_set_option(e, name, v);
+  for (const KnobEntry &k : kKnobs)
+    if (k.from_env)
+      if (const char *v = getenv(k.name)) (void)wh_set_option(e, k.name, v);
 }
 
 int wh_set_timing(wh_ehmm *e, int enabled) {
@@ -401,8 +366,7 @@ int wh_merge_sharded(int device, const uint8_t *q_text, const int64_t *q_off, in
   if (g_device < 0 && wh_init(device) != WH_OK) return WH_EHIP;
   HIPCHK(hipSetDevice(device));
   // the merge needs no model: its device buffers live for this call only
-  struct Bufs { DevBuf b[12]; ~Bufs() { for (DevBuf &x : b) x.release(); } } bufs;
-  DevBuf *m_buf = bufs.b;
+  DevBuf m_buf[12];
   const int64_t total = nq > 0 ? q_off[nq] : 0;
   std::vector<int64_t> row_q;
   for (int64_t q = 0; q < nq; q++) {
@@ -455,38 +419,23 @@ int wh_merge_sharded(int device, const uint8_t *q_text, const int64_t *q_off, in
   return WH_OK;
 }
 
-static int max_query_len(const int64_t *offsets, int64_t nq) {
-  int64_t m = 0;
-  for (int64_t i = 0; i < nq; i++) m = std::max(m, offsets[i + 1] - offsets[i]);
-  return (int)m;
-}
-
 int wh_score(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, int32_t *decibits,
              uint8_t *flags, float *fwd_bits, wh_pair_detail *detail) {
   if (!e || !residues || !offsets || !decibits || !flags || nq < 0) { set_error("wh_score: bad argument"); return WH_EINVAL; }
   if (nq == 0) return WH_OK;
   HIPCHK(hipSetDevice(e->device));
-  const int H = (int)e->hmms.size();
   const int64_t total = offsets[nq];
-  for (int64_t i = 0; i < total; i++)
-    if (residues[i] >= e->Kp) { set_error("residue code %d at position %lld is not in the alphabet", residues[i], (long long)i); return WH_EINVAL; }
-  const size_t np = (size_t)nq * H;
-  if (e->s_res.ensure((size_t)total + 16) || e->s_off.ensure(sizeof(int64_t) * (size_t)(nq + 1)) ||
-      e->s_deci.ensure(sizeof(int32_t) * np) || e->s_flags.ensure(np) ||
-      (fwd_bits && e->s_fwd.ensure(sizeof(float) * np)) || (detail && e->s_det.ensure(sizeof(wh_pair_detail) * np)))
-    return WH_ENOMEM;
-  HIPCHK(hipMemcpy(e->s_res.p, residues, (size_t)total, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_off.p, offsets, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice));
-  int rc = wh_score_dev(e, (const uint8_t *)e->s_res.p, (const int64_t *)e->s_off.p, nq, total, max_query_len(offsets, nq),
-                        (int32_t *)e->s_deci.p, (uint8_t *)e->s_flags.p, fwd_bits ? (float *)e->s_fwd.p : nullptr,
-                        detail ? (wh_pair_detail *)e->s_det.p : nullptr, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(decibits, e->s_deci.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(flags, e->s_flags.p, np, hipMemcpyDeviceToHost));
-  if (fwd_bits) HIPCHK(hipMemcpy(fwd_bits, e->s_fwd.p, sizeof(float) * np, hipMemcpyDeviceToHost));
-  if (detail) HIPCHK(hipMemcpy(detail, e->s_det.p, sizeof(wh_pair_detail) * np, hipMemcpyDeviceToHost));
-  return WH_OK;
+  if (check_residues(e->Kp, residues, total)) return WH_EINVAL;
+  const size_t np = (size_t)nq * e->hmms.size();
+  Staging st(e);
+  const uint8_t *d_res = st.in(residues, (size_t)total, 16);
+  const int64_t *d_off = st.in(offsets, sizeof(int64_t) * (size_t)(nq + 1));
+  int32_t *d_deci = st.out(decibits, sizeof(int32_t) * np);
+  uint8_t *d_flags = st.out(flags, np);
+  float *d_fwd = st.out(fwd_bits, sizeof(float) * np);
+  wh_pair_detail *d_det = st.out(detail, sizeof(wh_pair_detail) * np);
+  if (st.rc) return st.rc;
+  return st.finish(wh_score_dev(e, d_res, d_off, nq, total, max_query_len(offsets, nq), d_deci, d_flags, d_fwd, d_det, nullptr));
 }
 
 // ------------------------------------------------------------------------------------ top-k
@@ -515,20 +464,15 @@ int wh_topk(wh_ehmm *e, const int32_t *decibits, const uint8_t *flags, int64_t n
   if (nq == 0) return WH_OK;
   HIPCHK(hipSetDevice(e->device));
   const size_t np = (size_t)nq * e->hmms.size(), nk = (size_t)nq * (size_t)k;
-  if (e->s_deci.ensure(sizeof(int32_t) * np) || e->s_flags.ensure(np) || e->s_idx.ensure(sizeof(int32_t) * nk) ||
-      e->s_w.ensure(sizeof(double) * nk) || e->s_nk.ensure(sizeof(int32_t) * (size_t)nq) || e->s_nu.ensure(sizeof(int32_t) * (size_t)nq))
-    return WH_ENOMEM;
-  HIPCHK(hipMemcpy(e->s_deci.p, decibits, sizeof(int32_t) * np, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_flags.p, flags, np, hipMemcpyHostToDevice));
-  int rc = wh_topk_dev(e, (const int32_t *)e->s_deci.p, (const uint8_t *)e->s_flags.p, nq, k, (int32_t *)e->s_idx.p,
-                       (double *)e->s_w.p, (int32_t *)e->s_nk.p, (int32_t *)e->s_nu.p, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(idx, e->s_idx.p, sizeof(int32_t) * nk, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(w, e->s_w.p, sizeof(double) * nk, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(n_kept, e->s_nk.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(n_used, e->s_nu.p, sizeof(int32_t) * (size_t)nq, hipMemcpyDeviceToHost));
-  return WH_OK;
+  Staging st(e);
+  const int32_t *d_deci = st.in(decibits, sizeof(int32_t) * np);
+  const uint8_t *d_flags = st.in(flags, np);
+  int32_t *d_idx = st.out(idx, sizeof(int32_t) * nk);
+  double *d_w = st.out(w, sizeof(double) * nk);
+  int32_t *d_nk = st.out(n_kept, sizeof(int32_t) * (size_t)nq);
+  int32_t *d_nu = st.out(n_used, sizeof(int32_t) * (size_t)nq);
+  if (st.rc) return st.rc;
+  return st.finish(wh_topk_dev(e, d_deci, d_flags, nq, k, d_idx, d_w, d_nk, d_nu, nullptr));
 }
 
 int wh_align(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
@@ -559,34 +503,22 @@ static int align_host(wh_ehmm *e, const uint8_t *residues, const int64_t *offset
   if (npairs == 0) return WH_OK;
   HIPCHK(hipSetDevice(e->device));
   const int64_t total = offsets[nq];
-  for (int64_t i = 0; i < total; i++)
-    if (residues[i] >= e->Kp) { set_error("residue code %d at position %lld is not in the alphabet", residues[i], (long long)i); return WH_EINVAL; }
+  if (check_residues(e->Kp, residues, total)) return WH_EINVAL;
   for (int64_t p = 0; p < npairs; p++)
     if (pair_q[p] < 0 || pair_q[p] >= nq) { set_error("pair %lld: query %lld out of range", (long long)p, (long long)pair_q[p]); return WH_EINVAL; }
   const int64_t ncols = col_offsets[npairs];
-  if (e->s_res.ensure((size_t)total + 16) || e->s_off.ensure(sizeof(int64_t) * (size_t)(nq + 1)) ||
-      e->s_pq.ensure(sizeof(int64_t) * (size_t)npairs) || e->s_ph.ensure(sizeof(int32_t) * (size_t)npairs) ||
-      e->s_co.ensure(sizeof(int64_t) * (size_t)(npairs + 1)) || e->s_cols.ensure(sizeof(int32_t) * (size_t)ncols + 16) ||
-      (pp && e->s_pp.ensure(ppw * (size_t)ncols + 16)))
-    return WH_ENOMEM;
-  HIPCHK(hipMemcpy(e->s_res.p, residues, (size_t)total, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_off.p, offsets, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_pq.p, pair_q, sizeof(int64_t) * (size_t)npairs, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_ph.p, pair_h, sizeof(int32_t) * (size_t)npairs, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_co.p, col_offsets, sizeof(int64_t) * (size_t)(npairs + 1), hipMemcpyHostToDevice));
-  if (pp) HIPCHK(hipMemcpy(e->s_pp.p, pp, ppw * (size_t)ncols, hipMemcpyHostToDevice));   // what lies between the pairs' ranges comes back as given
-  int rc = pp_is64 && pp
-      ? wh_align_pp64_dev(e, (const uint8_t *)e->s_res.p, (const int64_t *)e->s_off.p, nq, total, max_query_len(offsets, nq),
-                          (const int64_t *)e->s_pq.p, (const int32_t *)e->s_ph.p, npairs, (const int64_t *)e->s_co.p,
-                          (int32_t *)e->s_cols.p, (double *)e->s_pp.p, nullptr)
-      : wh_align_pp_dev(e, (const uint8_t *)e->s_res.p, (const int64_t *)e->s_off.p, nq, total, max_query_len(offsets, nq),
-                        (const int64_t *)e->s_pq.p, (const int32_t *)e->s_ph.p, npairs, (const int64_t *)e->s_co.p,
-                        (int32_t *)e->s_cols.p, pp ? (float *)e->s_pp.p : nullptr, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(cols, e->s_cols.p, sizeof(int32_t) * (size_t)ncols, hipMemcpyDeviceToHost));
-  if (pp) HIPCHK(hipMemcpy(pp, e->s_pp.p, ppw * (size_t)ncols, hipMemcpyDeviceToHost));
-  return WH_OK;
+  const int max_len = max_query_len(offsets, nq);
+  Staging st(e);
+  const uint8_t *d_res = st.in(residues, (size_t)total, 16);
+  const int64_t *d_off = st.in(offsets, sizeof(int64_t) * (size_t)(nq + 1));
+  const int64_t *d_pq = st.in(pair_q, sizeof(int64_t) * (size_t)npairs);
+  const int32_t *d_ph = st.in(pair_h, sizeof(int32_t) * (size_t)npairs);
+  const int64_t *d_co = st.in(col_offsets, sizeof(int64_t) * (size_t)(npairs + 1));
+  int32_t *d_cols = st.out(cols, sizeof(int32_t) * (size_t)ncols, 16);
+  void *d_pp = st.inout(pp, ppw * (size_t)ncols, 16);      // what lies between the pairs' ranges comes back as given
+  if (st.rc) return st.rc;
+  return st.finish(pp_is64 && pp ? wh_align_pp64_dev(e, d_res, d_off, nq, total, max_len, d_pq, d_ph, npairs, d_co, d_cols, (double *)d_pp, nullptr)
+                                 : wh_align_pp_dev(e, d_res, d_off, nq, total, max_len, d_pq, d_ph, npairs, d_co, d_cols, (float *)d_pp, nullptr));
 }
 
 // ------------------------------------------------------------------------------------ consensus
@@ -663,25 +595,21 @@ int wh_consensus(wh_ehmm *e, const int64_t *offsets, int64_t nq, const int64_t *
     }
   for (int64_t t = 0; t < nret; t++)
     if (retained[t] < 0 || retained[t] >= backbone_length) { set_error("retained column %d outside the backbone", retained[t]); return WH_EINVAL; }
-  const void *src[10] = {offsets, qpair_off, pair_h, pair_w, col_offsets, cols, ret_off, retained, nongaps, nullptr};
-  const size_t bytes[10] = {sizeof(int64_t) * (size_t)(nq + 1), sizeof(int64_t) * (size_t)(nq + 1), sizeof(int32_t) * (size_t)npairs,
-                            sizeof(double) * (size_t)npairs, sizeof(int64_t) * (size_t)(npairs + 1), sizeof(int32_t) * (size_t)ncols,
-                            sizeof(int64_t) * (size_t)(H + 1), sizeof(int32_t) * (size_t)nret, sizeof(int32_t) * (size_t)nret,
-                            sizeof(int32_t) * (size_t)(total + 2 * nq)};
-  for (int t = 0; t < 10; t++) {
-    if (e->c_buf[t].ensure(bytes[t] + 16)) return WH_ENOMEM;
-    if (src[t] && bytes[t]) HIPCHK(hipMemcpy(e->c_buf[t].p, src[t], bytes[t], hipMemcpyHostToDevice));
-  }
-  int32_t *d_out = (int32_t *)e->c_buf[9].p, *d_mm = d_out + total;
-  int rc = wh_consensus_dev(e, (const int64_t *)e->c_buf[0].p, nq, max_query_len(offsets, nq), (const int64_t *)e->c_buf[1].p,
-                            (const int32_t *)e->c_buf[2].p, (const double *)e->c_buf[3].p, (const int64_t *)e->c_buf[4].p,
-                            (const int32_t *)e->c_buf[5].p, (const int64_t *)e->c_buf[6].p, (const int32_t *)e->c_buf[7].p,
-                            (const int32_t *)e->c_buf[8].p, backbone_length, maxpp, d_out, d_mm, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(out, d_out, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(minmax, d_mm, sizeof(int32_t) * (size_t)(2 * nq), hipMemcpyDeviceToHost));
-  return WH_OK;
+  Staging st(e);
+  const int64_t *d_off = st.in(offsets, sizeof(int64_t) * (size_t)(nq + 1), 16);
+  const int64_t *d_qpo = st.in(qpair_off, sizeof(int64_t) * (size_t)(nq + 1), 16);
+  const int32_t *d_ph = st.in(pair_h, sizeof(int32_t) * (size_t)npairs, 16);
+  const double *d_pw = st.in(pair_w, sizeof(double) * (size_t)npairs, 16);
+  const int64_t *d_co = st.in(col_offsets, sizeof(int64_t) * (size_t)(npairs + 1), 16);
+  const int32_t *d_cols = st.in(cols, sizeof(int32_t) * (size_t)ncols, 16);
+  const int64_t *d_ro = st.in(ret_off, sizeof(int64_t) * (size_t)(H + 1), 16);
+  const int32_t *d_ret = st.in(retained, sizeof(int32_t) * (size_t)nret, 16);
+  const int32_t *d_ng = st.in(nongaps, sizeof(int32_t) * (size_t)nret, 16);
+  int32_t *d_out = st.out(out, sizeof(int32_t) * (size_t)total, 16);
+  int32_t *d_mm = st.out(minmax, sizeof(int32_t) * (size_t)(2 * nq), 16);
+  if (st.rc) return st.rc;
+  return st.finish(wh_consensus_dev(e, d_off, nq, max_query_len(offsets, nq), d_qpo, d_ph, d_pw, d_co, d_cols, d_ro, d_ret, d_ng, backbone_length, maxpp,
+                                    d_out, d_mm, nullptr));
 }
 
 // The length up to which queries stay on the float32 kernels, from the planner's own functions (wh_plan.h): the largest

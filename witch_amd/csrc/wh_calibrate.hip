@@ -25,11 +25,10 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/witch_hip.h"
 #include "wh_calibrate.h"
+#include "wh_devbuf.h"
 
 namespace wh {
-void set_error(const char *fmt, ...);
 
 using namespace whc;
 
@@ -125,21 +124,6 @@ __global__ __launch_bounds__(kThreads) void calib_kernel(CalibArgs a) {
   }
 }
 
-struct DevMem {
-  void *p = nullptr;
-  ~DevMem() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-
-#define CALCHK(expr)                                                                                        \
-  do {                                                                                                      \
-    hipError_t _e = (expr);                                                                                 \
-    if (_e != hipSuccess) {                                                                                 \
-      set_error("wh_hmmbuild_batch: %s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return WH_EHIP;                                                                                       \
-    }                                                                                                       \
-  } while (0)
-
 struct Stream {
   hipStream_t s = nullptr;
   ~Stream() { if (s) (void)hipStreamDestroy(s); }
@@ -153,7 +137,7 @@ int calibrate_device(int device, int n, const CalibPrep *preps, const CalibSeqs 
     set_error("wh_hmmbuild_batch: no HIP device %d (%d visible; device < 0 calibrates on the host)", device, ndev);
     return WH_ENODEV;
   }
-  CALCHK(hipSetDevice(device));
+  HIPCHK(hipSetDevice(device));
   // ---- the budget of one group: rows and tables of its models
   size_t budget = (size_t)1 << 30;
   if (const char *env = getenv("WH_CALIB_WS_MB")) {
@@ -161,7 +145,7 @@ int calibrate_device(int device, int n, const CalibPrep *preps, const CalibSeqs 
     if (mb > 0) budget = (size_t)mb << 20;
   }
   size_t free_b = 0, total_b = 0;
-  CALCHK(hipMemGetInfo(&free_b, &total_b));
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
   if (budget > free_b / 2) budget = free_b / 2;
   std::vector<size_t> need((size_t)n);
   for (int i = 0; i < n; i++) {
@@ -189,26 +173,25 @@ int calibrate_device(int device, int n, const CalibPrep *preps, const CalibSeqs 
   int gmax = 0;
   for (size_t g = 0; g + 1 < first.size(); g++) gmax = std::max(gmax, first[g + 1] - first[g]);
   // ---- device memory: one block for rows and tables, the sequences, the descriptors, the results
-  DevMem d_blk, d_seq, d_desc, d_res;
+  DevBuf d_blk, d_seq, d_desc, d_res;
   Stream st;
   size_t seq_off[3], seq_bytes = 0;
   for (int ph = 0; ph < 3; ph++) { seq_off[ph] = seq_bytes; seq_bytes += up256((size_t)(seqs.L[ph] + 1) * kCalibN); }
   const size_t res_int = up256((size_t)gmax * kCalibN * sizeof(int)), res_dbl = up256((size_t)gmax * kCalibN * sizeof(double));
-  if (d_blk.alloc(biggest) != hipSuccess || d_seq.alloc(seq_bytes) != hipSuccess || d_desc.alloc((size_t)gmax * sizeof(CalibDesc)) != hipSuccess ||
-      d_res.alloc(3 * res_int + res_dbl) != hipSuccess) {
+  if (d_blk.ensure(biggest) || d_seq.ensure(seq_bytes) || d_desc.ensure((size_t)gmax * sizeof(CalibDesc)) || d_res.ensure(3 * res_int + res_dbl)) {
     set_error("wh_hmmbuild_batch: hipMalloc of the calibration workspace failed (%zu bytes for the largest of %zu groups, %zu bytes free)",
               biggest, first.size() - 1, free_b);
     return WH_ENOMEM;
   }
-  CALCHK(hipStreamCreate(&st.s));
-  CALCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&calib_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
+  HIPCHK(hipStreamCreate(&st.s));
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&calib_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
   {
     std::vector<uint8_t> t(seq_bytes, 0);      // sequence-major on the host, residue-major (lanes adjacent) on the device
     for (int ph = 0; ph < 3; ph++)
       for (int s = 0; s < kCalibN; s++)
         for (int i = 1; i <= seqs.L[ph]; i++) t[seq_off[ph] + (size_t)i * kCalibN + (size_t)s] = seqs.seq(ph, s)[i];
-    CALCHK(hipMemcpyAsync(d_seq.p, t.data(), seq_bytes, hipMemcpyHostToDevice, st.s));
-    CALCHK(hipStreamSynchronize(st.s));
+    HIPCHK(hipMemcpyAsync(d_seq.p, t.data(), seq_bytes, hipMemcpyHostToDevice, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
   }
   std::vector<unsigned char> tab;
   std::vector<CalibDesc> desc;
@@ -244,8 +227,8 @@ int calibrate_device(int device, int n, const CalibPrep *preps, const CalibSeqs 
       if (d.lds) lds = std::max(lds, lds_bytes(M, K));
     }
     if (woff > biggest) { set_error("wh_hmmbuild_batch: internal error: group %zu needs %zu bytes, %zu were planned", g, woff, biggest); return WH_EINVAL; }
-    CALCHK(hipMemcpyAsync(d_blk.p, tab.data(), tbytes, hipMemcpyHostToDevice, st.s));
-    CALCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)cnt * sizeof(CalibDesc), hipMemcpyHostToDevice, st.s));
+    HIPCHK(hipMemcpyAsync(d_blk.p, tab.data(), tbytes, hipMemcpyHostToDevice, st.s));
+    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)cnt * sizeof(CalibDesc), hipMemcpyHostToDevice, st.s));
     CalibArgs a;
     a.desc = (const CalibDesc *)d_desc.p;
     a.tables = (const unsigned char *)d_blk.p;
@@ -256,14 +239,14 @@ int calibrate_device(int device, int n, const CalibPrep *preps, const CalibSeqs 
     a.nscale = (int *)((char *)d_res.p + 2 * res_int);
     a.fwd = (double *)((char *)d_res.p + 3 * res_int);
     hipLaunchKernelGGL(calib_kernel, dim3(3, (unsigned)cnt), dim3(kThreads), lds, st.s, a);
-    CALCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     const size_t nres = (size_t)cnt * kCalibN;
     h_ns.resize(nres); h_fwd.resize(nres);
-    CALCHK(hipMemcpyAsync(msv + (size_t)lo * kCalibN, a.msv, nres * sizeof(int), hipMemcpyDeviceToHost, st.s));
-    CALCHK(hipMemcpyAsync(vit + (size_t)lo * kCalibN, a.vit, nres * sizeof(int), hipMemcpyDeviceToHost, st.s));
-    CALCHK(hipMemcpyAsync(h_ns.data(), a.nscale, nres * sizeof(int), hipMemcpyDeviceToHost, st.s));
-    CALCHK(hipMemcpyAsync(h_fwd.data(), a.fwd, nres * sizeof(double), hipMemcpyDeviceToHost, st.s));
-    CALCHK(hipStreamSynchronize(st.s));
+    HIPCHK(hipMemcpyAsync(msv + (size_t)lo * kCalibN, a.msv, nres * sizeof(int), hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipMemcpyAsync(vit + (size_t)lo * kCalibN, a.vit, nres * sizeof(int), hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipMemcpyAsync(h_ns.data(), a.nscale, nres * sizeof(int), hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipMemcpyAsync(h_fwd.data(), a.fwd, nres * sizeof(double), hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
     // the Forward scores: the logarithms are the host's; the rescale factors are fetched only where a sweep rescaled
     for (int i = lo; i < lo + cnt; i++) {
       const int M = preps[i].msv.M;
@@ -273,7 +256,7 @@ int calibrate_device(int device, int n, const CalibPrep *preps, const CalibSeqs 
       if (any) {
         h_sc.resize((size_t)kCalibEfL * kCalibN);
         const size_t off = desc[(size_t)(i - lo)].ws + ws_msv_bytes(M) + ws_vit_bytes(M) + ws_fwd_bytes(M);
-        CALCHK(hipMemcpy(h_sc.data(), (char *)d_blk.p + off, h_sc.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_sc.data(), (char *)d_blk.p + off, h_sc.size() * sizeof(double), hipMemcpyDeviceToHost));
       }
       for (int s = 0; s < kCalibN; s++)
         fwd[(size_t)i * kCalibN + (size_t)s] = calib_forward_score(h_fwd[(size_t)(i - lo) * kCalibN + (size_t)s], any ? h_sc.data() + s : nullptr, kCalibN, ns[s]);

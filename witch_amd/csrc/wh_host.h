@@ -1,6 +1,7 @@
 // Internal header of the host side of libwitch_hip.so: what wh_api.hip (handles, options, getters, host-pointer entry
-// points), wh_host_score.hip (wh_score_dev), wh_host_resolve.hip (its resolver stage), wh_host_align.hip (wh_align_dev) and
-// wh_host_domains.hip (wh_domains_dev) share.  No kernel file includes it.
+// points), wh_host_score.hip (wh_score_dev), wh_host_resolve.hip (its resolver stage), wh_host_align.hip (wh_align_dev),
+// wh_host_domains.hip (wh_domains_dev) and wh_host_filter.hip (the filters) share: the handle, the d_counter slots, the
+// staging of the host-pointer entry points.  No kernel file includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,8 +11,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <vector>
 
+#include "wh_devbuf.h"
+#include "wh_knobs.h"
 #include "wh_launch.h"
 #include "wh_plan.h"
 
@@ -21,66 +25,11 @@ const char *last_error();
 
 using namespace wh;
 
-#define HIPCHK(expr)                                                                  \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    if (_e != hipSuccess) {                                                           \
-      set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return WH_EHIP;                                                                 \
-    }                                                                                 \
-  } while (0)
-
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return WH_OK;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    size_t want = bytes + bytes / 8 + 256;
-    if (hipMalloc(&p, want) != hipSuccess) {
-      set_error("hipMalloc of %zu bytes failed", want);
-      return WH_ENOMEM;
-    }
-    cap = want;
-    return WH_OK;
-  }
-  void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
-};
-
 struct KernelTimer {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   double ms = 0.0;
   int launches = 0;
   bool pending = false;
-};
-
-// Development knobs.  Read from the environment ONCE, at wh_ehmm_load;
-// wh_set_option changes them on a live handle (tools/ab_score.py).  None is needed in production.
-struct Knobs {
-  int kernel = 7;            // 7 phase-call scoring kernel (one query per wavefront); 8 its second compilation (A/B slot);
-                             // 9 two queries per wavefront where a batch fits (wh_score9.hip; measured slower, kept for A/B: DESIGN.md);
-                             // 10 staged launches (wh_staged.hip) for the size classes and batches they serve, 7 for the rest
-  float keep_scale = 0.f;    // Forward-row spill threshold relative to E(row); 0 = the kernel's default
-  int spill_band = 1;        // 0: envelope Forward rows stored at every lane block that passes keep_scale (A/B; the two-query kernel has no band)
-  int max_waves = 0;         // cap on waves per workgroup (0 = planner's choice)
-  bool force_specg = false;  // force the HBM special-state mode
-  bool no_logspace = false;  // skip the log-space alignment pass
-  bool no_wide_align = false; // models beyond 3 072 nodes are aligned by the float64 kernel only (A/B and debugging)
-  bool no_window = false;    // envelope Backward sweeps run full width (no node window; A/B and debugging)
-  bool no_p2win = false;     // the multihit Backward sweep runs full width only (A/B and debugging)
-  bool no_long_list = false; // WH_NO_LONG_LIST: pairs with more than WH_MAX_ENVELOPES regions keep WH_FLAG_TRUNC (no second pass; tests)
-  bool no_big_region = false; // WH_NO_BIG_REGION: a region with more domains, segments or clusters than the resolver's lists hold keeps WH_FLAG_TRUNC (no big-region pass; tests)
-  bool no_long_query = false; // WH_NO_LONG_QUERY: a call whose longest query exceeds the resolver's LDS cap runs without the resolver, as before the long-query pass (tests)
-  bool no_resolve = false;   // multidomain regions stay ONE envelope (round-1 behaviour) instead of HMMER's stochastic resolver
-  int score_lmain = 0;       // WH_SCORE_LMAIN=<n>: the main length cap of scoring and alignment calls is at most n (tests: reaches the long-query scoring and alignment passes with short queries)
-  bool no_long_score = false; // WH_NO_LONG_SCORE: no long-query scoring / alignment pass - a call with a query beyond a class's LDS plan is refused (WH_ERANGE), as before the pass
-  bool longq_force = false;  // WH_LONGQ_FORCE: the passes run the float64 kernels' residues-in-HBM instantiations whatever the length (tests)
-  int rqueue_cap = 0;        // test hook: size the resolver's queue for this many pairs instead of the estimate (forces the overflow re-run)
-  int item_g = 0;            // queries per wave in a work item of the phase-call kernels (0 = 32; A/B)
-  int st_units = 0;          // staged launches: envelope units (Forward slabs) per batch (0 = sized from the free HBM)
-  bool stats = false, trace = false;
-  int dbg = 0;
-  int rdbg = 0;              // resolver: print the first <n> sampled segments and the cluster statistics of every region
 };
 
 // ---- d_counter: 256 ints in HBM, zeroed at load.  Every owner of a slot or range, in one place: the kernels and the
@@ -117,6 +66,8 @@ static_assert(kSlotScorePath + kScorePathInts <= kSlotWideScore && kSlotWideScor
               (kSlotResolveFeedback * sizeof(int) + offsetof(ResolveFeedback, big_list)) % 8 == 0 && (kSlotResolveFeedback * sizeof(int) + offsetof(ResolveFeedback, long_list)) % 8 == 0,
               "d_counter slots overlap or leave the buffer, the resolver's feedback does not fill its range, or a list's address is not 8-byte aligned");
 
+struct FilterState;      // private to wh_host_filter.hip
+
 struct wh_ehmm {
   Knobs knobs;
   int device = 0;
@@ -147,10 +98,10 @@ struct wh_ehmm {
   int64_t last_long_align[2] = {0, 0};      // ... and the same of the last wh_align call's long-query alignment pass
   DevBuf d_lqlist;                          // long-query scoring pass: the queries beyond the main length cap (their pairs: d_tlist)
   // wh_domains_dev: Forward tau / lambda per model (NaN without the STATS line), per-domain pair and envelope length, the
-  // packed envelopes with their CSR, the alignment's pair lists, columns and posteriors; staging of the host entry points
+  // packed envelopes with their CSR, the alignment's pair lists, columns and posteriors
   std::vector<int64_t> h_env_off;           // ... host sources of asynchronous uploads: they outlive the call
   std::vector<float> h_evp;
-  DevBuf d_evp, d_dom_pair, d_dom_len, d_env_res, d_env_off, d_dom_q, d_dom_h, d_dom_cols, d_dom_pp, s_dcnt, s_dunl, s_doff, s_dom;
+  DevBuf d_evp, d_dom_pair, d_dom_len, d_env_res, d_env_off, d_dom_q, d_dom_h, d_dom_cols, d_dom_pp;
   int64_t rq_cap = 0;                       // records the queue of the current scoring call holds
   double rq_rate = 0.0;                     // largest share of queued pairs any call on this handle has seen (sizes the next queue)
   int64_t rq_floor = 0;                     // ... at least this many (set when a call overflowed its estimate; the call then runs again)
@@ -166,11 +117,16 @@ struct wh_ehmm {
   uint8_t *path_buf = nullptr;              // wh_set_path_buffer: device array [nq x H] the next scoring calls fill with WH_PATH_* bits
   uint16_t *path_buf16 = nullptr;           // wh_set_path_buffer16: the 16-bit record (its address reaches the ScoreArgs kernels that write it
                                             // through the spare slot of the path counters: kPathRecSlot, wh_launch.h)
-  // staging for the host-pointer entry points
-  DevBuf s_res, s_off, s_deci, s_flags, s_fwd, s_det, s_idx, s_w, s_nk, s_nu, s_pq, s_ph, s_co, s_cols, s_pp, s_pos;
-  DevBuf d_rkeys, d_rorder, d_rchunks, d_qorder, d_order, d_items, d_recs, d_spec, d_back, d_cwj, d_cwv, d_cwn, d_crow, c_buf[10];
+  // staging of the host-pointer entry points: the arrays of ONE call take these in call order (Staging, below); no two
+  // entry points run at once on a handle and no *_dev function reads them, so they are as many as the call with the most
+  // arrays needs (wh_consensus)
+  static const int kStagingSlots = 11;
+  DevBuf staging[kStagingSlots];
+  DevBuf d_rkeys, d_rorder, d_rchunks, d_qorder, d_order, d_items, d_recs, d_spec, d_back, d_cwj, d_cwv, d_cwn, d_crow;
   uint32_t degen[32];
-  struct FilterState *filter = nullptr;     // acceleration filters (wh_host_filter.hip): tables, per-length settings, last counts; made by the first wh_filter call
+  // acceleration filters (wh_host_filter.hip, which alone knows the type): tables, per-length settings, last counts; made by the first wh_filter call
+  struct FilterStateDelete { void operator()(FilterState *f) const; };
+  std::unique_ptr<FilterState, FilterStateDelete> filter;
   bool timing = false;
   KernelTimer timers[6];                    // wh_last_kernel_ms: 0 scoring, 1 topk, 2 align, 3 consensus, 4 resolver, 5 domain stage
   int max_M = 0;
@@ -188,8 +144,53 @@ struct wh_ehmm {
   ResolveFeedback *d_feedback() const { return (ResolveFeedback *)counter(kSlotResolveFeedback); }
 };
 
-// wh_host_filter.hip: releases e->filter (wh_ehmm_free)
-void filter_release(wh_ehmm *e);
+// ---- the host-pointer entry points (wh_score, wh_align_pp, ...): what they check and how they stage their arrays
+static inline int max_query_len(const int64_t *offsets, int64_t nq) {
+  int64_t m = 0;
+  for (int64_t i = 0; i < nq; i++) m = std::max(m, offsets[i + 1] - offsets[i]);
+  return (int)m;
+}
+// every residue code is below the alphabet's Kp
+static inline int check_residues(int Kp, const uint8_t *residues, int64_t total) {
+  for (int64_t i = 0; i < total; i++)
+    if (residues[i] >= Kp) { set_error("residue code %d at position %lld is not in the alphabet", residues[i], (long long)i); return WH_EINVAL; }
+  return WH_OK;
+}
+
+// The staging of one call, made on the entry point's stack: every array takes the handle's next slot (an optional array
+// that is absent takes its slot too, so that an array's slot does not depend on the options, and gives null); finish()
+// waits for the device and copies the outputs back.  The first failure is latched in <rc>: the arrays after it are null,
+// and the entry point returns it before it launches anything.  <pad>: bytes a kernel may read beyond the array's end.
+struct Staging {
+  wh_ehmm *e;
+  int rc = WH_OK, next = 0, nback = 0;
+  struct { void *host; const void *dev; size_t bytes; } back[wh_ehmm::kStagingSlots];
+  explicit Staging(wh_ehmm *handle) : e(handle) {}
+  template <class T> const T *in(const T *host, size_t bytes, size_t pad = 0) { return (const T *)take((void *)host, bytes, pad, true, false); }
+  template <class T> T *out(T *host, size_t bytes, size_t pad = 0) { return (T *)take(host, bytes, pad, false, true); }
+  template <class T> T *inout(T *host, size_t bytes, size_t pad = 0) { return (T *)take(host, bytes, pad, true, true); }
+  // <dev_rc>: what the *_dev function returned (a failure goes back as it is, without waiting for the device)
+  int finish(int dev_rc) {
+    if (dev_rc || rc) return dev_rc ? dev_rc : rc;
+    HIPCHK(hipDeviceSynchronize());
+    for (int t = 0; t < nback; t++)
+      if (back[t].bytes) HIPCHK(hipMemcpy(back[t].host, back[t].dev, back[t].bytes, hipMemcpyDeviceToHost));
+    return WH_OK;
+  }
+ private:
+  void *take(void *host, size_t bytes, size_t pad, bool upload, bool download) {
+    if (next >= wh_ehmm::kStagingSlots) { if (!rc) { set_error("internal error: a call stages more than %d arrays", wh_ehmm::kStagingSlots); rc = WH_EINVAL; } return nullptr; }
+    DevBuf &b = e->staging[next++];
+    if (!host || rc) return nullptr;
+    if ((rc = b.ensure(bytes + pad))) return nullptr;
+    if (upload && bytes) {
+      const hipError_t err = hipMemcpy(b.p, host, bytes, hipMemcpyHostToDevice);
+      if (err != hipSuccess) { set_error("hipMemcpy of %zu bytes to the device failed: %s", bytes, hipGetErrorString(err)); rc = WH_EHIP; return nullptr; }
+    }
+    if (download) { back[nback].host = host; back[nback].dev = b.p; back[nback].bytes = bytes; nback++; }
+    return b.p;
+  }
+};
 
 // one event per scoring launch (timing mode only); events are created once and reused
 static inline int class_mark(wh_ehmm *e, hipStream_t s, int Q, int kind) {

@@ -4,12 +4,6 @@
 
 #include "wh_host.h"
 
-static int max_query_len(const int64_t *offsets, int64_t nq) {
-  int64_t m = 0;
-  for (int64_t i = 0; i < nq; i++) m = std::max(m, offsets[i + 1] - offsets[i]);
-  return (int)m;
-}
-
 extern "C" {
 
 int wh_ehmm_evparams(const wh_ehmm *e, float *tau, float *lambda, int32_t *present) {
@@ -135,18 +129,13 @@ int wh_domain_counts(wh_ehmm *e, const uint8_t *flags, const wh_pair_detail *det
   if (nq == 0) return WH_OK;
   HIPCHK(hipSetDevice(e->device));
   const size_t np = (size_t)nq * e->hmms.size();
-  if (e->s_flags.ensure(np) || e->s_det.ensure(sizeof(wh_pair_detail) * np) || e->s_dcnt.ensure(sizeof(int32_t) * np) ||
-      (n_unlisted && e->s_dunl.ensure(sizeof(int32_t) * np)))
-    return WH_ENOMEM;
-  HIPCHK(hipMemcpy(e->s_flags.p, flags, np, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_det.p, detail, sizeof(wh_pair_detail) * np, hipMemcpyHostToDevice));
-  int rc = wh_domain_counts_dev(e, (const uint8_t *)e->s_flags.p, (const wh_pair_detail *)e->s_det.p, nq, (int32_t *)e->s_dcnt.p,
-                                n_unlisted ? (int32_t *)e->s_dunl.p : nullptr, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(counts, e->s_dcnt.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
-  if (n_unlisted) HIPCHK(hipMemcpy(n_unlisted, e->s_dunl.p, sizeof(int32_t) * np, hipMemcpyDeviceToHost));
-  return WH_OK;
+  Staging st(e);
+  const uint8_t *d_flags = st.in(flags, np);
+  const wh_pair_detail *d_det = st.in(detail, sizeof(wh_pair_detail) * np);
+  int32_t *d_cnt = st.out(counts, sizeof(int32_t) * np);
+  int32_t *d_unl = st.out(n_unlisted, sizeof(int32_t) * np);
+  if (st.rc) return st.rc;
+  return st.finish(wh_domain_counts_dev(e, d_flags, d_det, nq, d_cnt, d_unl, nullptr));
 }
 
 int wh_domains(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const uint8_t *flags,
@@ -157,23 +146,16 @@ int wh_domains(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int6
   const size_t np = (size_t)nq * e->hmms.size();
   const int64_t total = offsets[nq], ndom = dom_off[np];
   if (ndom < 0 || (ndom > 0 && !out)) { set_error("wh_domains: bad argument"); return WH_EINVAL; }
-  for (int64_t i = 0; i < total; i++)
-    if (residues[i] >= e->Kp) { set_error("residue code %d at position %lld is not in the alphabet", residues[i], (long long)i); return WH_EINVAL; }
-  if (e->s_res.ensure((size_t)total + 16) || e->s_off.ensure(sizeof(int64_t) * (size_t)(nq + 1)) || e->s_flags.ensure(np) ||
-      e->s_det.ensure(sizeof(wh_pair_detail) * np) || e->s_doff.ensure(sizeof(int64_t) * (np + 1)) || e->s_dom.ensure(sizeof(wh_domain) * (size_t)ndom + 16))
-    return WH_ENOMEM;
-  HIPCHK(hipMemcpy(e->s_res.p, residues, (size_t)total, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_off.p, offsets, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_flags.p, flags, np, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_det.p, detail, sizeof(wh_pair_detail) * np, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_doff.p, dom_off, sizeof(int64_t) * (np + 1), hipMemcpyHostToDevice));
-  int rc = wh_domains_dev(e, (const uint8_t *)e->s_res.p, (const int64_t *)e->s_off.p, nq, total, max_query_len(offsets, nq),
-                          (const uint8_t *)e->s_flags.p, (const wh_pair_detail *)e->s_det.p, (const int64_t *)e->s_doff.p,
-                          (wh_domain *)e->s_dom.p, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  if (ndom > 0) HIPCHK(hipMemcpy(out, e->s_dom.p, sizeof(wh_domain) * (size_t)ndom, hipMemcpyDeviceToHost));
-  return WH_OK;
+  if (check_residues(e->Kp, residues, total)) return WH_EINVAL;
+  Staging st(e);
+  const uint8_t *d_res = st.in(residues, (size_t)total, 16);
+  const int64_t *d_off = st.in(offsets, sizeof(int64_t) * (size_t)(nq + 1));
+  const uint8_t *d_flags = st.in(flags, np);
+  const wh_pair_detail *d_det = st.in(detail, sizeof(wh_pair_detail) * np);
+  const int64_t *d_doff = st.in(dom_off, sizeof(int64_t) * (np + 1));
+  wh_domain *d_out = st.out(out, sizeof(wh_domain) * (size_t)ndom, 16);
+  if (st.rc) return st.rc;
+  return st.finish(wh_domains_dev(e, d_res, d_off, nq, total, max_query_len(offsets, nq), d_flags, d_det, d_doff, d_out, nullptr));
 }
 
 }  // extern "C"

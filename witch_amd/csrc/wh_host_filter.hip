@@ -25,20 +25,9 @@ struct FilterState {
   std::vector<uint8_t> h_keep;
   std::vector<int64_t> h_off, h_coff, h_qlist, h_qmap;
   std::vector<float> h_x3;
-  // staging of the host-pointer entry points
-  DevBuf s_stage, s_bias, s_msv, s_vit;      // wh_filter's outputs
-  DevBuf s_res, s_off;                       // wh_score_filtered's inputs (the handle's own s_res / s_off are the compacted call's)
 };
 
-void filter_release(wh_ehmm *e) {
-  FilterState *f = e->filter;
-  if (!f) return;
-  for (DevBuf *b : {&f->d_tables, &f->d_desc, &f->d_lens, &f->d_list, &f->d_ws, &f->d_counts, &f->d_stage, &f->d_bias, &f->d_keep, &f->d_qmap, &f->d_qlist,
-                    &f->d_coff, &f->d_cres, &f->d_cdeci, &f->d_cflags, &f->d_cfwd, &f->d_cdet, &f->d_x3, &f->s_stage, &f->s_bias, &f->s_msv, &f->s_vit, &f->s_res, &f->s_off})
-    b->release();
-  delete f;
-  e->filter = nullptr;
-}
+void wh_ehmm::FilterStateDelete::operator()(FilterState *f) const { delete f; }
 
 namespace {
 
@@ -65,7 +54,7 @@ int model_of(const HostHMM &h, const uint32_t *degen, FilterModel &fm) {
 
 // the handle's filter state: tables of every model on the device, the class lists
 int state_of(wh_ehmm *e, FilterState **out) {
-  if (e->filter) { *out = e->filter; return WH_OK; }
+  if (e->filter) { *out = e->filter.get(); return WH_OK; }
   std::unique_ptr<FilterState> f(new FilterState);
   const int H = (int)e->hmms.size();
   f->models.resize((size_t)H);
@@ -109,18 +98,15 @@ int state_of(wh_ehmm *e, FilterState **out) {
   std::vector<int> all;
   for (int c = 0; c < kFilterClasses; c++) { f->list_off[c] = all.size(); all.insert(all.end(), f->lists[c].begin(), f->lists[c].end()); }
   if (f->d_tables.ensure(tab.size() + 16) || f->d_desc.ensure(sizeof(FilterDevModel) * (size_t)H) || f->d_list.ensure(sizeof(int) * (all.size() + 1)) ||
-      f->d_counts.ensure(8 * sizeof(unsigned long long))) {
-    for (DevBuf *b : {&f->d_tables, &f->d_desc, &f->d_list, &f->d_counts}) b->release();
+      f->d_counts.ensure(8 * sizeof(unsigned long long)))
     return WH_ENOMEM;
-  }
   if (hipMemcpy(f->d_tables.p, tab.data(), tab.size(), hipMemcpyHostToDevice) != hipSuccess ||
       (all.size() && hipMemcpy(f->d_list.p, all.data(), sizeof(int) * all.size(), hipMemcpyHostToDevice) != hipSuccess)) {
-    for (DevBuf *b : {&f->d_tables, &f->d_desc, &f->d_list, &f->d_counts}) b->release();
     set_error("wh_filter: uploading the filter tables failed");
     return WH_EHIP;
   }
-  e->filter = f.release();
-  *out = e->filter;
+  e->filter.reset(f.release());
+  *out = e->filter.get();
   return WH_OK;
 }
 
@@ -178,12 +164,6 @@ __global__ void scatter_kernel(ScatterArgs a) {
   }
   const unsigned long long m = __ballot(pass);
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(&a.counts[4], (unsigned long long)__builtin_popcountll(m));
-}
-
-int max_len_of(const int64_t *offsets, int64_t nq) {
-  int64_t m = 0;
-  for (int64_t i = 0; i < nq; i++) m = std::max(m, offsets[i + 1] - offsets[i]);
-  return (int)m;
 }
 
 // the filters of one call; counts [0..3] are left on the device
@@ -265,25 +245,18 @@ int wh_filter(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64
   FilterState *f = nullptr;
   if ((rc = state_of(e, &f))) return rc;
   if (nq == 0) return WH_OK;
-  const int H = (int)e->hmms.size();
   const int64_t total = offsets[nq];
-  for (int64_t i = 0; i < total; i++)
-    if (residues[i] >= e->Kp) { set_error("residue code %d at position %lld is not in the alphabet", residues[i], (long long)i); return WH_EINVAL; }
-  const size_t np = (size_t)nq * H;
-  if (e->s_res.ensure((size_t)total + 16) || e->s_off.ensure(sizeof(int64_t) * (size_t)(nq + 1)) || f->s_stage.ensure(np) ||
-      (filter_bias_nats && f->s_bias.ensure(4 * np)) || (msv_raw && f->s_msv.ensure(4 * np)) || (vit_raw && f->s_vit.ensure(4 * np)))
-    return WH_ENOMEM;
-  HIPCHK(hipMemcpy(e->s_res.p, residues, (size_t)total, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(e->s_off.p, offsets, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice));
-  rc = run_filters(e, f, fo, (const uint8_t *)e->s_res.p, (const int64_t *)e->s_off.p, nq, max_len_of(offsets, nq), (uint8_t *)f->s_stage.p,
-                   filter_bias_nats ? (float *)f->s_bias.p : nullptr, msv_raw ? (int32_t *)f->s_msv.p : nullptr, vit_raw ? (int32_t *)f->s_vit.p : nullptr, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(stage, f->s_stage.p, np, hipMemcpyDeviceToHost));
-  if (filter_bias_nats) HIPCHK(hipMemcpy(filter_bias_nats, f->s_bias.p, 4 * np, hipMemcpyDeviceToHost));
-  if (msv_raw) HIPCHK(hipMemcpy(msv_raw, f->s_msv.p, 4 * np, hipMemcpyDeviceToHost));
-  if (vit_raw) HIPCHK(hipMemcpy(vit_raw, f->s_vit.p, 4 * np, hipMemcpyDeviceToHost));
-  return WH_OK;
+  if (check_residues(e->Kp, residues, total)) return WH_EINVAL;
+  const size_t np = (size_t)nq * e->hmms.size();
+  Staging st(e);
+  const uint8_t *d_res = st.in(residues, (size_t)total, 16);
+  const int64_t *d_off = st.in(offsets, sizeof(int64_t) * (size_t)(nq + 1));
+  uint8_t *d_stage = st.out(stage, np);
+  float *d_bias = st.out(filter_bias_nats, 4 * np);
+  int32_t *d_msv = st.out(msv_raw, 4 * np);
+  int32_t *d_vit = st.out(vit_raw, 4 * np);
+  if (st.rc) return st.rc;
+  return st.finish(run_filters(e, f, fo, d_res, d_off, nq, max_query_len(offsets, nq), d_stage, d_bias, d_msv, d_vit, nullptr));
 }
 
 int wh_filter_host(const char *const *hmm_paths, int n, const uint8_t *residues, const int64_t *offsets, int64_t nq, const wh_filter_opts *opts,
@@ -307,8 +280,7 @@ int wh_filter_host(const char *const *hmm_paths, int n, const uint8_t *residues,
     maxM = std::max(maxM, hm.M);
   }
   const int64_t total = offsets[nq];
-  for (int64_t i = 0; i < total; i++)
-    if (residues[i] >= Kp) { set_error("residue code %d at position %lld is not in the alphabet", residues[i], (long long)i); return WH_EINVAL; }
+  if (check_residues(Kp, residues, total)) return WH_EINVAL;
   std::vector<int16_t> rows((size_t)7 * ((size_t)maxM + 1));
   int64_t c[4] = {nq * n, 0, 0, 0};
   for (int64_t q = 0; q < nq; q++)
@@ -401,33 +373,25 @@ int wh_score_filtered(wh_ehmm *e, const uint8_t *residues, const int64_t *offset
   HIPCHK(hipSetDevice(e->device));
   FilterState *f = nullptr;
   if ((rc = state_of(e, &f))) return rc;
-  const int H = (int)e->hmms.size();
   const int64_t total = offsets[nq];
-  for (int64_t i = 0; i < total; i++)
-    if (residues[i] >= e->Kp) { set_error("residue code %d at position %lld is not in the alphabet", residues[i], (long long)i); return WH_EINVAL; }
-  const size_t np = (size_t)nq * H;
-  if (f->s_res.ensure((size_t)total + 16) || f->s_off.ensure(sizeof(int64_t) * (size_t)(nq + 1)) || e->s_deci.ensure(4 * np) || e->s_flags.ensure(np) ||
-      f->s_stage.ensure(np) || (fwd_bits && e->s_fwd.ensure(4 * np)) || (detail && e->s_det.ensure(sizeof(wh_pair_detail) * np)))
-    return WH_ENOMEM;
-  HIPCHK(hipMemcpy(f->s_res.p, residues, (size_t)total, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(f->s_off.p, offsets, sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyHostToDevice));
-  rc = wh_score_filtered_dev(e, (const uint8_t *)f->s_res.p, (const int64_t *)f->s_off.p, nq, total, max_len_of(offsets, nq), opts, (int32_t *)e->s_deci.p,
-                             (uint8_t *)e->s_flags.p, fwd_bits ? (float *)e->s_fwd.p : nullptr, detail ? (wh_pair_detail *)e->s_det.p : nullptr,
-                             (uint8_t *)f->s_stage.p, nullptr);
-  if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  HIPCHK(hipMemcpy(decibits, e->s_deci.p, 4 * np, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(flags, e->s_flags.p, np, hipMemcpyDeviceToHost));
-  if (fwd_bits) HIPCHK(hipMemcpy(fwd_bits, e->s_fwd.p, 4 * np, hipMemcpyDeviceToHost));
-  if (detail) HIPCHK(hipMemcpy(detail, e->s_det.p, sizeof(wh_pair_detail) * np, hipMemcpyDeviceToHost));
-  if (stage) HIPCHK(hipMemcpy(stage, f->s_stage.p, np, hipMemcpyDeviceToHost));
-  return WH_OK;
+  if (check_residues(e->Kp, residues, total)) return WH_EINVAL;
+  const size_t np = (size_t)nq * e->hmms.size();
+  Staging st(e);
+  const uint8_t *d_res = st.in(residues, (size_t)total, 16);
+  const int64_t *d_off = st.in(offsets, sizeof(int64_t) * (size_t)(nq + 1));
+  int32_t *d_deci = st.out(decibits, 4 * np);
+  uint8_t *d_flags = st.out(flags, np);
+  float *d_fwd = st.out(fwd_bits, 4 * np);
+  wh_pair_detail *d_det = st.out(detail, sizeof(wh_pair_detail) * np);
+  uint8_t *d_stage = st.out(stage, np);
+  if (st.rc) return st.rc;
+  return st.finish(wh_score_filtered_dev(e, d_res, d_off, nq, total, max_query_len(offsets, nq), opts, d_deci, d_flags, d_fwd, d_det, d_stage, nullptr));
 }
 
 int wh_last_filter_counts(wh_ehmm *e, int64_t out[6]) {
   if (!e || !out) { set_error("wh_last_filter_counts: bad argument"); return WH_EINVAL; }
   for (int i = 0; i < 6; i++) out[i] = 0;
-  FilterState *f = e->filter;
+  FilterState *f = e->filter.get();
   if (!f) return WH_OK;
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipDeviceSynchronize());
