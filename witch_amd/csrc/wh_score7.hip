@@ -66,8 +66,21 @@ constexpr bool kMaskedAcc = true;   // P4: only lanes that own a stored Forward 
 #ifndef WH_UNI
 #define WH_UNI WH_K7_NEW_DEFAULT
 #endif
+// WH_ROW_PAIRS (bits; the default object: 3; 0 = the loops as they were, what the A/B slot keeps).  1: the envelope window sweep
+// walks two rows per loop trip with two sets of registers for the prefetched Forward cells (sweep_backward_null2_win).  2: the
+// wave-uniform arguments of the Forward sweeps, the window sweeps and the region scans are moved to scalar registers where the
+// function begins (uniform_i below).
+// WH_SPLIT_SLACK: the multidomain test of the certified region scan bounds each split point by the rows ITS two sums run over
+// (region_scan_cert).  It changes which windows are certified, never a region, so every object has it.
+#ifndef WH_ROW_PAIRS
+#define WH_ROW_PAIRS (WH_K7_NEW_DEFAULT ? 3 : 0)
+#endif
+#ifndef WH_SPLIT_SLACK
+#define WH_SPLIT_SLACK 1
+#endif
 constexpr int kLayout = WH_SPEC_ROWS ? SPEC_ROWS : SPEC_SOA;
 constexpr bool kUni = WH_UNI != 0;
+constexpr bool kRowPairs = ((WH_ROW_PAIRS) & 1) != 0, kUniArgs = ((WH_ROW_PAIRS) & 2) != 0, kSplitSlack = WH_SPLIT_SLACK != 0;
 static_assert(kLayout == SPEC_SOA || kSlim, "a row record has six words (WH_SLIM_SPEC)");
 template <bool SG> using SpecOf = SpecAt<SG ? (int)SPEC_SOA : kLayout>;
 constexpr int kSpecTag = kSpArr | (kLayout << 8);      // what ScoreArgs::spec_arrays must say for this object
@@ -121,6 +134,14 @@ __device__ __forceinline__ int64_t uniform_i64(int64_t v) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
   return (int64_t)(((unsigned long long)hi << 32) | lo);
 }
+// The arguments of a non-inlined sweep arrive in vector registers, the wave-uniform ones too (row count, window origin, band,
+// scale exponent, the SP and alpha words of the context): a row counter in a VGPR makes every uniform test of the row loop a
+// v_cmp + s_and_saveexec + s_cbranch_execz.  Moved to scalar registers where the sweep begins (WH_ROW_PAIRS & 2), the counter
+// and the tests are scalar code.  The two full-width Backward sweeps are left as they were: sweep_backward_null2 with scalar
+// arguments changes its register assignment such that score_kernel7<12, 768, false> keeps 240 B per lane in scratch (cap 176)
+// and <8, 768, true> 192 B (cap 176), and sweep_backward_decode<16> gained 7 instructions per row (452 -> 459).
+__device__ __forceinline__ int uniform_i(int x) { return kUniArgs ? __builtin_amdgcn_readfirstlane(x) : x; }
+__device__ __forceinline__ WaveCtx uniform_ctx(WaveCtx c) { c.SP = uniform_i(c.SP); c.alpha = uniform_i(c.alpha); return c; }
 // A sweep that knows its length model to be unihit (WH_UNI) still READS all four words of it, once: with two words read
 // the compiler hands them over as scalars instead of the 16-byte struct, the call no longer refers to the caller's frame and becomes
 // a tail-call candidate, and a function with such a call site saves every callee-saved register it touches (the
@@ -138,7 +159,9 @@ __device__ __forceinline__ FwdOut uniform_fwd(FwdOut o) { return FwdOut{uniform_
 constexpr int kUmSlot = 30;
 // (STORE: an envelope's sweep - every caller passes the unihit length model, which WH_UNI builds into the sweep)
 template <int Q, bool STORE, int TH, bool SG>
-__device__ __noinline__ FwdOut sweep_forward(const WaveCtx c, lds_u8 *seq3, int L, LenCfg cfg, float keep_scale, int keep_lanes = 63 << 8) {
+__device__ __noinline__ FwdOut sweep_forward(const WaveCtx c_, lds_u8 *seq3, int L, LenCfg cfg, float keep_scale, int keep_lanes = 63 << 8) {
+  const WaveCtx c = uniform_ctx(c_);
+  L = uniform_i(L); keep_lanes = uniform_i(keep_lanes);
   const uint8_t *seq = (const uint8_t *)seq3;
   TransTab<Q, false> T;
   T.load(nullptr, (const float *)c.fwL, c.lane);
@@ -396,10 +419,12 @@ __device__ __noinline__ P4Out sweep_backward_null2(const WaveCtx c, lds_u8 *eseq
 // BWG (staged launches, wh_staged.hip): the reversed transition arrays are gathered from the table buffer in L2
 // (c.specg points at them there) instead of an LDS copy - the window sweep reads them once per envelope.
 template <int QB, int Q, int TH, bool SG, bool BWG = false>
-__device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c, lds_u8 *eseq3, int Ld, LenCfg cu, float invZe, float mass_tol, int m0) {
+__device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 *eseq3, int Ld, LenCfg cu, float invZe, float mass_tol, int m0) {
   static_assert(Q % QB == 0 && QB % 4 == 0, "a window lane must stay inside one forward lane block");
   static_assert(!(SG && BWG), "c.specg cannot be both");
   constexpr int Q4 = Q / 4, B4 = QB / 4;
+  const WaveCtx c = uniform_ctx(c_);
+  Ld = uniform_i(Ld); m0 = uniform_i(m0);
   const uint8_t *eseq = (const uint8_t *)eseq3;
   const int lane = c.lane, SP = c.SP, Klds = ctxKlds(c);
   const SpecOf<SG> at{SP};
@@ -438,15 +463,21 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c, lds_u8 *
   int S_next = 0;
   // the stored Forward cells of a row are requested ONE ROW AHEAD (2 * QB registers: affordable here, not at full
   // width), so their HBM round trip runs beside a whole row of arithmetic
-  float4 fm_n[B4], fi_n[B4];
-  bool have_n = false;
+  // TWO sets of them (kPairs): a row consumes one set and requests the next row into the other, and the loop walks two rows
+  // per trip with the sets swapped in between - with one set a row began by copying last row's request out of the way
+  // (2 * QB v_mov behind a wait for the loads, on each of three paths).  The prefetch distance is one row either way.
+  // Not for long queries (their kernels' frames are at their caps) and not for the 512-node window at 768 threads: a second set
+  // of 16 registers does not fit beside its 64 table registers in 168 VGPRs (the sweep's frame 28 -> 76 B, with reloads in the row).
+  constexpr bool kPairs = kRowPairs && !SG && (QB == 4 || TH < 768);
+  float4 fm_a[B4], fi_a[B4], fm_b[B4], fi_b[B4];
+  bool have_a = false, have_b = false;
   // long-query mode: 64 rows of the per-row arrays per coalesced load; the masks are read a row ahead, so their
   // chunk is reloaded one row early (arrays 0 / 1 hold rows top - 1 - t)
   RowsDown<7> R;
   const int r_off[7] = {kSpML * SP, kSpMH * SP, SP_S * SP, SP_S * SP, SP_N * SP, SP_J * SP, SP_C * SP};
   const int r_sh[7] = {-1, -1, 0, -1, -1, -1, -1};
   if (SG) R.load(spec, r_off, r_sh, Ld, lane);
-  auto request_row = [&](int r, bool first) {
+  auto request_row = [&](int r, bool first, float4 (&fm_n)[B4], float4 (&fi_n)[B4], bool &have_n) {
     const unsigned mword = SG ? (first ? (lanef < 32 ? ldu(kSpML * SP + r) : ldu(kSpMH * SP + r)) : (lanef < 32 ? R.u(0, r + 1) : R.u(1, r + 1)))
                               : (lanef < 32 ? ldu(at(kSpML, r)) : ldu(at(kSpMH, r)));
     have_n = (mword >> (lanef & 31)) & 1u;
@@ -456,19 +487,13 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c, lds_u8 *
       for (int p4 = 0; p4 < B4; p4++) { fm_n[p4] = nt_load4(row + frow[p4]); fi_n[p4] = nt_load4(row + (SG ? Q4 * kWave : Q4) + frow[p4]); }
     }
   };
-  request_row(Ld, true);
+  request_row(Ld, true, fm_a, fi_a, have_a);
   // CARRY: the words of record i - 1 are loaded together where row i begins - beside its mask word, which the row request
   // reads there anyway - and its scale exponent is row i - 1's own one iteration later: one LDS round trip per row, not six
   int S_row = CARRY ? ldi(at(SP_S, Ld)) : 0;
-#pragma unroll 1
-  for (int i = Ld; i >= 1; i--) {
-    asm volatile("" ::: "memory");
-    if (SG && R.spent(i)) R.load(spec, r_off, r_sh, i, lane);
-    float4 fm_c[B4], fi_c[B4];
-#pragma unroll
-    for (int p4 = 0; p4 < B4; p4++) { fm_c[p4] = fm_n[p4]; fi_c[p4] = fi_n[p4]; }
-    const bool have = have_n;
-    if (i > 1) request_row(i - 1, false);
+  // row i: its stored Forward cells are in <fm_c, fi_c, have>; row i - 1 is requested into <fm_n, fi_n, have_n>
+  auto row = [&](int i, const float4 (&fm_c)[B4], const float4 (&fi_c)[B4], bool have, float4 (&fm_n)[B4], float4 (&fi_n)[B4], bool &have_n) {
+    if (i > 1) request_row(i - 1, false, fm_n, fi_n, have_n);
     int S_p = 0;
     float N_p = 0.f, J_p = 0.f, C_p = 0.f;
     if (CARRY) {
@@ -526,6 +551,27 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c, lds_u8 *
     S_next = S_i;
     if (CARRY) S_row = S_p;
     xfac = fmaf(nj * cu.loop, s_p, xfac);
+  };
+  if (kPairs) {
+    int i = Ld;
+#pragma unroll 1
+    for (; i >= 2; i -= 2) {
+      asm volatile("" ::: "memory");
+      row(i, fm_a, fi_a, have_a, fm_b, fi_b, have_b);
+      asm volatile("" ::: "memory");
+      row(i - 1, fm_b, fi_b, have_b, fm_a, fi_a, have_a);
+    }
+    if (i == 1) row(1, fm_a, fi_a, have_a, fm_b, fi_b, have_b);      // (an odd row count: the trip without its second row)
+  } else {
+#pragma unroll 1
+    for (int i = Ld; i >= 1; i--) {
+      asm volatile("" ::: "memory");
+      if (SG && R.spent(i)) R.load(spec, r_off, r_sh, i, lane);
+      float4 fm_c[B4], fi_c[B4];
+#pragma unroll
+      for (int p4 = 0; p4 < B4; p4++) { fm_c[p4] = fm_a[p4]; fi_c[p4] = fi_a[p4]; }
+      row(i, fm_c, fi_c, have_a, fm_a, fi_a, have_a);
+    }
   }
   float sm = 0.f;
 #pragma unroll
@@ -812,9 +858,11 @@ struct WinDec { float eps; };
 // TMPG (four envelopes per wave, score_kernel7q): the three posterior rows go to the wave's HBM region (c.specg), not to
 // LDS - the wave's LDS block then has room for four queries' residues and records.
 template <int QB, int Q, int TH, bool INPL = false, bool BWG = false, bool TMPG = false>
-__device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c, lds_u8 *seq3, int L, LenCfg cm, float invZ, int ef_L, int m0) {
+__device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c_, lds_u8 *seq3, int L, LenCfg cm, float invZ, int ef_L, int m0) {
   static_assert(Q % QB == 0 && QB % 4 == 0, "a window lane must stay inside one forward lane block");
   static_assert(!(BWG && TMPG) && !(INPL && TMPG), "c.specg serves one purpose per call");
+  const WaveCtx c = uniform_ctx(c_);
+  L = uniform_i(L); ef_L = uniform_i(ef_L); m0 = uniform_i(m0);
   constexpr int Q4 = Q / 4, B4 = QB / 4;
   const uint8_t *seq = (const uint8_t *)seq3;
   const int lane = c.lane, SP = c.SP, Klds = ctxKlds(c);
@@ -929,6 +977,7 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c, lds_u8
 // The cumulative sums go back into the pe row (etot) and the njc row (btot): both are read at the row they are written.
 template <int TH, bool INPL = false, bool TMPG = false>
 __device__ __noinline__ RegOut region_scan_cert(lds_f *spec3, int SP, int L, lds_i *regs3, int lane, float eps, glb_f *tmpg = nullptr) {
+  SP = uniform_i(SP); L = uniform_i(L);
   float *tmp = TMPG ? (float *)tmpg : (float *)spec3 + kSpArr * SP;
   // word <row> of the three posterior rows: INPL the E, B and N words of the wave's block (stride-6 column reads where the block
   // holds records), else three arrays of their own
@@ -994,21 +1043,23 @@ __device__ __noinline__ RegOut region_scan_cert(lds_f *spec3, int SP, int L, lds
   }
   __builtin_amdgcn_wave_barrier();
   if (TMPG) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");       // the cumulative sums were stored by other lanes of this wave
-  // multidomain test: max_z min(etot[z]-etot[i-1], btot[j]-btot[z-1]) >= rt3; each sum of windowed posteriors over the
-  // region's rows falls short of the true one by at most (rows) x eps
+  // multidomain test: max_z min(etot[z]-etot[i-1], btot[j]-btot[z-1]) >= rt3; each sum of windowed posteriors falls short of
+  // the true one by at most (rows it sums) x eps
   int multi_mask = 0;
   for (int e = 0; e < nenv; e++) {
     const int ri = regs[2 * e], rj = regs[2 * e + 1];
-    float mx = -1.0f;
+    float mx = -1.0f, ux = -1.0f;
     const float e0 = ldt(tE + (ri - 1)), bj = ldt(tN + rj);
     for (int z = ri + lane; z <= rj; z += kWave) {
       const float u = ldt(tE + z) - e0, v = bj - ldt(tN + (z - 1));
       mx = fmaxf(mx, fminf(u, v));
+      // WH_SPLIT_SLACK: the slack of THIS split point - u sums z - ri + 1 rows, v sums rj - z + 1, and the minimum of two upper
+      // bounds bounds the minimum (the region's row count bounds both sums at once: it is right only for a split at either end)
+      if (kSplitSlack) ux = fmaxf(ux, fminf(u + (float)(z - ri + 1) * eps, v + (float)(rj - z + 1) * eps));
     }
     mx = wave_max(mx);
-    const float up = mx + (float)(rj - ri + 1) * eps + slack;
     if (mx >= rt3) { flags |= WH_FLAG_MULTI; multi_mask |= 1 << e; if (mx < rt3 + slack) doubt_md = 1; }
-    else if (up >= rt3) doubt_md = 1;
+    else if ((kSplitSlack ? wave_max(ux) : mx + (float)(rj - ri + 1) * eps) + slack >= rt3) doubt_md = 1;
   }
   RegOut o;
   o.nenv = nenv; o.nreg = nreg; o.flags = flags | (multi_mask << 8) | (doubt << 24) | (doubt_md << 25);
@@ -1018,6 +1069,7 @@ __device__ __noinline__ RegOut region_scan_cert(lds_f *spec3, int SP, int L, lds
 // ---------------------------------------------------------------- region scan (A.4)
 template <int TH, bool SG>
 __device__ __noinline__ RegOut region_scan(lds_f *spec3, glb_f *specg, int SP, int L, lds_i *regs3, int lane) {
+  SP = uniform_i(SP); L = uniform_i(L);
   float *spec = SG ? (float *)specg : (float *)spec3;
   auto ldf = [&](int idx) -> float { return SG ? __builtin_nontemporal_load(spec + idx) : spec[idx]; };
   int *regs = (int *)regs3;
