@@ -423,7 +423,8 @@ int wh_consensus_dev(wh_ehmm *e, const int64_t *d_offsets, int64_t nq, int32_t m
 /* Duration (ms) and launch count of the kernels of the last *_dev/plain call, measured
  * with HIP events on the stream the kernels ran on: which = 0 scoring kernels, 1 topk, 2 align, 3 consensus,
  * 4 multidomain resolver (the second part of wh_score: stage time of scoring = 0 + 4), 5 the domain stage (wh_domains: its
- * gather and summary kernels and the alignment launches between them; which = 2 then holds the alignment launches alone). */
+ * gather and summary kernels and the alignment launches between them; which = 2 then holds the alignment launches alone),
+ * 6 the alignment assembly (wh_msa_dev: widths, layout, render and PP_cons kernels, and the host's one wait between them). */
 int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches);
 /* Timing mode only: the scoring launches of the last wh_score[_dev] call, in launch order - the cells-per-lane class of the
  * launch's models (16 = models of 961..1024 nodes ...), the kernel family (0 phase-call wh::k7::score_kernel7, 1
@@ -461,6 +462,37 @@ int wh_merge(int device, const uint8_t *q_text, const int64_t *q_off, int64_t nq
 int wh_merge_sharded(int device, const uint8_t *q_text, const int64_t *q_off, int64_t nq, const int32_t *codes, const int32_t *q_row,
                      const uint8_t *backbone, int32_t nb, int32_t B, int32_t *widths_local, const int32_t *widths_global,
                      uint8_t **out_full, uint8_t **out_masked, int64_t *out_rows, int64_t *out_width);
+
+/* ---- hmmalign for a FILE of sequences: one alignment of all of them to one model ------------------------------------
+ * What `hmmalign [--trim] HMM SEQFILE` computes (HMMER 3.1b2: p7_tracealign_Seqs; the reference's bundled MAGUS, SEPP and
+ * UPP call it with whole fragment files), assembled on the device from wh_align_pp_dev's per-residue columns and posteriors
+ * for the pairs (q, h), q = 0..nq-1 (CSR by the sequences' offsets), and the sequences' characters as given (text, as
+ * wh_merge's q_text: match residues come out upper case, inserts lower case).  Layout: every node 1..M is a column; between
+ * the columns of nodes k and k + 1 lies insert block k, as wide as the longest insert run any sequence has there (block 0:
+ * the N flank, right-justified; block M: the C flank, left-justified; an internal run of n residues puts its first n / 2
+ * flush left and the rest flush right); a deleted node is '-', an unused insert cell '.'.  Returned, each malloc'ed (release
+ * with wh_free_text; on failure nothing is left allocated):
+ *   W                 the alignment's width
+ *   rows[nq x W]      the sequences' rows           pp_rows[nq x W]  their "#=GR PP" rows ('.' where the row has no residue)
+ *   pp_cons[W]        "#=GC PP_cons": on a match column the character of the MEAN posterior over the sequences with a residue
+ *                     there (float32 sum in sequence order - no floating-point atomics - divided by the count), '.' elsewhere
+ *   rf[W]             "#=GC RF" of a model without a reference line of its own: 'x' on match columns, '.' on insert columns
+ *   matmap[M]         0-based alignment column of node k + 1
+ *   pathless          sequences that came back from the alignment without a match state: they render as gaps only
+ * flags: WH_MSA_TRIM = hmmalign --trim: the residues of both flanks are dropped (blocks 0 and M stay empty).
+ * nq == 0: WH_OK, W = M.  h out of range or a NULL handle: WH_EINVAL, wh_last_error names the entry point.
+ * wh_msa_dev is the assembly alone, on device arrays (total_residues = d_offsets[nq]; it waits for the stream once, to read
+ * W, and once at the end); wh_msa takes host pointers and runs wh_align_pp_dev first.  wh_last_kernel_ms(6): the assembly's
+ * kernels; (2): the alignment launches of wh_msa. */
+#define WH_MSA_TRIM   1
+#define WH_MSA_NO_LDS 2   /* test hook: the rows are rendered in global memory whatever the width */
+int wh_msa(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, const uint8_t *text, int64_t nq, int32_t h,
+           int32_t flags, int64_t *out_W, uint8_t **out_rows, uint8_t **out_pp_rows, uint8_t **out_pp_cons, uint8_t **out_rf,
+           int32_t **out_matmap, int64_t *out_pathless);
+int wh_msa_dev(wh_ehmm *e, const int32_t *d_cols, const float *d_pp, const uint8_t *d_text, const int64_t *d_offsets,
+               int64_t nq, int64_t total_residues, int32_t h, int32_t flags, int64_t *out_W, uint8_t **out_rows,
+               uint8_t **out_pp_rows, uint8_t **out_pp_cons, uint8_t **out_rf, int32_t **out_matmap, int64_t *out_pathless,
+               void *stream);
 
 /* ---- eHMM construction (host code, no GPU needed) -------------------------------
  * Replaces the reference's per-subset call

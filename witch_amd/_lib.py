@@ -21,6 +21,7 @@ VIT_NOT_RUN, VIT_OVERFLOW, MSV_OVERFLOW = -32769, 32768, -1
 ALPH_DNA, ALPH_RNA, ALPH_AMINO = 0, 1, 2
 WH_OK, WH_EINVAL, WH_EIO, WH_ENODEV, WH_EHIP, WH_ERANGE, WH_ENOMEM = 0, -1, -2, -3, -4, -5, -6      # include/witch_hip.h
 WH_BUILD_STATS, WH_BUILD_CALIB_NO_LDS = 1, 4
+WH_MSA_TRIM, WH_MSA_NO_LDS = 1, 2
 PATH_P2_WIN, PATH_P2_FULL, PATH_P4_W256, PATH_P4_W512, PATH_P4_WFAIL, PATH_P4_FULL, PATH_DENSE, PATH_MULTI = 1, 2, 4, 8, 16, 32, 64, 128
 
 
@@ -77,6 +78,9 @@ SYMBOLS = {
                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_merge": (C.c_int, [C.c_int, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_msa": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)] + [C.POINTER(C.c_void_p)] * 5 + [C.POINTER(C.c_int64)]),
+    "wh_msa_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)] + [C.POINTER(C.c_void_p)] * 5 +
+                   [C.POINTER(C.c_int64), _P]),
     "wh_ehmm_free": (None, [_P]),
     "wh_ehmm_count": (C.c_int, [_P]),
     "wh_ehmm_alphabet": (C.c_int, [_P]),

@@ -1,6 +1,6 @@
 // Internal header of the host side of libwitch_hip.so: what wh_api.hip (handles, options, getters, host-pointer entry
 // points), wh_host_score.hip (wh_score_dev), wh_host_resolve.hip (its resolver stage), wh_host_align.hip (wh_align_dev),
-// wh_host_domains.hip (wh_domains_dev) and wh_host_filter.hip (the filters) share: the handle, the d_counter slots, the
+// wh_host_domains.hip (wh_domains_dev), wh_host_msa.hip (wh_msa_dev) and wh_host_filter.hip (the filters) share: the handle, the d_counter slots, the
 // staging of the host-pointer entry points.  No kernel file includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -102,6 +102,9 @@ struct wh_ehmm {
   std::vector<int64_t> h_env_off;           // ... host sources of asynchronous uploads: they outlive the call
   std::vector<float> h_evp;
   DevBuf d_evp, d_dom_pair, d_dom_len, d_env_res, d_env_off, d_dom_q, d_dom_h, d_dom_cols, d_dom_pp;
+  // wh_msa_dev: widths / layout / matmap / PP_cons sums, per-residue cells, RF and PP_cons, the rows, the posterior chunk;
+  // wh_msa: the alignment's columns, posteriors and pair lists
+  DevBuf d_msa_lay, d_msa_res, d_msa_gc, d_msa_rows, d_msa_pprows, d_msa_ppm, d_msa_cols, d_msa_pp;
   int64_t rq_cap = 0;                       // records the queue of the current scoring call holds
   double rq_rate = 0.0;                     // largest share of queued pairs any call on this handle has seen (sizes the next queue)
   int64_t rq_floor = 0;                     // ... at least this many (set when a call overflowed its estimate; the call then runs again)
@@ -128,7 +131,7 @@ struct wh_ehmm {
   struct FilterStateDelete { void operator()(FilterState *f) const; };
   std::unique_ptr<FilterState, FilterStateDelete> filter;
   bool timing = false;
-  KernelTimer timers[6];                    // wh_last_kernel_ms: 0 scoring, 1 topk, 2 align, 3 consensus, 4 resolver, 5 domain stage
+  KernelTimer timers[7];                    // wh_last_kernel_ms: 0 scoring, 1 topk, 2 align, 3 consensus, 4 resolver, 5 domain stage, 6 alignment assembly (wh_msa_dev)
   int max_M = 0;
   int max_Q = 4;                              // largest cells-per-lane of any model (sizes the float64 slabs)
   int last_align_redo = 0;          // pairs of the last wh_align call that went through the log-space pass

@@ -380,6 +380,38 @@ hipError_t launch_merge_runs(const MergeArgs &a, hipStream_t s);
 hipError_t launch_merge_layout(const MergeArgs &a, hipStream_t s);
 hipError_t launch_merge_render(const MergeArgs &a, int64_t nrows, hipStream_t s);
 
+// wh_msa_dev (wh_msa.hip): hmmalign's alignment of nq sequences to ONE model, assembled from the alignment's per-residue
+// columns and posteriors (CSR by the sequences' offsets).  Block k (0..M) is the insert block behind node k (0: the N flank,
+// M: the C flank); layout[0..M] its first alignment column, layout[M + 1] the alignment's width W.
+struct MsaArgs {
+  const int32_t *cols;         // per residue: 0-based node, or -1
+  const float *pp;             // per residue: posterior of its state on the path
+  const uint8_t *text;         // the sequences' characters as given
+  const int64_t *off;          // [nq + 1]
+  int64_t nq, total;           // total: residues the per-residue arrays hold (no kernel goes beyond it)
+  int32_t M;
+  int32_t trim;                // --trim: flank residues are dropped, blocks 0 and M stay empty
+  int32_t *width;              // [M + 1] widest insert run per block (zeroed before the widths kernel)
+  int32_t *res_blk, *res_k;    // per insert residue: its block (-1: not rendered) and its cell in it: k >= 0 from the
+                               //   block's left end, k < 0 from its right end (width + k)
+  int *pathless;               // [1] sequences without a match state
+  long long *layout;           // [M + 2]
+  int32_t *matmap;             // [M] alignment column of node k + 1
+  uint8_t *rf, *pp_cons;       // [W] (allocated for the largest possible W)
+  uint8_t *rows, *pp_rows;     // [nq][W]
+  float *ppm;                  // [chunk rows][M] posterior of the residue at a node, -1: none (a chunk of sequences)
+  int64_t q0, q1;              // ... the chunk
+  float *cons_sum;             // [M] running float32 sums, in sequence order ...
+  int32_t *cons_cnt;           // [M] ... and counts over the chunks so far
+  int32_t last;                // the chunk ends the file: PP_cons is written
+};
+hipError_t launch_msa_widths(const MsaArgs &a, hipStream_t s);
+hipError_t launch_msa_layout(const MsaArgs &a, hipStream_t s);
+hipError_t launch_msa_render(const MsaArgs &a, long long W, bool lds, hipStream_t s);
+hipError_t launch_msa_cons(const MsaArgs &a, hipStream_t s);
+size_t msa_render_lds_bytes(long long W);
+constexpr size_t kMsaLdsBudget = 64 * 1024;   // the two rows of a sequence in LDS: up to 32 K columns, two workgroups per CU stay resident
+
 struct TopkArgs {
   const int32_t *decibits;
   const uint8_t *flags;

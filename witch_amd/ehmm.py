@@ -295,6 +295,45 @@ class EHMM:
                                     cols.ctypes.data, pp.ctypes.data), "wh_align_pp")
         return cols, co, pp
 
+    @staticmethod
+    def _msa_outputs():
+        W, npl = C.c_int64(0), C.c_int64(0)
+        ptrs = [C.c_void_p(None) for _ in range(5)]
+        return W, npl, ptrs
+
+    def _msa_collect(self, nq, h, W, npl, ptrs):
+        """The malloc'ed buffers of wh_msa / wh_msa_dev as numpy arrays (copied; the buffers are released)."""
+        W, M = int(W.value), int(self.M[h])
+        sizes = [(nq * W, np.uint8), (nq * W, np.uint8), (W, np.uint8), (W, np.uint8), (M, np.int32)]
+        out = []
+        for ptr, (n, dt) in zip(ptrs, sizes):
+            nbytes = n * np.dtype(dt).itemsize
+            out.append(np.frombuffer((C.c_char * nbytes).from_address(ptr.value), dtype=dt).copy() if nbytes else np.zeros(0, dtype=dt))
+            lib().wh_free_text(ptr)
+        rows, pp_rows, pp_cons, rf, matmap = out
+        return {"W": W, "rows": rows.reshape(nq, W), "pp_rows": pp_rows.reshape(nq, W), "pp_cons": pp_cons, "rf": rf,
+                "matmap": matmap, "pathless": int(npl.value)}
+
+    def msa(self, residues, offsets, text, h=0, trim=False, no_lds=False):
+        """hmmalign's alignment of ALL the sequences to model h (include/witch_hip.h: wh_msa): the sequences are aligned
+        (wh_align_pp_dev) and the alignment is assembled on the device.  text: the sequences' characters as given, one
+        byte per residue (bytes, str or uint8 array).  Returns {"W", "rows" uint8 [nq, W], "pp_rows" uint8 [nq, W],
+        "pp_cons" uint8 [W], "rf" uint8 [W], "matmap" int32 [M], "pathless"}; trim: hmmalign --trim; no_lds: test hook
+        (WH_MSA_NO_LDS)."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if isinstance(text, str):
+            text = text.encode()
+        text = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        nq = len(offsets) - 1
+        if len(text) != len(residues) or (nq and int(offsets[-1]) != len(residues)):
+            raise ValueError("msa: residues, text and offsets disagree")
+        W, npl, ptrs = self._msa_outputs()
+        flags = (_lib.WH_MSA_TRIM if trim else 0) | (_lib.WH_MSA_NO_LDS if no_lds else 0)
+        check(lib().wh_msa(self._h, residues.ctypes.data, offsets.ctypes.data, text.ctypes.data, nq, int(h), flags, C.byref(W),
+                           *[C.byref(p) for p in ptrs], C.byref(npl)), "wh_msa")
+        return self._msa_collect(nq, int(h), W, npl, ptrs)
+
     def evparams(self):
         """(tau float32 [H], lambda float32 [H], present bool [H]): the models' "STATS LOCAL FORWARD" parameters, NaN where a
         model file has no such line (include/witch_hip.h: wh_ehmm_evparams)."""
@@ -432,6 +471,18 @@ class EHMM:
                                         npairs, col_offsets_t.data_ptr(), cols.data_ptr(), pp.data_ptr(),
                                         self._stream()), "wh_align_pp_dev")
         return (cols, pp) if want_pp else cols
+
+    def msa_t(self, cols_t, pp_t, text_t, offsets_t, h=0, trim=False, no_lds=False):
+        """The assembly alone (wh_msa_dev) on torch tensors resident on the device: cols int32 and pp float32 as
+        align_t(want_pp=True) returns them for the pairs (q, h), text uint8, offsets int64 [nq + 1].  Returns what msa
+        returns (numpy arrays: the library hands the alignment back in host memory)."""
+        nq = offsets_t.numel() - 1
+        W, npl, ptrs = self._msa_outputs()
+        flags = (_lib.WH_MSA_TRIM if trim else 0) | (_lib.WH_MSA_NO_LDS if no_lds else 0)
+        check(lib().wh_msa_dev(self._h, cols_t.data_ptr(), pp_t.data_ptr(), text_t.data_ptr(), offsets_t.data_ptr(), nq,
+                               int(cols_t.numel()), int(h), flags, C.byref(W), *[C.byref(p) for p in ptrs], C.byref(npl),
+                               self._stream()), "wh_msa_dev")
+        return self._msa_collect(nq, int(h), W, npl, ptrs)
 
     def domains_dev(self, residues_t, offsets_t, max_len: int, flags_t, detail_t):
         """domains() on torch tensors resident on the device (wh_domain_counts_dev, wh_domains_dev on torch's current

@@ -8,5 +8,6 @@ through os.system from forked pool workers - one process per (HMM, chunk) and pe
 fork), so the executables are thin C clients (client.c) of ONE resident server process
 (server.py) that owns the GPU: they pass argv over a UNIX socket and exit with its status; the
 server writes the output files - text that evalHMMSearchOutput (algorithm.py:579-605) and
-ExtendedAlignment._read_sto (helpers/alignment_tools.py:926-955) accept.
+ExtendedAlignment._read_sto (helpers/alignment_tools.py:926-955) accept.  A sequence file with several
+records (MAGUS' hmmAlignQueries, SEPP, UPP) gets hmmalign's one alignment of all of them (wh_msa).
 """

@@ -1,5 +1,5 @@
-"""Text formats of the level-0 shim: FASTA in, hmmsearch per-sequence table and single-sequence
-Stockholm out.  Pure Python, no GPU."""
+"""Text formats of the level-0 shim: FASTA in, hmmsearch per-sequence table, single-sequence
+Stockholm and hmmalign's multi-sequence alignment (Stockholm, Pfam, afa) out.  Pure Python, no GPU."""
 import math
 
 
@@ -347,6 +347,61 @@ def format_stockholm(name, row, width=200, pp=None, rf=True):
         if rfl is not None:
             out.append("%-*s %s" % (tagw, "#=GC RF", rfl[a:a + width]))
         if a != blocks[-1]:
+            out.append("")
+    out.append("//")
+    return "\n".join(out) + "\n"
+
+
+class FormatError(ValueError):
+    """An output format format_msa does not write (the server reports it as hmmalign does)."""
+
+
+MSA_FORMATS = ("stockholm", "pfam", "afa")
+
+
+def _text(x):
+    """A row as str: str, bytes or a uint8 array."""
+    if isinstance(x, str):
+        return x
+    return (x if isinstance(x, (bytes, bytearray)) else bytes(bytearray(x))).decode("ascii")
+
+
+def format_msa(names, rows, pp_rows, pp_cons, rf, outformat="Stockholm", width=200):
+    """hmmalign's output for an alignment of several sequences (EHMM.msa: rows, pp_rows [nq][W], pp_cons, rf [W]; str,
+    bytes or uint8 arrays; rf None: no "#=GC RF" line, as for a model with a reference line of its own), byte for byte
+    HMMER 3.1b2's: "Stockholm" in blocks of <width> columns, every block with its "#=GR PP" and "#=GC" lines; "Pfam" in
+    one block; "afa" the rows alone, 60 characters per line.  The format's name is matched without case, as Easel does;
+    any other format raises FormatError."""
+    fmt = str(outformat).lower()
+    if fmt not in MSA_FORMATS:
+        raise FormatError("%s is not a recognized output MSA file format" % outformat)
+    names = list(names)
+    rows = [_text(r) for r in rows]
+    if fmt == "afa":
+        out = []
+        for n, r in zip(names, rows):
+            out.append(">" + n)
+            out.extend(r[a:a + 60] for a in range(0, len(r), 60))
+        return "\n".join(out) + "\n" if out else ""
+    pps = [_text(r) for r in pp_rows]
+    cons = _text(pp_cons)
+    rfl = None if rf is None else _text(rf)
+    W = len(cons)
+    namew = max([len(n) for n in names] + [1])
+    margin = max(namew + 1, len("#=GC PP_cons "), namew + len("#=GR  PP "))      # Easel: the widest of the line tags, plus a space
+    if rfl is not None:
+        margin = max(margin, len("#=GC RF "))
+    step = W if fmt == "pfam" or W == 0 else width
+    out = ["# STOCKHOLM 1.0", ""]
+    starts = list(range(0, max(W, 1), max(step, 1)))
+    for a in starts:
+        for n, r, p in zip(names, rows, pps):
+            out.append("%-*s%s" % (margin, n, r[a:a + step]))
+            out.append("%-*s%s" % (margin, "#=GR %-*s PP" % (namew, n), p[a:a + step]))
+        out.append("%-*s%s" % (margin, "#=GC PP_cons", cons[a:a + step]))
+        if rfl is not None:
+            out.append("%-*s%s" % (margin, "#=GC RF", rfl[a:a + step]))
+        if a != starts[-1]:
             out.append("")
     out.append("//")
     return "\n".join(out) + "\n"

@@ -236,6 +236,15 @@ class GpuBackend:
                     out[j] = (int(e.M[0]), cols[co[n]:co[n + 1]].copy(), pp[co[n]:co[n + 1]].copy())
         return out
 
+    def align_msa(self, hmm_path, records, trim=False):
+        """records: [(name, text)] -> EHMM.msa's dict: hmmalign's ONE alignment of all the sequences to the model, aligned
+        and assembled on the device (wh_msa).  The rows carry the records' own characters, match residues upper case and
+        inserts lower case."""
+        with self.lock:
+            e, hdr = self.model(hmm_path)
+            res, offs = e.digitize_many([t.upper() for _, t in records])
+            return e.msa(res, offs, "".join(t for _, t in records), h=0, trim=trim)
+
 
 class AlignBatcher:
     """Collects hmmalign jobs that arrive within a short window and runs them together."""
@@ -326,9 +335,11 @@ class Server:
         if not os.path.exists(fa):
             raise ArgError("Error: Failed to open sequence file %s for reading" % fa)
         records = formats.read_fasta(fa)
+        if len(records) != 1 and hasattr(self.backend, "align_msa"):
+            return self.run_hmmalign_msa(opts, hmm, fa, records, cwd)
         if len(records) != 1:
             # WITCH aligns one query per call (aligner.py:90-100); a multi-sequence alignment
-            # needs the shared insert columns hmmalign computes, which this shim does not emit
+            # needs the shared insert columns hmmalign computes, which this backend does not emit
             raise ArgError("witch-hip hmmalign shim: exactly one sequence per call (got %d)" % len(records))
         name, text = records[0]
         res = self.batcher.submit((hmm, name, text))
@@ -345,6 +356,23 @@ class Server:
                 f.write(sto)
             return ""
         return sto
+
+    def run_hmmalign_msa(self, opts, hmm, fa, records, cwd):
+        """A file of several sequences: hmmalign's one alignment of all of them (the reference's bundled MAGUS, SEPP and UPP
+        call it so), honouring --trim, --outformat Stockholm | Pfam | afa and -o."""
+        if not records:
+            raise ArgError("Error: Sequence file %s is empty or misformatted" % fa)
+        outformat = opts.get("--outformat", "Stockholm")
+        if str(outformat).lower() not in formats.MSA_FORMATS:
+            raise ArgError("ERROR: %s is not a recognized output MSA file format (witch-hip hmmalign shim: Stockholm, Pfam, afa)" % outformat)
+        m = self.backend.align_msa(hmm, records, trim="--trim" in opts)
+        text = formats.format_msa([n for n, _ in records], m["rows"], m["pp_rows"], m["pp_cons"],
+                                  None if formats.hmm_has_rf(hmm) else m["rf"], outformat)
+        if "-o" in opts:
+            with open(os.path.join(cwd, opts["-o"]), "w") as f:
+                f.write(text)
+            return ""
+        return text
 
     # ---------------------------------------------------------------- plumbing
     def handle(self, conn):
