@@ -424,7 +424,8 @@ int wh_consensus_dev(wh_ehmm *e, const int64_t *d_offsets, int64_t nq, int32_t m
  * with HIP events on the stream the kernels ran on: which = 0 scoring kernels, 1 topk, 2 align, 3 consensus,
  * 4 multidomain resolver (the second part of wh_score: stage time of scoring = 0 + 4), 5 the domain stage (wh_domains: its
  * gather and summary kernels and the alignment launches between them; which = 2 then holds the alignment launches alone),
- * 6 the alignment assembly (wh_msa_dev: widths, layout, render and PP_cons kernels, and the host's one wait between them). */
+ * 6 the alignment assembly (wh_msa_dev: widths, layout, render and PP_cons kernels, and the host's one wait between them),
+ * 7 the --mapali mapping (wh_msa_mapali_dev: count and map kernels, and the host's one wait between them). */
 int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches);
 /* Timing mode only: the scoring launches of the last wh_score[_dev] call, in launch order - the cells-per-lane class of the
  * launch's models (16 = models of 961..1024 nodes ...), the kernel family (0 phase-call wh::k7::score_kernel7, 1
@@ -493,6 +494,37 @@ int wh_msa_dev(wh_ehmm *e, const int32_t *d_cols, const float *d_pp, const uint8
                int64_t nq, int64_t total_residues, int32_t h, int32_t flags, int64_t *out_W, uint8_t **out_rows,
                uint8_t **out_pp_rows, uint8_t **out_pp_cons, uint8_t **out_rf, int32_t **out_matmap, int64_t *out_pathless,
                void *stream);
+
+/* ---- hmmalign --mapali ALN HMM SEQS: the alignment model h was built from as rows of the output, in front of the new
+ * sequences (HMMER's way to add sequences to an existing alignment: what UPP and SEPP call the extended alignment of a
+ * subset).  map_rows: the n_map rows of that alignment, alen characters each, no terminator (a letter is a residue, any
+ * other character of the alphabet a gap).  A residue of such a row goes by its alignment COLUMN, through the model's MAP
+ * annotation (wh_ehmm_map): in the column of node k it is node k's, upper case; in a column between those of nodes k and
+ * k + 1 it is an insert of block k, lower case (before node 1's column: block 0, behind node M's: block M) - also where the
+ * row has no residue in node k's column, or none in any node's column before it.  Inside a block the alignment's own columns
+ * are not kept: the residues a row has there form one run, laid out like a new sequence's (above); block widths are the
+ * maximum over rows and new sequences together; WH_MSA_TRIM drops the rows' residues of blocks 0 and M too.
+ * Outputs as wh_msa's, with these differences: rows holds n_map + nq rows, the alignment's first; pp_rows holds nq rows (a
+ * row of the alignment has no posteriors, hmmalign writes no "#=GR PP" line for it); pp_cons is the mean over the new
+ * sequences alone; pathless counts new sequences only.  n_map == 0: wh_msa's result.  nq == 0 with n_map > 0: the rows alone.
+ * WH_EINVAL, wh_last_error naming the entry point: a model without "MAP yes" or without a CKSUM line, or whose MAP columns do
+ * not increase; alen short of the last MAP column; bad pointers; and, wh_msa_mapali only, a character outside the alphabet or
+ * an alignment whose checksum (wh_alignment_checksum) is not the model's CKSUM - hmmalign's "checksum mismatch".
+ * wh_msa_mapali_dev takes the rows and the new sequences' alignment on the device and does NOT verify the checksum (its caller
+ * has the rows on the host, or has none); it waits for the stream three times (the rows' residue counts, the uploads, W) and
+ * at the end.  wh_last_kernel_ms(7): the count and map kernels with the host's wait between them; (6): the assembly. */
+int wh_msa_mapali(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, const uint8_t *text, int64_t nq, int32_t h,
+                  int32_t flags, const uint8_t *map_rows, int64_t n_map, int64_t alen, int64_t *out_W, uint8_t **out_rows,
+                  uint8_t **out_pp_rows, uint8_t **out_pp_cons, uint8_t **out_rf, int32_t **out_matmap, int64_t *out_pathless);
+int wh_msa_mapali_dev(wh_ehmm *e, const int32_t *d_cols, const float *d_pp, const uint8_t *d_text, const int64_t *d_offsets,
+                      int64_t nq, int64_t total_residues, int32_t h, int32_t flags, const uint8_t *d_map_rows, int64_t n_map,
+                      int64_t alen, int64_t *out_W, uint8_t **out_rows, uint8_t **out_pp_rows, uint8_t **out_pp_cons,
+                      uint8_t **out_rf, int32_t **out_matmap, int64_t *out_pathless, void *stream);
+/* hmmbuild's CKSUM of an alignment (nseq rows of alen characters, flat): Jenkins' one-at-a-time hash over the digital
+ * residues; case and the gap character ('-' '.' '_') do not enter it.  Host code, no GPU needed.  molecule as wh_hmmbuild. */
+int wh_alignment_checksum(const char *molecule, const char *rows, int32_t nseq, int64_t alen, uint32_t *out_cksum);
+/* The CKSUM line of model h: *present = 0 where the file has none. */
+int wh_ehmm_cksum(const wh_ehmm *e, int h, uint32_t *cksum, int32_t *present);
 
 /* ---- eHMM construction (host code, no GPU needed) -------------------------------
  * Replaces the reference's per-subset call

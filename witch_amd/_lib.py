@@ -81,6 +81,12 @@ SYMBOLS = {
     "wh_msa": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)] + [C.POINTER(C.c_void_p)] * 5 + [C.POINTER(C.c_int64)]),
     "wh_msa_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)] + [C.POINTER(C.c_void_p)] * 5 +
                    [C.POINTER(C.c_int64), _P]),
+    "wh_msa_mapali": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, C.POINTER(C.c_int64)] +
+                      [C.POINTER(C.c_void_p)] * 5 + [C.POINTER(C.c_int64)]),
+    "wh_msa_mapali_dev": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64,
+                                    C.POINTER(C.c_int64)] + [C.POINTER(C.c_void_p)] * 5 + [C.POINTER(C.c_int64), _P]),
+    "wh_alignment_checksum": (C.c_int, [C.c_char_p, _P, C.c_int32, C.c_int64, C.POINTER(C.c_uint32)]),
+    "wh_ehmm_cksum": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]),
     "wh_ehmm_free": (None, [_P]),
     "wh_ehmm_count": (C.c_int, [_P]),
     "wh_ehmm_alphabet": (C.c_int, [_P]),

@@ -219,6 +219,13 @@ int wh_ehmm_map(const wh_ehmm *e, int h, int32_t *map_cols) {
   return WH_OK;
 }
 
+int wh_ehmm_cksum(const wh_ehmm *e, int h, uint32_t *cksum, int32_t *present) {
+  if (!e || h < 0 || h >= (int)e->hmms.size() || !cksum || !present) { set_error("wh_ehmm_cksum: bad argument"); return WH_EINVAL; }
+  const HostHMM &m = e->hmms[(size_t)h];
+  *cksum = m.cksum; *present = m.has_cksum ? 1 : 0;
+  return WH_OK;
+}
+
 int wh_set_option(wh_ehmm *e, const char *name, const char *value) {
   if (!e || !name) { set_error("wh_set_option: bad argument"); return WH_EINVAL; }
   const int set = set_knob(e->knobs, name, value);
@@ -333,7 +340,7 @@ int wh_last_score_launches(wh_ehmm *e, int32_t *cells_per_lane, int32_t *kind, d
 }
 
 int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches) {
-  if (!e || which < 0 || which > 6) return WH_EINVAL;
+  if (!e || which < 0 || which > 7) return WH_EINVAL;
   KernelTimer &t = e->timers[which];
   if (t.pending) {
     HIPCHK(hipEventSynchronize(t.e1));

@@ -337,15 +337,9 @@ struct Built {
   std::vector<float> compo;
 };
 
-// who: the caller's name for the messages ("wh_hmmbuild", "wh_hmmbuild_batch: model 3")
-int build_model(const char *who, const char *molecule, int32_t nseq, int64_t alen, const char *const *rows, double ere, double symfrac,
-                double fragthresh, Built &b) {
-  if (!molecule || !rows || nseq < 1 || alen < 1) { wh::set_error("%s: bad argument", who); return WH_EINVAL; }
-  Alphabet &abc = b.abc;
-  if (!make_alphabet(molecule, abc)) { wh::set_error("%s: unknown molecule '%s' (dna, rna, amino)", who, molecule); return WH_EINVAL; }
-  const int K = abc.K;
-  // ---- digitize
-  std::vector<uint8_t> ax((size_t)nseq * alen);
+// the alignment's rows as digital residues [nseq][alen]; a character outside the alphabet is refused
+int digitize_rows(const char *who, const Alphabet &abc, int32_t nseq, int64_t alen, const char *const *rows, std::vector<uint8_t> &ax) {
+  ax.resize((size_t)nseq * alen);
   for (int i = 0; i < nseq; i++) {
     if (!rows[i]) { wh::set_error("%s: row %d is NULL", who, i); return WH_EINVAL; }
     for (int64_t p = 0; p < alen; p++) {
@@ -355,10 +349,28 @@ int build_model(const char *who, const char *molecule, int32_t nseq, int64_t ale
       ax[(size_t)i * alen + p] = x;
     }
   }
-  // ---- alignment checksum (Jenkins one-at-a-time over the digital residues), as hmmbuild's CKSUM line
+  return WH_OK;
+}
+
+// hmmbuild's CKSUM line: Jenkins' one-at-a-time hash over the digital residues, gaps included (case and the gap character
+// do not enter it: they digitise alike)
+uint32_t alignment_checksum(const std::vector<uint8_t> &ax) {
   uint32_t cksum = 0;
   for (size_t z = 0; z < ax.size(); z++) { cksum += ax[z]; cksum += (cksum << 10); cksum ^= (cksum >> 6); }
   cksum += (cksum << 3); cksum ^= (cksum >> 11); cksum += (cksum << 15);
+  return cksum;
+}
+
+// who: the caller's name for the messages ("wh_hmmbuild", "wh_hmmbuild_batch: model 3")
+int build_model(const char *who, const char *molecule, int32_t nseq, int64_t alen, const char *const *rows, double ere, double symfrac,
+                double fragthresh, Built &b) {
+  if (!molecule || !rows || nseq < 1 || alen < 1) { wh::set_error("%s: bad argument", who); return WH_EINVAL; }
+  Alphabet &abc = b.abc;
+  if (!make_alphabet(molecule, abc)) { wh::set_error("%s: unknown molecule '%s' (dna, rna, amino)", who, molecule); return WH_EINVAL; }
+  const int K = abc.K;
+  std::vector<uint8_t> ax;
+  if (int rc = digitize_rows(who, abc, nseq, alen, rows, ax)) return rc;
+  const uint32_t cksum = alignment_checksum(ax);
   // ---- 1. position-based weights
   std::vector<double> wgt((size_t)nseq, 0.0);
   {
@@ -564,6 +576,18 @@ int text_out(const char *who, const std::string &s, char **out_text, int64_t *ou
 }
 
 }  // namespace
+
+extern "C" int wh_alignment_checksum(const char *molecule, const char *rows, int32_t nseq, int64_t alen, uint32_t *out_cksum) {
+  if (!molecule || !rows || nseq < 1 || alen < 1 || !out_cksum) { wh::set_error("wh_alignment_checksum: bad argument"); return WH_EINVAL; }
+  Alphabet abc;
+  if (!make_alphabet(molecule, abc)) { wh::set_error("wh_alignment_checksum: unknown molecule '%s' (dna, rna, amino)", molecule); return WH_EINVAL; }
+  std::vector<const char *> ptr((size_t)nseq);
+  for (int i = 0; i < nseq; i++) ptr[(size_t)i] = rows + (size_t)i * (size_t)alen;
+  std::vector<uint8_t> ax;
+  if (int rc = digitize_rows("wh_alignment_checksum", abc, nseq, alen, ptr.data(), ax)) return rc;
+  *out_cksum = alignment_checksum(ax);
+  return WH_OK;
+}
 
 extern "C" int wh_hmmbuild(const char *molecule, int32_t nseq, int64_t alen, const char *const *rows, const char *name,
                            double ere, double symfrac, double fragthresh, char **out_text, int64_t *out_len,

@@ -37,6 +37,8 @@ struct HostHMM {
   std::vector<double> t;      // [(M+1)*7]  MM MI MD IM II DM DD, as in the file (node 0..M)
   std::vector<double> mat;    // [(M+1)*K]
   std::vector<int32_t> map;   // [M+1]
+  bool has_map = false, has_cksum = false;   // the header's "MAP yes" and "CKSUM n" lines (hmmalign --mapali: wh_msa_mapali)
+  uint32_t cksum = 0;         // hmmbuild's checksum of the alignment the model was built from
   bool has_fstats = false;    // the file has a "STATS LOCAL FORWARD tau lambda" line (per-domain E-values: wh_ehmm_evparams)
   float ftau = 0.f, flambda = 0.f;
   // what the acceleration filters need (wh_filter.h): the probabilities in float32 as HMMER's parser holds them

@@ -104,6 +104,8 @@ int parse_hmm_file(const std::string &path, HostHMM &h) {
     if (key == "NAME" && tok.size() > 1) h.name = tok[1];
     else if (key == "LENG" && tok.size() > 1) h.M = atoi(tok[1].c_str());
     else if (key == "NSEQ" && tok.size() > 1) h.nseq = atoi(tok[1].c_str());
+    else if (key == "MAP" && tok.size() > 1) h.has_map = tok[1] == "yes";
+    else if (key == "CKSUM" && tok.size() > 1) { h.has_cksum = true; h.cksum = (uint32_t)strtoul(tok[1].c_str(), nullptr, 10); }
     else if (key == "ALPH" && tok.size() > 1) {
       std::string a = tok[1];
       for (auto &c : a) c = (char)tolower((unsigned char)c);

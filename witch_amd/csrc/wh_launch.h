@@ -384,11 +384,15 @@ hipError_t launch_merge_render(const MergeArgs &a, int64_t nrows, hipStream_t s)
 // columns and posteriors (CSR by the sequences' offsets).  Block k (0..M) is the insert block behind node k (0: the N flank,
 // M: the C flank); layout[0..M] its first alignment column, layout[M + 1] the alignment's width W.
 struct MsaArgs {
-  const int32_t *cols;         // per residue: 0-based node, or -1
-  const float *pp;             // per residue: posterior of its state on the path
+  const int32_t *cols;         // per residue: 0-based node; -1: an insert of the block behind the last match residue (a flank
+                               //   at the sequence's ends), as wh_align writes it; -(k + 2): an insert of block k whatever
+                               //   surrounds it (the rows of a --mapali alignment: wh_mapali.hip)
+  const float *pp;             // per residue r >= pp_shift: pp[r - pp_shift], the posterior of its state on the path
   const uint8_t *text;         // the sequences' characters as given
   const int64_t *off;          // [nq + 1]
   int64_t nq, total;           // total: residues the per-residue arrays hold (no kernel goes beyond it)
+  int64_t n_nopp, pp_shift;    // the first n_nopp sequences (residues 0 .. pp_shift - 1) carry no posteriors: no PP row, no part
+                               //   in PP_cons, never counted as pathless (0, 0: every sequence has them)
   int32_t M;
   int32_t trim;                // --trim: flank residues are dropped, blocks 0 and M stay empty
   int32_t *width;              // [M + 1] widest insert run per block (zeroed before the widths kernel)
@@ -398,7 +402,7 @@ struct MsaArgs {
   long long *layout;           // [M + 2]
   int32_t *matmap;             // [M] alignment column of node k + 1
   uint8_t *rf, *pp_cons;       // [W] (allocated for the largest possible W)
-  uint8_t *rows, *pp_rows;     // [nq][W]
+  uint8_t *rows, *pp_rows;     // [nq][W], [nq - n_nopp][W]
   float *ppm;                  // [chunk rows][M] posterior of the residue at a node, -1: none (a chunk of sequences)
   int64_t q0, q1;              // ... the chunk
   float *cons_sum;             // [M] running float32 sums, in sequence order ...
@@ -410,6 +414,23 @@ hipError_t launch_msa_layout(const MsaArgs &a, hipStream_t s);
 hipError_t launch_msa_render(const MsaArgs &a, long long W, bool lds, hipStream_t s);
 hipError_t launch_msa_cons(const MsaArgs &a, hipStream_t s);
 size_t msa_render_lds_bytes(long long W);
+
+// wh_msa_mapali_dev (wh_mapali.hip): the rows of the alignment a model was built from, as sequences for the kernels above.
+// colcode[alen]: per alignment column node - 1, or -(k + 2) for an insert column of block k (made from MAP on the host).
+struct MapaliArgs {
+  const uint8_t *rows;         // [n_map][alen] the alignment's characters (a letter is a residue, anything else a gap)
+  int64_t n_map, alen;
+  const int32_t *colcode;      // [alen]
+  int32_t *count;              // [n_map] residues per row (count kernel)
+  const int64_t *off;          // [n_map + 1] their CSR (formed on the host from count), read by the map kernel
+  uint8_t *text;               // packed residues' characters ...
+  int32_t *cols;               // ... and codes
+  const int64_t *seq_off;      // [nq + 1] the new sequences' offsets ...
+  int64_t nq, shift;
+  int64_t *all_off;            // ... [n_map + nq + 1]: off, then seq_off + shift
+};
+hipError_t launch_mapali_count(const MapaliArgs &a, hipStream_t s);
+hipError_t launch_mapali_map(const MapaliArgs &a, hipStream_t s);
 constexpr size_t kMsaLdsBudget = 64 * 1024;   // the two rows of a sequence in LDS: up to 32 K columns, two workgroups per CU stay resident
 
 struct TopkArgs {

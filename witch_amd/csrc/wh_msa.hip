@@ -4,7 +4,9 @@
 // tests/golden/msa against the bundled 3.1b2 binary): every node is a column; block k (0..M) between the columns of nodes k
 // and k + 1 is as wide as the LONGEST insert run any sequence has there; N-flank residues (block 0) are right-justified,
 // C-flank residues (block M) left-justified, an internal run of n puts its first n / 2 residues flush left and the rest
-// flush right; --trim drops both flanks.
+// flush right; --trim drops both flanks.  A residue's code may also NAME its block, -(k + 2), whatever surrounds it - the
+// rows of a --mapali alignment (wh_mapali.hip), the first n_nopp sequences: they carry no posteriors, get no PP row and
+// take no part in PP_cons.
 //   msa_widths_kernel   one wavefront per sequence; the thread that finds the first residue of an insert run walks it:
 //                       run length -> atomicMax into width[block] (integer max: order-independent), per residue its block and
 //                       its cell (from the left end, or from the right end) - the render kernel then needs no second walk;
@@ -35,21 +37,42 @@ __device__ __forceinline__ uint8_t msa_pp_char(float p) {
   return (uint8_t)('0' + d);
 }
 
+// a residue's insert block where its code names it: -(k + 2) -> k
+__device__ __forceinline__ int msa_code_block(int c) { return -(c + 2); }
+
+// NAMED: the codes -(k + 2) have their meaning (a call with --mapali rows); without, the kernel is wh_msa's as it always was
+template <bool NAMED>
 __global__ __launch_bounds__(64) void msa_widths_kernel(MsaArgs a) {
   const int64_t q = blockIdx.x;
   const int64_t lo = a.off[q], hi = a.off[q + 1] < a.total ? a.off[q + 1] : a.total;
   for (int64_t r = lo + threadIdx.x; r < hi; r += blockDim.x) {
-    if (msa_is_match(a.cols[r], a.M)) continue;
-    if (r > lo && !msa_is_match(a.cols[r - 1], a.M)) continue;      // inside a run: its first residue's thread walks it
+    const int c0 = a.cols[r];
+    if (msa_is_match(c0, a.M)) continue;
+    // a run: residues outside the match columns that share a block.  A code of -1 (or any other value without a meaning)
+    // takes its block from what surrounds it, so such a run ends at the next match residue or explicit code; a code
+    // -(k + 2), k in 0..M, names block k, so a run ends where the code changes, even with no match residue between.
+    const bool named = NAMED && c0 <= -2 && c0 >= -(a.M + 2);
+    auto in_run = [&](int c) {
+      if (!NAMED) return !msa_is_match(c, a.M);
+      return named ? c == c0 : !msa_is_match(c, a.M) && !(c <= -2 && c >= -(a.M + 2));
+    };
+    if (r > lo && in_run(a.cols[r - 1])) continue;                    // inside a run: its first residue's thread walks it
     int64_t e = r + 1;
-    while (e < hi && !msa_is_match(a.cols[e], a.M)) e++;
+    while (e < hi && in_run(a.cols[e])) e++;
     const int64_t n = e - r;
-    const bool nflank = r == lo, cflank = e == hi;
+    bool nflank, cflank;
     int blk;
-    if (nflank && cflank) { blk = -1; atomicAdd(a.pathless, 1); }     // no match state at all: gaps only, counted
-    else if (nflank) blk = a.trim ? -1 : 0;
-    else if (cflank) blk = a.trim ? -1 : a.M;
-    else blk = a.cols[r - 1] + 1;
+    if (named) {
+      blk = msa_code_block(c0);
+      nflank = blk == 0; cflank = blk == a.M;
+      if ((nflank || cflank) && a.trim) blk = -1;
+    } else {
+      nflank = r == lo; cflank = e == hi;
+      if (nflank && cflank) { blk = -1; if (!NAMED || q >= a.n_nopp) atomicAdd(a.pathless, 1); }     // no match state at all: gaps only, counted
+      else if (nflank) blk = a.trim ? -1 : 0;
+      else if (cflank) blk = a.trim ? -1 : a.M;
+      else { const int p = a.cols[r - 1]; blk = !NAMED || msa_is_match(p, a.M) ? p + 1 : msa_code_block(p); }
+    }
     if (blk >= 0) atomicMax(a.width + blk, (int)n);
     for (int64_t i = 0; i < n; i++) {
       a.res_blk[r + i] = blk;
@@ -83,21 +106,24 @@ __global__ __launch_bounds__(256) void msa_layout_kernel(MsaArgs a) {
 // the two rows of one sequence.  LDS: both rows are built in LDS, each at the offset its global row has inside a 16-byte
 // line, so that aligned 16-byte pieces of LDS are aligned 16-byte pieces of the output; the unaligned head and tail of a
 // row go out byte by byte.  Without LDS the rows are built in place.
-template <bool LDS>
+// PP: the sequences of the launch have posteriors (false: the rows of a --mapali alignment, the sequence row alone)
+template <bool LDS, bool PP>
 __global__ __launch_bounds__(kMsaRenderThreads) void msa_render_kernel(MsaArgs a) {
   extern __shared__ __align__(16) uint8_t msa_smem[];
   const int64_t q = a.q0 + blockIdx.x;
   const long long W = a.layout[a.M + 1];
   const int tid = threadIdx.x;
-  uint8_t *grow = a.rows + (size_t)q * (size_t)W, *gpp = a.pp_rows + (size_t)q * (size_t)W;
+  constexpr bool has_pp = PP;
+  uint8_t *grow = a.rows + (size_t)q * (size_t)W, *gpp = has_pp ? a.pp_rows + (size_t)(q - a.n_nopp) * (size_t)W : nullptr;
   const size_t stride = (size_t)((W + 30) >> 4) << 4;
   const int shift_row = LDS ? (int)(reinterpret_cast<uintptr_t>(grow) & 15) : 0;
   const int shift_pp = LDS ? (int)(reinterpret_cast<uintptr_t>(gpp) & 15) : 0;
   uint8_t *row = LDS ? msa_smem + shift_row : grow;
   uint8_t *ppr = LDS ? msa_smem + stride + shift_pp : gpp;
-  float *ppm = a.ppm + (size_t)blockIdx.x * (size_t)a.M;
-  for (long long c = tid; c < W; c += kMsaRenderThreads) { row[c] = a.rf[c] == 'x' ? '-' : '.'; ppr[c] = '.'; }
-  for (int k = tid; k < a.M; k += kMsaRenderThreads) ppm[k] = -1.0f;
+  float *ppm = has_pp ? a.ppm + (size_t)blockIdx.x * (size_t)a.M : nullptr;
+  const float *pp = a.pp - a.pp_shift;
+  for (long long c = tid; c < W; c += kMsaRenderThreads) { row[c] = a.rf[c] == 'x' ? '-' : '.'; if (has_pp) ppr[c] = '.'; }
+  if (has_pp) for (int k = tid; k < a.M; k += kMsaRenderThreads) ppm[k] = -1.0f;
   __syncthreads();
   const int64_t lo = a.off[q], hi = a.off[q + 1] < a.total ? a.off[q + 1] : a.total;
   for (int64_t r = lo + tid; r < hi; r += kMsaRenderThreads) {
@@ -108,7 +134,7 @@ __global__ __launch_bounds__(kMsaRenderThreads) void msa_render_kernel(MsaArgs a
     if (msa_is_match(c, a.M)) {
       if (alpha) ch &= 0xDF;
       at = a.matmap[c];
-      ppm[c] = a.pp[r];
+      if (has_pp) ppm[c] = pp[r];
     } else {
       const int b = a.res_blk[r];
       if (b < 0) continue;                             // a trimmed flank, a sequence without a path
@@ -117,11 +143,11 @@ __global__ __launch_bounds__(kMsaRenderThreads) void msa_render_kernel(MsaArgs a
       at = a.layout[b] + (k >= 0 ? k : a.width[b] + k);
     }
     row[at] = ch;
-    ppr[at] = msa_pp_char(a.pp[r]);
+    if (has_pp) ppr[at] = msa_pp_char(pp[r]);
   }
   if (!LDS) return;
   __syncthreads();
-  for (int which = 0; which < 2; which++) {
+  for (int which = 0; which < (has_pp ? 2 : 1); which++) {
     uint8_t *dst = which ? gpp : grow;
     const uint8_t *src = which ? ppr : row;
     const int shift = which ? shift_pp : shift_row;
@@ -155,7 +181,8 @@ __global__ __launch_bounds__(64) void msa_cons_kernel(MsaArgs a) {
 size_t msa_render_lds_bytes(long long W) { return 2 * ((size_t)((W + 30) >> 4) << 4); }
 
 hipError_t launch_msa_widths(const MsaArgs &a, hipStream_t s) {
-  if (a.nq > 0) hipLaunchKernelGGL(msa_widths_kernel, dim3((unsigned)a.nq), dim3(64), 0, s, a);
+  if (a.nq > 0 && a.n_nopp > 0) hipLaunchKernelGGL(msa_widths_kernel<true>, dim3((unsigned)a.nq), dim3(64), 0, s, a);
+  else if (a.nq > 0) hipLaunchKernelGGL(msa_widths_kernel<false>, dim3((unsigned)a.nq), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
@@ -164,15 +191,19 @@ hipError_t launch_msa_layout(const MsaArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// the sequences q0 .. q1 - 1; <lds>: the caller checked msa_render_lds_bytes(W) against kMsaLdsBudget
+// the sequences q0 .. q1 - 1 (all with posteriors or all without: ppm holds the rows of a chunk from its row 0); <lds>: the caller checked msa_render_lds_bytes(W) against kMsaLdsBudget
 hipError_t launch_msa_render(const MsaArgs &a, long long W, bool lds, hipStream_t s) {
   const unsigned n = (unsigned)(a.q1 - a.q0);
   if (n == 0) return hipSuccess;
+  const bool pp = a.q0 >= a.n_nopp;
+  if (!pp && a.q1 > a.n_nopp) return hipErrorInvalidValue;
   if (lds) {
     if (msa_render_lds_bytes(W) > kMsaLdsBudget) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(msa_render_kernel<true>, dim3(n), dim3(kMsaRenderThreads), msa_render_lds_bytes(W), s, a);
+    if (pp) hipLaunchKernelGGL((msa_render_kernel<true, true>), dim3(n), dim3(kMsaRenderThreads), msa_render_lds_bytes(W), s, a);
+    else hipLaunchKernelGGL((msa_render_kernel<true, false>), dim3(n), dim3(kMsaRenderThreads), msa_render_lds_bytes(W), s, a);
   } else {
-    hipLaunchKernelGGL(msa_render_kernel<false>, dim3(n), dim3(kMsaRenderThreads), 0, s, a);
+    if (pp) hipLaunchKernelGGL((msa_render_kernel<false, true>), dim3(n), dim3(kMsaRenderThreads), 0, s, a);
+    else hipLaunchKernelGGL((msa_render_kernel<false, false>), dim3(n), dim3(kMsaRenderThreads), 0, s, a);
   }
   return hipGetLastError();
 }

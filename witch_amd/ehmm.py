@@ -26,6 +26,17 @@ def pack_queries(seqs):
     return np.ascontiguousarray(res), offs
 
 
+def alignment_checksum(molecule, rows):
+    """hmmbuild's CKSUM of an alignment (wh_alignment_checksum): rows of one length (str or bytes), molecule "dna" | "rna" |
+    "amino".  Host code, no GPU."""
+    rows = [r.encode() if isinstance(r, str) else bytes(r) for r in rows]
+    if not rows or len(set(len(r) for r in rows)) != 1:
+        raise ValueError("alignment_checksum: the rows must be of one length")
+    out = C.c_uint32(0)
+    check(lib().wh_alignment_checksum(molecule.encode(), b"".join(rows), len(rows), len(rows[0]), C.byref(out)), "wh_alignment_checksum")
+    return int(out.value)
+
+
 class EHMM:
     def __init__(self, hmm_paths, hmm_index=None, nseq=None, device: int = 0):
         L = lib()
@@ -301,25 +312,42 @@ class EHMM:
         ptrs = [C.c_void_p(None) for _ in range(5)]
         return W, npl, ptrs
 
-    def _msa_collect(self, nq, h, W, npl, ptrs):
-        """The malloc'ed buffers of wh_msa / wh_msa_dev as numpy arrays (copied; the buffers are released)."""
+    def _msa_collect(self, nq, h, W, npl, ptrs, n_map=0):
+        """The malloc'ed buffers of wh_msa / wh_msa_dev (and their --mapali forms: n_map rows in front, without PP rows) as
+        numpy arrays (copied; the buffers are released)."""
         W, M = int(W.value), int(self.M[h])
-        sizes = [(nq * W, np.uint8), (nq * W, np.uint8), (W, np.uint8), (W, np.uint8), (M, np.int32)]
+        sizes = [((n_map + nq) * W, np.uint8), (nq * W, np.uint8), (W, np.uint8), (W, np.uint8), (M, np.int32)]
         out = []
         for ptr, (n, dt) in zip(ptrs, sizes):
             nbytes = n * np.dtype(dt).itemsize
             out.append(np.frombuffer((C.c_char * nbytes).from_address(ptr.value), dtype=dt).copy() if nbytes else np.zeros(0, dtype=dt))
             lib().wh_free_text(ptr)
         rows, pp_rows, pp_cons, rf, matmap = out
-        return {"W": W, "rows": rows.reshape(nq, W), "pp_rows": pp_rows.reshape(nq, W), "pp_cons": pp_cons, "rf": rf,
+        return {"W": W, "rows": rows.reshape(n_map + nq, W), "pp_rows": pp_rows.reshape(nq, W), "pp_cons": pp_cons, "rf": rf,
                 "matmap": matmap, "pathless": int(npl.value)}
 
-    def msa(self, residues, offsets, text, h=0, trim=False, no_lds=False):
+    @staticmethod
+    def _mapali_rows(mapali):
+        """mapali = (names, rows) -> uint8 [n_map, alen]: the rows (str, bytes or uint8 arrays) of one length."""
+        rows = [r.encode() if isinstance(r, str) else bytes(bytearray(r)) for r in mapali[1]]
+        if len(set(len(r) for r in rows)) > 1:
+            raise ValueError("msa: the rows of the mapali alignment differ in length")
+        return np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), len(rows[0]) if rows else 0)
+
+    def cksum(self, h=0):
+        """The CKSUM line of model h (hmmbuild's checksum of the alignment it was built from), None where the file has none."""
+        v, present = C.c_uint32(0), C.c_int32(0)
+        check(lib().wh_ehmm_cksum(self._h, int(h), C.byref(v), C.byref(present)), "wh_ehmm_cksum")
+        return int(v.value) if present.value else None
+
+    def msa(self, residues, offsets, text, h=0, trim=False, no_lds=False, mapali=None):
         """hmmalign's alignment of ALL the sequences to model h (include/witch_hip.h: wh_msa): the sequences are aligned
         (wh_align_pp_dev) and the alignment is assembled on the device.  text: the sequences' characters as given, one
         byte per residue (bytes, str or uint8 array).  Returns {"W", "rows" uint8 [nq, W], "pp_rows" uint8 [nq, W],
         "pp_cons" uint8 [W], "rf" uint8 [W], "matmap" int32 [M], "pathless"}; trim: hmmalign --trim; no_lds: test hook
-        (WH_MSA_NO_LDS)."""
+        (WH_MSA_NO_LDS).  mapali=(names, rows): hmmalign --mapali (wh_msa_mapali) - the rows of the alignment the model was
+        built from come first in "rows" ([n_map + nq, W]); they have no PP rows ("pp_rows" stays [nq, W]).  An alignment that
+        is not the model's (checksum mismatch) raises."""
         residues = np.ascontiguousarray(residues, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         if isinstance(text, str):
@@ -330,6 +358,12 @@ class EHMM:
             raise ValueError("msa: residues, text and offsets disagree")
         W, npl, ptrs = self._msa_outputs()
         flags = (_lib.WH_MSA_TRIM if trim else 0) | (_lib.WH_MSA_NO_LDS if no_lds else 0)
+        if mapali is not None:
+            mrows = self._mapali_rows(mapali)
+            check(lib().wh_msa_mapali(self._h, residues.ctypes.data, offsets.ctypes.data, text.ctypes.data, nq, int(h), flags,
+                                      mrows.ctypes.data, mrows.shape[0], mrows.shape[1], C.byref(W), *[C.byref(p) for p in ptrs],
+                                      C.byref(npl)), "wh_msa_mapali")
+            return self._msa_collect(nq, int(h), W, npl, ptrs, n_map=mrows.shape[0])
         check(lib().wh_msa(self._h, residues.ctypes.data, offsets.ctypes.data, text.ctypes.data, nq, int(h), flags, C.byref(W),
                            *[C.byref(p) for p in ptrs], C.byref(npl)), "wh_msa")
         return self._msa_collect(nq, int(h), W, npl, ptrs)
@@ -472,13 +506,22 @@ class EHMM:
                                         self._stream()), "wh_align_pp_dev")
         return (cols, pp) if want_pp else cols
 
-    def msa_t(self, cols_t, pp_t, text_t, offsets_t, h=0, trim=False, no_lds=False):
+    def msa_t(self, cols_t, pp_t, text_t, offsets_t, h=0, trim=False, no_lds=False, mapali_t=None):
         """The assembly alone (wh_msa_dev) on torch tensors resident on the device: cols int32 and pp float32 as
         align_t(want_pp=True) returns them for the pairs (q, h), text uint8, offsets int64 [nq + 1].  Returns what msa
-        returns (numpy arrays: the library hands the alignment back in host memory)."""
+        returns (numpy arrays: the library hands the alignment back in host memory).  mapali_t: a uint8 tensor
+        [n_map, alen] on the device, the rows of the alignment the model was built from (wh_msa_mapali_dev; the checksum is
+        the caller's to verify: witch_amd.ehmm.alignment_checksum against cksum())."""
         nq = offsets_t.numel() - 1
         W, npl, ptrs = self._msa_outputs()
         flags = (_lib.WH_MSA_TRIM if trim else 0) | (_lib.WH_MSA_NO_LDS if no_lds else 0)
+        if mapali_t is not None:
+            n_map, alen = int(mapali_t.shape[0]), int(mapali_t.shape[1])
+            mapali_t = mapali_t.contiguous()
+            check(lib().wh_msa_mapali_dev(self._h, cols_t.data_ptr(), pp_t.data_ptr(), text_t.data_ptr(), offsets_t.data_ptr(), nq,
+                                          int(cols_t.numel()), int(h), flags, mapali_t.data_ptr(), n_map, alen, C.byref(W),
+                                          *[C.byref(p) for p in ptrs], C.byref(npl), self._stream()), "wh_msa_mapali_dev")
+            return self._msa_collect(nq, int(h), W, npl, ptrs, n_map=n_map)
         check(lib().wh_msa_dev(self._h, cols_t.data_ptr(), pp_t.data_ptr(), text_t.data_ptr(), offsets_t.data_ptr(), nq,
                                int(cols_t.numel()), int(h), flags, C.byref(W), *[C.byref(p) for p in ptrs], C.byref(npl),
                                self._stream()), "wh_msa_dev")

@@ -9,5 +9,7 @@ fork), so the executables are thin C clients (client.c) of ONE resident server p
 (server.py) that owns the GPU: they pass argv over a UNIX socket and exit with its status; the
 server writes the output files - text that evalHMMSearchOutput (algorithm.py:579-605) and
 ExtendedAlignment._read_sto (helpers/alignment_tools.py:926-955) accept.  A sequence file with several
-records (MAGUS' hmmAlignQueries, SEPP, UPP) gets hmmalign's one alignment of all of them (wh_msa).
+records (MAGUS' hmmAlignQueries, SEPP, UPP) gets hmmalign's one alignment of all of them (wh_msa); with
+--mapali ALN the rows of the alignment the model was built from come first (wh_msa_mapali: UPP's and SEPP's extended
+alignment of a subset).
 """

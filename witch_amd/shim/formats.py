@@ -366,12 +366,47 @@ def _text(x):
     return (x if isinstance(x, (bytes, bytearray)) else bytes(bytearray(x))).decode("ascii")
 
 
-def format_msa(names, rows, pp_rows, pp_cons, rf, outformat="Stockholm", width=200):
+def read_msa(path):
+    """An alignment file, aligned FASTA or Stockholm (told apart by the "# STOCKHOLM" line; Pfam's one block or interleaved
+    blocks): {"names", "rows" (one length, the characters as given), "desc": {name: text of its "#=GS name DE" line}}.  Other
+    Stockholm annotation is skipped.  ValueError for rows of different lengths, a repeated FASTA name or an empty file."""
+    with open(path) as f:
+        lines = f.read().splitlines()
+    first = next((ln for ln in lines if ln.strip()), "")
+    names, rows, desc = [], {}, {}
+    if first.startswith("# STOCKHOLM"):
+        for ln in lines:
+            if ln.startswith("//"):
+                break
+            w = ln.split(None, 3)
+            if ln.startswith("#=GS") and len(w) >= 3 and w[2] == "DE":
+                desc[w[1]] = w[3].strip() if len(w) > 3 else ""
+            elif ln.strip() and not ln.startswith("#"):
+                n, t = ln.split()[:2]
+                if n not in rows:
+                    names.append(n)
+                    rows[n] = []
+                rows[n].append(t)
+    else:
+        for n, t in read_fasta(path):
+            if n in rows:
+                raise ValueError("alignment file %s: the name %s is repeated" % (path, n))
+            names.append(n)
+            rows[n] = [t]
+    out = ["".join(rows[n]) for n in names]
+    if not out or len(set(len(r) for r in out)) != 1 or not out[0]:
+        raise ValueError("alignment file %s is empty, or its rows differ in length" % path)
+    return {"names": names, "rows": out, "desc": desc}
+
+
+def format_msa(names, rows, pp_rows, pp_cons, rf, outformat="Stockholm", width=200, desc=None):
     """hmmalign's output for an alignment of several sequences (EHMM.msa: rows, pp_rows [nq][W], pp_cons, rf [W]; str,
     bytes or uint8 arrays; rf None: no "#=GC RF" line, as for a model with a reference line of its own), byte for byte
     HMMER 3.1b2's: "Stockholm" in blocks of <width> columns, every block with its "#=GR PP" and "#=GC" lines; "Pfam" in
     one block; "afa" the rows alone, 60 characters per line.  The format's name is matched without case, as Easel does;
-    any other format raises FormatError."""
+    any other format raises FormatError.  An entry of pp_rows may be None: a row without posteriors (a row of the --mapali
+    alignment) gets no "#=GR PP" line.  desc: {name: text}, hmmalign's "#=GS name DE text" block in front of the rows (in
+    afa: behind the name)."""
     fmt = str(outformat).lower()
     if fmt not in MSA_FORMATS:
         raise FormatError("%s is not a recognized output MSA file format" % outformat)
@@ -380,24 +415,30 @@ def format_msa(names, rows, pp_rows, pp_cons, rf, outformat="Stockholm", width=2
     if fmt == "afa":
         out = []
         for n, r in zip(names, rows):
-            out.append(">" + n)
+            out.append(">" + n + (" " + desc[n] if desc and n in desc else ""))
             out.extend(r[a:a + 60] for a in range(0, len(r), 60))
         return "\n".join(out) + "\n" if out else ""
-    pps = [_text(r) for r in pp_rows]
+    pps = [None if r is None else _text(r) for r in pp_rows]
     cons = _text(pp_cons)
     rfl = None if rf is None else _text(rf)
     W = len(cons)
     namew = max([len(n) for n in names] + [1])
-    margin = max(namew + 1, len("#=GC PP_cons "), namew + len("#=GR  PP "))      # Easel: the widest of the line tags, plus a space
+    margin = max(namew + 1, len("#=GC PP_cons "))                                 # Easel: the widest of the line tags, plus a space
+    if any(p is not None for p in pps) or not pps:
+        margin = max(margin, namew + len("#=GR  PP "))
     if rfl is not None:
         margin = max(margin, len("#=GC RF "))
     step = W if fmt == "pfam" or W == 0 else width
     out = ["# STOCKHOLM 1.0", ""]
+    if desc and any(n in desc for n in names):
+        out.extend("#=GS %-*s DE %s" % (namew, n, desc[n]) for n in names if n in desc)
+        out.append("")
     starts = list(range(0, max(W, 1), max(step, 1)))
     for a in starts:
         for n, r, p in zip(names, rows, pps):
             out.append("%-*s%s" % (margin, n, r[a:a + step]))
-            out.append("%-*s%s" % (margin, "#=GR %-*s PP" % (namew, n), p[a:a + step]))
+            if p is not None:
+                out.append("%-*s%s" % (margin, "#=GR %-*s PP" % (namew, n), p[a:a + step]))
         out.append("%-*s%s" % (margin, "#=GC PP_cons", cons[a:a + step]))
         if rfl is not None:
             out.append("%-*s%s" % (margin, "#=GC RF", rfl[a:a + step]))

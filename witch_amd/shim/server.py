@@ -129,6 +129,10 @@ def check_hmmsearch_options(opts):
                 raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
 
 
+class MapaliMismatch(Exception):
+    """The --mapali alignment is not the one the model was built from (its checksum is not the model's CKSUM)."""
+
+
 def parse_hmmalign_argv(argv):
     takes_value = {"-o", "--mapali", "--informat", "--outformat"}
     opts, pos, i = {}, [], 0
@@ -236,14 +240,21 @@ class GpuBackend:
                     out[j] = (int(e.M[0]), cols[co[n]:co[n + 1]].copy(), pp[co[n]:co[n + 1]].copy())
         return out
 
-    def align_msa(self, hmm_path, records, trim=False):
+    def align_msa(self, hmm_path, records, trim=False, mapali=None):
         """records: [(name, text)] -> EHMM.msa's dict: hmmalign's ONE alignment of all the sequences to the model, aligned
         and assembled on the device (wh_msa).  The rows carry the records' own characters, match residues upper case and
-        inserts lower case."""
+        inserts lower case.  mapali=(names, rows): hmmalign --mapali, the rows of the model's own alignment in front
+        (wh_msa_mapali); MapaliMismatch where the alignment is not the one the model came from."""
+        from witch_amd.ehmm import alignment_checksum
         with self.lock:
             e, hdr = self.model(hmm_path)
             res, offs = e.digitize_many([t.upper() for _, t in records])
-            return e.msa(res, offs, "".join(t for _, t in records), h=0, trim=trim)
+            if mapali is None:
+                return e.msa(res, offs, "".join(t for _, t in records), h=0, trim=trim)
+            want = e.cksum(0)
+            if want is not None and alignment_checksum({2: "amino", 1: "rna"}.get(e.alphabet, "dna"), mapali[1]) != want:
+                raise MapaliMismatch()
+            return e.msa(res, offs, "".join(t for _, t in records), h=0, trim=trim, mapali=mapali)
 
 
 class AlignBatcher:
@@ -335,6 +346,12 @@ class Server:
         if not os.path.exists(fa):
             raise ArgError("Error: Failed to open sequence file %s for reading" % fa)
         records = formats.read_fasta(fa)
+        if "--mapali" in opts:
+            # the rows of the model's alignment come with every call, also one for a single sequence
+            if not hasattr(self.backend, "align_msa"):
+                raise ArgError("witch-hip hmmalign shim: --mapali needs a backend that assembles alignments (align_msa); "
+                               "this one does not, and the option is not ignored")
+            return self.run_hmmalign_msa(opts, hmm, fa, records, cwd)
         if len(records) != 1 and hasattr(self.backend, "align_msa"):
             return self.run_hmmalign_msa(opts, hmm, fa, records, cwd)
         if len(records) != 1:
@@ -365,9 +382,27 @@ class Server:
         outformat = opts.get("--outformat", "Stockholm")
         if str(outformat).lower() not in formats.MSA_FORMATS:
             raise ArgError("ERROR: %s is not a recognized output MSA file format (witch-hip hmmalign shim: Stockholm, Pfam, afa)" % outformat)
-        m = self.backend.align_msa(hmm, records, trim="--trim" in opts)
-        text = formats.format_msa([n for n, _ in records], m["rows"], m["pp_rows"], m["pp_cons"],
-                                  None if formats.hmm_has_rf(hmm) else m["rf"], outformat)
+        names, pp_rows, desc = [n for n, _ in records], None, None
+        if "--mapali" in opts:
+            ali_path = os.path.join(cwd, opts["--mapali"])
+            if not os.path.exists(ali_path):
+                raise ArgError("Error: Failed to open --mapali alignment file %s for reading" % ali_path)
+            try:
+                ali = formats.read_msa(ali_path)
+            except ValueError as ex:
+                raise ArgError("Error: %s" % ex)
+            try:
+                m = self.backend.align_msa(hmm, records, trim="--trim" in opts, mapali=(ali["names"], ali["rows"]))
+            except MapaliMismatch:
+                # HMMER's own words and its exit status 1
+                raise ArgError("--mapali MSA %s isn't same as the one HMM came from (checksum mismatch)" % opts["--mapali"])
+            names, desc = ali["names"] + names, ali["desc"]
+            pp_rows = [None] * len(ali["names"]) + list(m["pp_rows"])
+        else:
+            m = self.backend.align_msa(hmm, records, trim="--trim" in opts)
+            pp_rows = m["pp_rows"]
+        text = formats.format_msa(names, m["rows"], pp_rows, m["pp_cons"], None if formats.hmm_has_rf(hmm) else m["rf"], outformat,
+                                  **({"desc": desc} if desc else {}))
         if "-o" in opts:
             with open(os.path.join(cwd, opts["-o"]), "w") as f:
                 f.write(text)
