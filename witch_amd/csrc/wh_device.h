@@ -235,7 +235,14 @@ struct LdsF4 {      // float4 pieces of an LDS-resident array
   __device__ __forceinline__ float4 operator[](int i) const { const v4f_t v = p[i]; return make_float4(v.x, v.y, v.z, v.w); }
 };
 
-template <int Q>
+// DRAIN (the fallback of a degenerate code, where a sweep asks for it): the loads from L2 complete INSIDE their branch.  Left
+// pending, they reach the point where the branches meet, and the compiler guards the first use of the row - on the LDS path
+// too - with s_waitcnt vmcnt(0).  gfx950 counts loads and stores on the one vmcnt: on a canonical residue, which has no emission
+// load in flight, that wait catches whatever else the wave has outstanding - the row stores of a storing Forward sweep, the row
+// a Backward sweep has requested ahead.  (0x0F70: vmcnt(0), expcnt and lgkmcnt left open.)
+__device__ __forceinline__ void wait_vmcnt0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
+template <int Q, bool DRAIN = false>
 __device__ __forceinline__ void load_em_fwd(float (&od)[Q], const float *emL, const float *emG, int x, int K,
                                             int lane) {
   if (x < K) {
@@ -252,11 +259,12 @@ __device__ __forceinline__ void load_em_fwd(float (&od)[Q], const float *emL, co
       float4 v = p[q4 * kWave];
       od[4 * q4] = v.x; od[4 * q4 + 1] = v.y; od[4 * q4 + 2] = v.z; od[4 * q4 + 3] = v.w;
     }
+    if (DRAIN) wait_vmcnt0();
   }
 }
 
 // reversed node order: position (lane, p) is forward position (63-lane, Q-1-p)
-template <int Q>
+template <int Q, bool DRAIN = false>
 __device__ __forceinline__ void load_em_rev(float (&od)[Q], const float *emL, const float *emG, int x, int K,
                                             int lane) {
   if (x < K) {
@@ -273,6 +281,7 @@ __device__ __forceinline__ void load_em_rev(float (&od)[Q], const float *emL, co
       float4 v = p[(Q / 4 - 1 - p4) * kWave];
       od[4 * p4] = v.w; od[4 * p4 + 1] = v.z; od[4 * p4 + 2] = v.y; od[4 * p4 + 3] = v.x;
     }
+    if (DRAIN) wait_vmcnt0();
   }
 }
 
@@ -396,7 +405,9 @@ __device__ __forceinline__ void region_scan_global(float *spec, int SP, int L, i
 // stays 0 on every row, so the sweep keeps no J recurrence and stores no J row - what it leaves out multiplies by 0 or by 1, the
 // stored values are the same bits - and the Backward sweep that reads the rows must not read J (its UNI flag).
 // LAYOUT: where a row's special states go (SpecAt, above).
-template <int Q, bool TREG, bool STORE, bool USEP = false, bool SLIM = false, bool UM = false, bool COUNT = false, bool BLK = false, bool UNI = false, int LAYOUT = SPEC_SOA>
+// DRAIN: the residue code is taken wave-uniform, so the choice between the two emission sources is a scalar branch, and the L2
+// branch completes its loads itself (load_em_fwd): a storing sweep's row then never waits for the stores of the row before it.
+template <int Q, bool TREG, bool STORE, bool USEP = false, bool SLIM = false, bool UM = false, bool COUNT = false, bool BLK = false, bool UNI = false, int LAYOUT = SPEC_SOA, bool DRAIN = false>
 __device__ __forceinline__ void forward_sweep(const TransTab<Q, TREG> &T, const ScanC &sc, const float *emL,
                                               const float *emG, int K, const uint8_t *seq, int L, LenCfg cfg,
                                               float *spec, int SP, float *Fs, float keep_scale, int lane,
@@ -420,9 +431,9 @@ __device__ __forceinline__ void forward_sweep(const TransTab<Q, TREG> &T, const 
 #pragma unroll 1
   for (int i = 1; i <= L; i++) {
     asm volatile("" ::: "memory");   // keep LDS table reads inside the row (no hoisting into VGPRs)
-    const int x = seq[i - 1];
+    const int x = DRAIN ? __builtin_amdgcn_readfirstlane((int)seq[i - 1]) : seq[i - 1];
     float od[Q];
-    load_em_fwd<Q>(od, emL, emG, x, K, lane);
+    load_em_fwd<Q, DRAIN>(od, emL, emG, x, K, lane);
     const float mm1 = wave_shr1(Mp[Q - 1]), im1 = wave_shr1(Ip[Q - 1]), dm1 = wave_shr1(Dp[Q - 1]);
 #pragma unroll
     for (int q4 = Q / 4 - 1; q4 >= 0; q4--) {

@@ -78,9 +78,25 @@ constexpr bool kMaskedAcc = true;   // P4: only lanes that own a stored Forward 
 #ifndef WH_SPLIT_SLACK
 #define WH_SPLIT_SLACK 1
 #endif
+// WH_ROW_WAITS (bits; the default object: 3; 0 = the parent's code, what the A/B slot keeps): what a row of the LDS sweeps waits
+// for on vmcnt, the one counter of loads AND stores.  1: the L2 fallback of a degenerate residue code completes inside its own
+// branch (wait_vmcnt0, wh_device.h) - in the Forward sweeps, which also take the residue code wave-uniform, and in both window
+// sweeps - so that the common path holds no wait for it: the stored Forward sweep no longer begins a row by waiting for the
+// stores of the row before.  2: the envelope window sweep requests row i - 1 right AFTER it has consumed row i's cells, into the
+// same registers: at the consumer the only load in flight is the one it needs, issued almost a row earlier (requested at the
+// row's top inside `if (have_n)`, the younger request could not be counted on and the consumer waited for it too).  One register
+// set, one row per trip: the two-row rotation of WH_ROW_PAIRS & 1 is not needed then, and the 512-node window at 768 threads,
+// which had no room for a second set, loses its copy of the requested cells as well.
+// Every LDS instantiation of the default object takes both (all 24 caps of tests/test_kernel_resources.py hold, none rose).  The
+// long-query sweeps (SG: special states in HBM, their kernels' frames at their caps) keep the parent's form, like the objects that
+// compile this file for its sweeps (WH_SWEEPS_ONLY) and the A/B slot.  tests/test_sweep_row_waits_isa.py reads the compiled loops.
+#ifndef WH_ROW_WAITS
+#define WH_ROW_WAITS (WH_K7_NEW_DEFAULT ? 3 : 0)
+#endif
 constexpr int kLayout = WH_SPEC_ROWS ? SPEC_ROWS : SPEC_SOA;
 constexpr bool kUni = WH_UNI != 0;
 constexpr bool kRowPairs = ((WH_ROW_PAIRS) & 1) != 0, kUniArgs = ((WH_ROW_PAIRS) & 2) != 0, kSplitSlack = WH_SPLIT_SLACK != 0;
+constexpr bool kDrain = ((WH_ROW_WAITS) & 1) != 0, kLateRequest = ((WH_ROW_WAITS) & 2) != 0;
 static_assert(kLayout == SPEC_SOA || kSlim, "a row record has six words (WH_SLIM_SPEC)");
 template <bool SG> using SpecOf = SpecAt<SG ? (int)SPEC_SOA : kLayout>;
 constexpr int kSpecTag = kSpArr | (kLayout << 8);      // what ScoreArgs::spec_arrays must say for this object
@@ -170,9 +186,10 @@ __device__ __noinline__ FwdOut sweep_forward(const WaveCtx c_, lds_u8 *seq3, int
   constexpr bool UM = !STORE && !SG && Q >= 8;
   if (STORE && kUni && !SG) touch_len_config(cfg);
   o.nst = 0;
-  forward_sweep<Q, false, STORE, (Q <= kMaxQP), kSlim, UM, STORE, !SG, (STORE && kUni && !SG), (SG ? (int)SPEC_SOA : kLayout)>(T, sc, (const float *)c.emL, (const float *)c.emG, ctxKlds(c), seq, L, cfg, SG ? (float *)c.specg : (float *)c.spec, c.SP, (float *)c.Fs, keep_scale, c.lane, o.xC, o.ef,
+  forward_sweep<Q, false, STORE, (Q <= kMaxQP), kSlim, UM, STORE, !SG, (STORE && kUni && !SG), (SG ? (int)SPEC_SOA : kLayout), (kDrain && !SG)>(T, sc, (const float *)c.emL, (const float *)c.emG, ctxKlds(c), seq, L, cfg, SG ? (float *)c.specg : (float *)c.spec, c.SP, (float *)c.Fs, keep_scale, c.lane, o.xC, o.ef,
                                                                   reinterpret_cast<unsigned *>((float *)c.n2tab) + kUmSlot, &o.nst, keep_lanes);
   if (SG) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the rows were written by lane 0, every lane reads them next
+  if (STORE && kDrain && !SG) wait_vmcnt0();   // no row waits for the stores of the row before: the sweep does, once, for all of them - P4 reads the rows
   return o;
 }
 
@@ -379,7 +396,7 @@ __device__ __noinline__ P4Out sweep_backward_null2(const WaveCtx c, lds_u8 *eseq
   float mine = 1.0f;
   for (int x = 0; x < ctxK(c); x++) {
     float od[Q];
-    load_em_rev<Q>(od, emL, (const float *)c.emG, x, ctxKlds(c), lane);
+    load_em_rev<Q, (kDrain && !SG)>(od, emL, (const float *)c.emG, x, ctxKlds(c), lane);
     float s = 0.f;
 #pragma unroll
     for (int p = 0; p < Q; p++) s = fmaf(fM[p], od[p], s);
@@ -488,12 +505,20 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 
     }
   };
   request_row(Ld, true, fm_a, fi_a, have_a);
+  // kLate (WH_ROW_WAITS & 2): row i reads the mask word of row i - 1 where it begins, beside record i - 1, and issues the loads
+  // right after it has consumed its own cells, into the registers those cells leave.  The consumer's wait (vmcnt(0), the loads
+  // sit inside `if (have)`) then covers one request, issued a row's arithmetic earlier less the consumer itself; issued at the
+  // row's top it also covered the request of the same row, half a row old.  Not for long queries (as kPairs).
+  constexpr bool kLate = kLateRequest && !SG;
   // CARRY: the words of record i - 1 are loaded together where row i begins - beside its mask word, which the row request
   // reads there anyway - and its scale exponent is row i - 1's own one iteration later: one LDS round trip per row, not six
   int S_row = CARRY ? ldi(at(SP_S, Ld)) : 0;
   // row i: its stored Forward cells are in <fm_c, fi_c, have>; row i - 1 is requested into <fm_n, fi_n, have_n>
   auto row = [&](int i, const float4 (&fm_c)[B4], const float4 (&fi_c)[B4], bool have, float4 (&fm_n)[B4], float4 (&fi_n)[B4], bool &have_n) {
-    if (i > 1) request_row(i - 1, false, fm_n, fi_n, have_n);
+    bool have_l = false;
+    if (kLate) {
+      if (i > 1) have_l = ((lanef < 32 ? ldu(at(kSpML, i - 1)) : ldu(at(kSpMH, i - 1))) >> (lanef & 31)) & 1u;
+    } else if (i > 1) request_row(i - 1, false, fm_n, fi_n, have_n);
     int S_p = 0;
     float N_p = 0.f, J_p = 0.f, C_p = 0.f;
     if (CARRY) {
@@ -519,7 +544,10 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 
         }
       };
       if (x < Klds) emit([&](int p4) { return em4L[x * (Q * 16) + fwd[p4]]; });
-      else emit([&](int p4) { return em4G[(size_t)x * (Q * 16) + fwd[p4]]; });
+      else {
+        emit([&](int p4) { return em4G[(size_t)x * (Q * 16) + fwd[p4]]; });
+        if (kDrain && !SG) wait_vmcnt0();
+      }
       xB = wave_sum(part);
       if (!UNI) xJ = fmaf(xJ, cu.loop, xB * cu.move);
       xC = xC * cu.loop;
@@ -545,6 +573,14 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 
       }
       fIs = fmaf(idot, s_i, fIs);
     }
+    if (kLate) {
+      have_n = have_l;
+      if (have_l) {
+        const float4 *rown = reinterpret_cast<const float4 *>((const float *)c.Fs) + (size_t)(i - 1) * (2 * Q4 * kWave);
+#pragma unroll
+        for (int p4 = 0; p4 < B4; p4++) { fm_n[p4] = nt_load4(rown + frow[p4]); fi_n[p4] = nt_load4(rown + Q4 + frow[p4]); }
+      }
+    }
     float nj = (CARRY ? N_p : SG ? R.f(4, i) : ldf(at(SP_N, i, 1))) * xN;
     if (!UNI) nj = fmaf(CARRY ? J_p : SG ? R.f(5, i) : ldf(at(SP_J, i, 1)), xJ, nj);
     nj = fmaf(CARRY ? C_p : SG ? R.f(6, i) : ldf(at(SP_C, i, 1)), xC, nj);
@@ -552,7 +588,13 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 
     if (CARRY) S_row = S_p;
     xfac = fmaf(nj * cu.loop, s_p, xfac);
   };
-  if (kPairs) {
+  if (kLate) {
+#pragma unroll 1
+    for (int i = Ld; i >= 1; i--) {
+      asm volatile("" ::: "memory");
+      row(i, fm_a, fi_a, have_a, fm_a, fi_a, have_a);      // (one set: the request follows the consumer)
+    }
+  } else if (kPairs) {
     int i = Ld;
 #pragma unroll 1
     for (; i >= 2; i -= 2) {
@@ -928,7 +970,10 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c_, lds_u
         }
       };
       if (x < Klds) emit([&](int p4) { return em4L[x * (Q * 16) + fwd[p4]]; });
-      else emit([&](int p4) { return em4G[(size_t)x * (Q * 16) + fwd[p4]]; });
+      else {
+        emit([&](int p4) { return em4G[(size_t)x * (Q * 16) + fwd[p4]]; });
+        if (kDrain) wait_vmcnt0();
+      }
       xB = wave_sum(part);
       xJ = fmaf(xJ, cm.loop, xB * cm.move);
       xC = xC * cm.loop;
