@@ -18,6 +18,8 @@
  *   wh_domains*    <- hmmsearch's "Domain annotation for each sequence" section and its --domtblout file; NO reference
  *                     code reads either (evalHMMSearchOutput parses the per-sequence table only): they are here for the
  *                     users of the hmmsearch program the library replaces
+ *   wh_hits_msa*   <- "hmmsearch -A FILE": the alignment of all domains that satisfy the inclusion thresholds (HMMER's
+ *                     p7_tophits_Alignment); no reference code asks for it either
  *
  * Conventions: plain pointers and sizes; the caller owns every input and output
  * buffer; the library owns wh_ehmm handles and its device workspace.  Functions
@@ -425,7 +427,8 @@ int wh_consensus_dev(wh_ehmm *e, const int64_t *d_offsets, int64_t nq, int32_t m
  * 4 multidomain resolver (the second part of wh_score: stage time of scoring = 0 + 4), 5 the domain stage (wh_domains: its
  * gather and summary kernels and the alignment launches between them; which = 2 then holds the alignment launches alone),
  * 6 the alignment assembly (wh_msa_dev: widths, layout, render and PP_cons kernels, and the host's one wait between them),
- * 7 the --mapali mapping (wh_msa_mapali_dev: count and map kernels, and the host's one wait between them). */
+ * 7 the --mapali mapping (wh_msa_mapali_dev: count and map kernels, and the host's one wait between them),
+ * 8 the hit selection of hmmsearch -A (wh_hits_msa_dev: mark, scan, place and slice kernels, and the host's one wait between them). */
 int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches);
 /* Timing mode only: the scoring launches of the last wh_score[_dev] call, in launch order - the cells-per-lane class of the
  * launch's models (16 = models of 961..1024 nodes ...), the kernel family (0 phase-call wh::k7::score_kernel7, 1
@@ -487,6 +490,10 @@ int wh_merge_sharded(int device, const uint8_t *q_text, const int64_t *q_off, in
  * kernels; (2): the alignment launches of wh_msa. */
 #define WH_MSA_TRIM   1
 #define WH_MSA_NO_LDS 2   /* test hook: the rows are rendered in global memory whatever the width */
+#define WH_MSA_CONS_HMMER 4   /* wh_msa_dev only: PP_cons in HMMER's own arithmetic - the float posteriors summed in a double
+                               * in row order, divided by (float) n, the quotient rounded to float and encoded as (int)(p * 10.0 +
+                               * 0.5).  wh_hits_msa_dev sets it (the arithmetic reproduces the binary's -A files); wh_msa's
+                               * float32 sums stay as they are */
 int wh_msa(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, const uint8_t *text, int64_t nq, int32_t h,
            int32_t flags, int64_t *out_W, uint8_t **out_rows, uint8_t **out_pp_rows, uint8_t **out_pp_cons, uint8_t **out_rf,
            int32_t **out_matmap, int64_t *out_pathless);
@@ -525,6 +532,59 @@ int wh_msa_mapali_dev(wh_ehmm *e, const int32_t *d_cols, const float *d_pp, cons
 int wh_alignment_checksum(const char *molecule, const char *rows, int32_t nseq, int64_t alen, uint32_t *out_cksum);
 /* The CKSUM line of model h: *present = 0 where the file has none. */
 int wh_ehmm_cksum(const wh_ehmm *e, int h, uint32_t *cksum, int32_t *present);
+
+/* ---- hmmsearch -A FILE: the alignment of all hits that satisfy the inclusion thresholds ---------------------------------
+ * wh_domain_paths[_dev] replaces nothing of its own: it is wh_domains[_dev] - the same steps through the same code, the
+ * records bit for bit - that also hands back what it computes on the way, the alignment of every envelope: env_off
+ * [ndom + 1], the CSR of the envelopes in record order, and per envelope residue its 0-based node (-1: none) and the float32
+ * posterior of its state (wh_align_pp's values).
+ *  - _dev: *d_env_off, *d_cols, *d_pp point into the handle's workspace on the device and stay valid until the next
+ *    wh_domains*, wh_domain_paths* or wh_hits_msa call on the handle; *total_env = env_off[ndom].  Waits as wh_domains_dev.
+ *  - host: env_off is the caller's [ndom + 1]; *out_cols and *out_pp are malloc'ed (release with wh_free_text; NULL where
+ *    there is no domain).
+ * wh_hits_msa[_dev] replaces HMMER 3.1b2's p7_tophits_Alignment behind `hmmsearch -A`: every domain of model h that passes
+ * the inclusion thresholds becomes one row of hmmalign's alignment (wh_msa's layout and outputs).  A domain is included where
+ * its pair is WH_FLAG_REPORTED, it has a path (ali_i != 0), the sequence's E-value exp(lnP_seq) Z <= incE with lnP_seq =
+ * min(0, -lambda (seq_score - tau)) in double from the float32 fields, and its own conditional E-value exp(lnP) domZ <=
+ * incdomE; both are decided as lnP <= ln(threshold / Z), the logarithms taken once on the host (a model without a STATS
+ * line has no E-values: every reported sequence and every domain with a path is included, as in the level-0 tables).  Pairs of
+ * other models than h are ignored.  Rows: the queries in order[0..nq-1] (a permutation of 0..nq-1; NULL: query order), the
+ * domains of a query in domain order.  A row is the residues ali_i..ali_j of the sequence (text: the characters as given)
+ * with the domain's own path on that range - no re-alignment - and with posteriors as HMMER keeps them for such a row: the
+ * displayed PP character decoded again ('*' where p + 0.05 >= 1.0 -> 1.0, else d = (int)(p * 10.0 + 0.5) -> (float)d / 10), so
+ * the "#=GR PP" rows are the characters of the real posteriors and "#=GC PP_cons" is the character of the mean of the decoded
+ * tenths, in HMMER's own arithmetic (WH_MSA_CONS_HMMER).
+ * Outputs: *out_nrows and rows_rec[*out_nrows] (malloc'ed, wh_free_text: per row the query, the domain's index within its
+ * pair, ali_i, ali_j - the caller forms the name "name/ali_i-ali_j" from them), then wh_msa's W, rows, pp_rows, pp_cons, rf,
+ * matmap.  No included domain: WH_OK, 0 rows, W = M.  msa_flags: 0 or WH_MSA_NO_LDS.
+ * WH_EINVAL, wh_last_error naming the entry point: NULL handle, h out of range, opts NULL or Z <= 0 or domZ <= 0 or a
+ * negative or NaN threshold, records that do not fit dom_off / their envelopes / their queries, an order[] that names a query
+ * outside 0..nq-1 or yields more rows than there are domains (a query named twice: the caller's error, never a write out of
+ * bounds).
+ * wh_hits_msa_dev is the stage alone, on device arrays (it reads dom_off's last entry back, then the row and residue totals -
+ * two waits before wh_msa_dev's own).  wh_hits_msa takes host pointers and runs wh_domain_paths_dev then wh_hits_msa_dev;
+ * out_dom (optional, [dom_off[nq x H]]) receives the wh_domain records, so that a caller who wants the domain tables and the
+ * alignment pays for one alignment of the envelopes.  wh_last_kernel_ms(8): the mark, scan, place and slice kernels with the
+ * host's wait between them; (6): the assembly; (5): the domain stage of wh_hits_msa. */
+typedef struct wh_hits_opts { double Z, domZ, incE, incdomE; } wh_hits_opts;
+typedef struct wh_hit_row { int32_t query, index, ali_i, ali_j; } wh_hit_row;
+int wh_domain_paths(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const uint8_t *flags,
+                    const wh_pair_detail *detail, const int64_t *dom_off, wh_domain *out, int64_t *env_off,
+                    int32_t **out_cols, float **out_pp);
+int wh_domain_paths_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
+                        int32_t max_len, const uint8_t *d_flags, const wh_pair_detail *d_detail, const int64_t *d_dom_off,
+                        wh_domain *d_out, const int64_t **d_env_off, const int32_t **d_cols, const float **d_pp,
+                        int64_t *total_env, void *stream);
+int wh_hits_msa(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, const uint8_t *text, int64_t nq,
+                const uint8_t *flags, const wh_pair_detail *detail, const int64_t *dom_off, int32_t h, const int32_t *order,
+                const wh_hits_opts *opts, int32_t msa_flags, wh_domain *out_dom, int64_t *out_nrows, wh_hit_row **out_rows_rec,
+                int64_t *out_W, uint8_t **out_rows, uint8_t **out_pp_rows, uint8_t **out_pp_cons, uint8_t **out_rf,
+                int32_t **out_matmap);
+int wh_hits_msa_dev(wh_ehmm *e, const uint8_t *d_text, const int64_t *d_offsets, int64_t nq, const uint8_t *d_flags,
+                    const wh_pair_detail *d_detail, const int64_t *d_dom_off, const wh_domain *d_dom, const int64_t *d_env_off,
+                    const int32_t *d_cols, const float *d_pp, int32_t h, const int32_t *d_order, const wh_hits_opts *opts,
+                    int32_t msa_flags, int64_t *out_nrows, wh_hit_row **out_rows_rec, int64_t *out_W, uint8_t **out_rows,
+                    uint8_t **out_pp_rows, uint8_t **out_pp_cons, uint8_t **out_rf, int32_t **out_matmap, void *stream);
 
 /* ---- eHMM construction (host code, no GPU needed) -------------------------------
  * Replaces the reference's per-subset call

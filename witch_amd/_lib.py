@@ -21,7 +21,7 @@ VIT_NOT_RUN, VIT_OVERFLOW, MSV_OVERFLOW = -32769, 32768, -1
 ALPH_DNA, ALPH_RNA, ALPH_AMINO = 0, 1, 2
 WH_OK, WH_EINVAL, WH_EIO, WH_ENODEV, WH_EHIP, WH_ERANGE, WH_ENOMEM = 0, -1, -2, -3, -4, -5, -6      # include/witch_hip.h
 WH_BUILD_STATS, WH_BUILD_CALIB_NO_LDS = 1, 4
-WH_MSA_TRIM, WH_MSA_NO_LDS = 1, 2
+WH_MSA_TRIM, WH_MSA_NO_LDS, WH_MSA_CONS_HMMER = 1, 2, 4
 PATH_P2_WIN, PATH_P2_FULL, PATH_P4_W256, PATH_P4_W512, PATH_P4_WFAIL, PATH_P4_FULL, PATH_DENSE, PATH_MULTI = 1, 2, 4, 8, 16, 32, 64, 128
 
 
@@ -52,6 +52,12 @@ class FilterOpts(C.Structure):
     _fields_ = [("F1", C.c_double), ("F2", C.c_double), ("F3", C.c_double), ("nobias", C.c_int32)]
 
 
+class HitsOpts(C.Structure):
+    """wh_hits_opts (include/witch_hip.h): the search space sizes and inclusion thresholds of hmmsearch -A."""
+    _fields_ = [("Z", C.c_double), ("domZ", C.c_double), ("incE", C.c_double), ("incdomE", C.c_double)]
+
+
+HIT_ROW_FIELDS = [("query", "<i4"), ("index", "<i4"), ("ali_i", "<i4"), ("ali_j", "<i4")]      # wh_hit_row
 DOMAIN_FIELDS = [("pair", "<i8"), ("index", "<i4"), ("of", "<i4"), ("env_i", "<i4"), ("env_j", "<i4"), ("ali_i", "<i4"),
                  ("ali_j", "<i4"), ("hmm_i", "<i4"), ("hmm_j", "<i4"), ("bits", "<f4"), ("bias_bits", "<f4"), ("oasc", "<f4"),
                  ("lnP", "<f4")]
@@ -108,6 +114,13 @@ SYMBOLS = {
     "wh_domain_counts_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
     "wh_domains": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "wh_domains_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
+    "wh_domain_paths": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "wh_domain_paths_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P] + [C.POINTER(C.c_void_p)] * 3 +
+                            [C.POINTER(C.c_int64), _P]),
+    "wh_hits_msa": (C.c_int, [_P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, _P, C.POINTER(C.c_int64),
+                              C.POINTER(C.c_void_p), C.POINTER(C.c_int64)] + [C.POINTER(C.c_void_p)] * 5),
+    "wh_hits_msa_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64)] + [C.POINTER(C.c_void_p)] * 5 + [_P]),
     "wh_filter": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "wh_filter_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "wh_filter_host": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),

@@ -1,6 +1,6 @@
 // Internal header of the host side of libwitch_hip.so: what wh_api.hip (handles, options, getters, host-pointer entry
 // points), wh_host_score.hip (wh_score_dev), wh_host_resolve.hip (its resolver stage), wh_host_align.hip (wh_align_dev),
-// wh_host_domains.hip (wh_domains_dev), wh_host_msa.hip (wh_msa_dev) and wh_host_filter.hip (the filters) share: the handle, the d_counter slots, the
+// wh_host_domains.hip (wh_domains_dev), wh_host_msa.hip (wh_msa_dev), wh_host_hits.hip (wh_hits_msa_dev) and wh_host_filter.hip (the filters) share: the handle, the d_counter slots, the
 // staging of the host-pointer entry points.  No kernel file includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -106,6 +106,7 @@ struct wh_ehmm {
   // wh_msa: the alignment's columns, posteriors and pair lists
   DevBuf d_msa_lay, d_msa_res, d_msa_gc, d_msa_rows, d_msa_pprows, d_msa_ppm, d_msa_cols, d_msa_pp;
   DevBuf d_map_rows, d_map_code, d_map_cnt, d_map_off, d_map_alloff, d_map_cols, d_map_text;     // wh_msa_mapali[_dev]
+  DevBuf d_hits_work, d_hits_text, d_hits_cols, d_hits_pp, d_hits_dom;     // wh_hits_msa[_dev]: scan workspace and row records, the sliced batch, wh_hits_msa's domain records
   int64_t rq_cap = 0;                       // records the queue of the current scoring call holds
   double rq_rate = 0.0;                     // largest share of queued pairs any call on this handle has seen (sizes the next queue)
   int64_t rq_floor = 0;                     // ... at least this many (set when a call overflowed its estimate; the call then runs again)
@@ -132,7 +133,7 @@ struct wh_ehmm {
   struct FilterStateDelete { void operator()(FilterState *f) const; };
   std::unique_ptr<FilterState, FilterStateDelete> filter;
   bool timing = false;
-  KernelTimer timers[8];                    // wh_last_kernel_ms: 0 scoring, 1 topk, 2 align, 3 consensus, 4 resolver, 5 domain stage, 6 alignment assembly (wh_msa_dev), 7 --mapali mapping (wh_msa_mapali_dev)
+  KernelTimer timers[9];                    // wh_last_kernel_ms: 0 scoring, 1 topk, 2 align, 3 consensus, 4 resolver, 5 domain stage, 6 alignment assembly (wh_msa_dev), 7 --mapali mapping (wh_msa_mapali_dev), 8 hit selection (wh_hits_msa_dev)
   int max_M = 0;
   int max_Q = 4;                              // largest cells-per-lane of any model (sizes the float64 slabs)
   int last_align_redo = 0;          // pairs of the last wh_align call that went through the log-space pass

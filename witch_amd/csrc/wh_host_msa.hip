@@ -47,7 +47,8 @@ int msa_assemble(const char *who, wh_ehmm *e, const int32_t *d_cols, const float
   HIPCHK(hipSetDevice(e->device));
   // d_msa_lay: width [M + 1] | matmap [M] | cons_cnt [M] | pathless [1] (ints), then layout [M + 2] (8-byte aligned), cons_sum [M]
   const size_t n_int = (size_t)3 * M + 2, lay_at = (n_int * sizeof(int32_t) + 7) & ~(size_t)7;
-  const size_t lay_bytes = lay_at + sizeof(long long) * ((size_t)M + 2) + sizeof(float) * (size_t)M;
+  const size_t sum64_at = (lay_at + sizeof(long long) * ((size_t)M + 2) + sizeof(float) * (size_t)M + 7) & ~(size_t)7;     // (WH_MSA_CONS_HMMER)
+  const size_t lay_bytes = (flags & WH_MSA_CONS_HMMER) ? sum64_at + sizeof(double) * (size_t)M : lay_at + sizeof(long long) * ((size_t)M + 2) + sizeof(float) * (size_t)M;
   const size_t wmax = (size_t)M + (size_t)total_residues;          // no alignment is wider
   if (e->d_msa_lay.ensure(lay_bytes) || e->d_msa_res.ensure(2 * sizeof(int32_t) * (size_t)total_residues + 16) || e->d_msa_gc.ensure(2 * (wmax + 16)))
     return WH_ENOMEM;
@@ -58,6 +59,7 @@ int msa_assemble(const char *who, wh_ehmm *e, const int32_t *d_cols, const float
   a.cols = d_cols; a.pp = d_pp; a.text = d_text; a.off = d_offsets; a.nq = nq; a.total = total_residues; a.n_nopp = n_nopp; a.pp_shift = pp_shift; a.M = M; a.trim = (flags & WH_MSA_TRIM) ? 1 : 0;
   a.width = (int32_t *)e->d_msa_lay.p; a.matmap = a.width + (M + 1); a.cons_cnt = a.matmap + M; a.pathless = a.cons_cnt + M;
   a.layout = (long long *)((char *)e->d_msa_lay.p + lay_at); a.cons_sum = (float *)(a.layout + (M + 2));
+  if (flags & WH_MSA_CONS_HMMER) a.cons_sum64 = (double *)((char *)e->d_msa_lay.p + sum64_at);
   a.res_blk = (int32_t *)e->d_msa_res.p; a.res_k = a.res_blk + total_residues;
   a.rf = (uint8_t *)e->d_msa_gc.p; a.pp_cons = a.rf + ((wmax + 15) & ~(size_t)15);
   hipError_t err = launch_msa_widths(a, s);
@@ -129,7 +131,7 @@ int wh_msa_dev(wh_ehmm *e, const int32_t *d_cols, const float *d_pp, const uint8
   if (!e) { set_error("wh_msa_dev: null handle"); return WH_EINVAL; }
   if (h < 0 || h >= (int)e->hmms.size()) { set_error("wh_msa_dev: model position %d out of range (0..%d)", h, (int)e->hmms.size() - 1); return WH_EINVAL; }
   if (nq < 0 || total_residues < 0 || !out_W || !out_rows || !out_pp_rows || !out_pp_cons || !out_rf || !out_matmap || !out_pathless ||
-      (nq > 0 && !d_offsets) || (total_residues > 0 && (!d_cols || !d_pp || !d_text)) || (flags & ~(WH_MSA_TRIM | WH_MSA_NO_LDS))) {
+      (nq > 0 && !d_offsets) || (total_residues > 0 && (!d_cols || !d_pp || !d_text)) || (flags & ~(WH_MSA_TRIM | WH_MSA_NO_LDS | WH_MSA_CONS_HMMER))) {
     set_error("wh_msa_dev: bad argument");
     return WH_EINVAL;
   }

@@ -407,6 +407,7 @@ struct MsaArgs {
   int64_t q0, q1;              // ... the chunk
   float *cons_sum;             // [M] running float32 sums, in sequence order ...
   int32_t *cons_cnt;           // [M] ... and counts over the chunks so far
+  double *cons_sum64;          // WH_MSA_CONS_HMMER: [M] the sums as doubles, HMMER's PP_cons arithmetic (else NULL)
   int32_t last;                // the chunk ends the file: PP_cons is written
 };
 hipError_t launch_msa_widths(const MsaArgs &a, hipStream_t s);
@@ -432,6 +433,44 @@ struct MapaliArgs {
 hipError_t launch_mapali_count(const MapaliArgs &a, hipStream_t s);
 hipError_t launch_mapali_map(const MapaliArgs &a, hipStream_t s);
 constexpr size_t kMsaLdsBudget = 64 * 1024;   // the two rows of a sequence in LDS: up to 32 K columns, two workgroups per CU stay resident
+
+// wh_hits_msa_dev (wh_hits.hip): the included domains of model h as the sequences of an alignment.  <npairs> = nq x H; the
+// domain records, the envelope CSR and the per-residue columns / posteriors are wh_domain_paths_dev's.
+struct HitsArgs {
+  const uint8_t *flags;        // [npairs]
+  const wh_pair_detail *detail;
+  const int64_t *dom_off;      // [npairs + 1]
+  const wh_domain *dom;        // [ndom]
+  int64_t npairs, ndom, nq;
+  int H, h;
+  const int64_t *env_off;      // [ndom + 1]
+  const int32_t *cols;         // per envelope residue: 0-based node or -1 ...
+  const float *pp;             // ... and the posterior of its state
+  const uint8_t *text;         // the sequences' characters as given ...
+  const int64_t *offsets;      // ... [nq + 1]
+  const int32_t *order;        // [nq] the queries in output order, or NULL: query order
+  float tau, lambda;           // model h's Forward E-value parameters (NaN: no STATS line)
+  double ln_inc_seq, ln_inc_dom;   // ln(incE / Z), ln(incdomE / domZ)
+  int32_t *len;                // mark kernel: [ndom] residues ali_i..ali_j of an included domain, 0: not included
+  int *bad;                    // ... set when a record does not fit dom_off, its envelope or its query, or order[] leaves 0..nq-1
+  int64_t nblk;                // workgroups of the scan
+  int32_t *pos_row;            // scan: [nq] per output position the rows in front of it inside its workgroup ...
+  long long *pos_res;          // ... and their residues
+  long long *blk_row, *blk_res;   // [nblk] the workgroups' sums, then their exclusive scan
+  long long *totals;           // [2] rows, residues
+  int64_t nrows, nres;         // ... as the host read them back
+  int64_t *row_dom;            // place kernel: [nrows] the row's domain ...
+  int64_t *row_off;            // ... [nrows + 1] the CSR of the batch ...
+  wh_hit_row *row_rec;         // ... and the record the caller names the row from
+  uint8_t *out_text;           // slice kernel: the batch wh_msa_dev assembles
+  int32_t *out_cols;
+  float *out_pp;
+};
+hipError_t launch_hits_mark(const HitsArgs &a, hipStream_t s);
+hipError_t launch_hits_scan(const HitsArgs &a, hipStream_t s);
+hipError_t launch_hits_place(const HitsArgs &a, hipStream_t s);
+hipError_t launch_hits_slice(const HitsArgs &a, hipStream_t s);
+int64_t hits_scan_blocks(int64_t nq);
 
 struct TopkArgs {
   const int32_t *decibits;

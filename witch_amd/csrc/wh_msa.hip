@@ -161,9 +161,33 @@ __global__ __launch_bounds__(kMsaRenderThreads) void msa_render_kernel(MsaArgs a
   }
 }
 
+// HMMER's own arithmetic for PP_cons (p7_tracealign.c: the rows' float posteriors summed in a double, divided by (float) n,
+// the quotient handed to p7_alidisplay_EncodePostProb(float)): WH_MSA_CONS_HMMER, which the alignment of hmmsearch -A sets
+__device__ __forceinline__ uint8_t msa_pp_char_hmmer(float p) {
+  const double v = (double)p;
+  if (v + 0.05 >= 1.0) return '*';
+  int d = (int)(v * 10.0 + 0.5);
+  d = d < 0 ? 0 : d > 9 ? 9 : d;
+  return (uint8_t)('0' + d);
+}
+
 __global__ __launch_bounds__(64) void msa_cons_kernel(MsaArgs a) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= a.M) return;
+  if (a.cons_sum64) {
+    double s = a.cons_sum64[k];
+    int n = a.cons_cnt[k];
+    const float *col = a.ppm + k;
+    const int64_t rows = a.q1 - a.q0;
+    for (int64_t q = 0; q < rows; q++) {
+      const float v = col[(size_t)q * (size_t)a.M];
+      if (v > -0.5f) { s += (double)v; n++; }
+    }
+    a.cons_sum64[k] = s;
+    a.cons_cnt[k] = n;
+    if (a.last) a.pp_cons[a.matmap[k]] = n ? msa_pp_char_hmmer((float)(s / (double)(float)n)) : '.';
+    return;
+  }
   float s = a.cons_sum[k];
   int n = a.cons_cnt[k];
   const float *col = a.ppm + k;

@@ -408,6 +408,105 @@ class EHMM:
                                    C.addressof(detail), dom_off.ctypes.data, out.ctypes.data), "wh_domains")
         return (out, dom_off, unl) if want_unlisted else (out, dom_off)
 
+    def domain_paths(self, residues, offsets, flags, detail):
+        """domains() that also returns the alignment of every envelope (include/witch_hip.h: wh_domain_paths): (records,
+        dom_off, env_off int64 [n + 1], cols int32, pp float32) - env_off is the CSR of the envelopes in record order, cols
+        the 0-based node (-1: none) and pp the posterior of every envelope residue.  The records are domains()' bit for bit."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        nq = len(offsets) - 1
+        counts, _ = self.domain_counts(flags, detail)
+        dom_off = np.zeros(nq * self.H + 1, dtype=np.int64)
+        np.cumsum(counts.reshape(-1), out=dom_off[1:])
+        n = int(dom_off[-1])
+        out = np.zeros(n, dtype=np.dtype(DOMAIN_FIELDS))
+        env_off = np.zeros(n + 1, dtype=np.int64)
+        pc, pp = C.c_void_p(None), C.c_void_p(None)
+        if nq:
+            check(lib().wh_domain_paths(self._h, residues.ctypes.data, offsets.ctypes.data, nq, flags.ctypes.data,
+                                        C.addressof(detail), dom_off.ctypes.data, out.ctypes.data, env_off.ctypes.data,
+                                        C.byref(pc), C.byref(pp)), "wh_domain_paths")
+        total = int(env_off[-1])
+        cols = self._take(pc, total, np.int32)
+        post = self._take(pp, total, np.float32)
+        return out, dom_off, env_off, cols, post
+
+    @staticmethod
+    def _take(ptr, n, dt):
+        """A malloc'ed buffer of the library as a numpy array (copied; the buffer is released)."""
+        nbytes = n * np.dtype(dt).itemsize
+        out = np.frombuffer((C.c_char * nbytes).from_address(ptr.value), dtype=dt).copy() if nbytes and ptr.value else np.zeros(0, dtype=dt)
+        if ptr.value:
+            lib().wh_free_text(ptr)
+        return out
+
+    @staticmethod
+    def hits_opts(Z, domZ, incE=0.01, incdomE=0.01) -> _lib.HitsOpts:
+        return _lib.HitsOpts(float(Z), float(domZ), float(incE), float(incdomE))
+
+    def _hits_collect(self, h, nrows, recs, W, ptrs):
+        n = int(nrows.value)
+        rec = self._take(recs, n * 4, np.int32).view(np.dtype(_lib.HIT_ROW_FIELDS)) if n else np.zeros(0, dtype=np.dtype(_lib.HIT_ROW_FIELDS))
+        m = self._msa_collect(n, h, W, C.c_int64(0), ptrs)
+        del m["pathless"]
+        m["row_recs"] = rec
+        return m
+
+    def hits_msa(self, residues, offsets, text, flags, detail, Z, domZ, incE=0.01, incdomE=0.01, h=0, order=None, no_lds=False,
+                 want_domains=False):
+        """hmmsearch -A: hmmalign's alignment of every domain of model h that satisfies the inclusion thresholds
+        (include/witch_hip.h: wh_hits_msa) - the envelopes are aligned (wh_domain_paths_dev), the included domains chosen,
+        ordered, sliced to ali_i..ali_j and assembled on the device.  flags, detail: what score(want_detail=True) returned;
+        text: the sequences' characters as given; order: the queries in output order (None: query order).  Returns msa()'s
+        dict without "pathless" and with "row_recs": a structured array (query, index, ali_i, ali_j) per row.  want_domains:
+        also "domains" and "dom_off", what domains() returns - from the same alignment of the envelopes."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        if isinstance(text, str):
+            text = text.encode()
+        text = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8)
+        nq = len(offsets) - 1
+        if len(text) != len(residues) or (nq and int(offsets[-1]) != len(residues)):
+            raise ValueError("hits_msa: residues, text and offsets disagree")
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.int32)
+            if len(order) != nq:
+                raise ValueError("hits_msa: order must name every query once")
+        counts, _ = self.domain_counts(flags, detail)
+        dom_off = np.zeros(nq * self.H + 1, dtype=np.int64)
+        np.cumsum(counts.reshape(-1), out=dom_off[1:])
+        dom = np.zeros(int(dom_off[-1]), dtype=np.dtype(DOMAIN_FIELDS))
+        o = self.hits_opts(Z, domZ, incE, incdomE)
+        W, _, ptrs = self._msa_outputs()
+        nrows, recs = C.c_int64(0), C.c_void_p(None)
+        check(lib().wh_hits_msa(self._h, residues.ctypes.data, offsets.ctypes.data, text.ctypes.data, nq, flags.ctypes.data,
+                                C.addressof(detail) if nq else None, dom_off.ctypes.data, int(h), None if order is None else order.ctypes.data,
+                                C.byref(o), _lib.WH_MSA_NO_LDS if no_lds else 0, dom.ctypes.data if len(dom) else None,
+                                C.byref(nrows), C.byref(recs), C.byref(W), *[C.byref(p) for p in ptrs]), "wh_hits_msa")
+        m = self._hits_collect(int(h), nrows, recs, W, ptrs)
+        if want_domains:
+            m["domains"], m["dom_off"] = dom, dom_off
+        return m
+
+    def hits_msa_t(self, text_t, offsets_t, flags_t, detail_t, dom_off_t, dom_t, env_off_t, cols_t, pp_t, Z, domZ, incE=0.01,
+                   incdomE=0.01, h=0, order_t=None, no_lds=False):
+        """The hit selection and the assembly alone (wh_hits_msa_dev) on torch tensors resident on the device: the scoring
+        call's flags and detail records (a uint8 tensor), dom_off int64 [nq * H + 1], the wh_domain records (uint8 [n, 56]), the
+        envelope CSR int64 [n + 1] with its columns int32 and posteriors float32, order_t int32 [nq] or None.  Returns what
+        hits_msa returns (numpy arrays)."""
+        nq = offsets_t.numel() - 1
+        o = self.hits_opts(Z, domZ, incE, incdomE)
+        W, _, ptrs = self._msa_outputs()
+        nrows, recs = C.c_int64(0), C.c_void_p(None)
+        check(lib().wh_hits_msa_dev(self._h, text_t.data_ptr(), offsets_t.data_ptr(), nq, flags_t.data_ptr(), detail_t.data_ptr(),
+                                    dom_off_t.data_ptr(), dom_t.data_ptr(), env_off_t.data_ptr(), cols_t.data_ptr(), pp_t.data_ptr(),
+                                    int(h), None if order_t is None else order_t.data_ptr(), C.byref(o),
+                                    _lib.WH_MSA_NO_LDS if no_lds else 0, C.byref(nrows), C.byref(recs), C.byref(W),
+                                    *[C.byref(p) for p in ptrs], self._stream()), "wh_hits_msa_dev")
+        return self._hits_collect(int(h), nrows, recs, W, ptrs)
+
     def last_align_status(self):
         """(pairs redone in log space, pair numbers the last align call returned UNALIGNED - all columns -1 -
         because the any-size kernel could not align them; include/witch_hip.h: wh_last_align_status)."""

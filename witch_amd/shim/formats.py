@@ -3,8 +3,9 @@ Stockholm and hmmalign's multi-sequence alignment (Stockholm, Pfam, afa) out.  P
 import math
 
 
-def read_fasta(path):
-    """[(name, sequence)] - name is the first word of the header, like HMMER's sqio."""
+def read_fasta(path, descriptions=None):
+    """[(name, sequence)] - name is the first word of the header, like HMMER's sqio.  descriptions: a dict that receives
+    {name: the rest of the header line} for the records that have one (the "DE" text of hmmsearch -A)."""
     out, name, chunks = [], None, []
     with open(path) as f:
         for line in f:
@@ -12,7 +13,10 @@ def read_fasta(path):
             if line.startswith(">"):
                 if name is not None:
                     out.append((name, "".join(chunks)))
-                name = line[1:].split()[0] if len(line) > 1 and line[1:].split() else ""
+                words = line[1:].split(None, 1)
+                name = words[0] if words else ""
+                if descriptions is not None and len(words) > 1 and words[1].strip():
+                    descriptions[name] = words[1].strip()
                 chunks = []
             elif name is not None:
                 chunks.append(line.strip())
@@ -80,9 +84,10 @@ def _hmmsearch_head(hmm_path, fasta_path, hdr, rows):
     return out, namew
 
 
-def _hmmsearch_tail(out, hdr, n_targets, passed=None):
+def _hmmsearch_tail(out, hdr, n_targets, passed=None, trailer=None):
     """The pipeline summary that ends the main output; returns the text.  passed: None (a search with --max, as ever), or
-    ((n MSV, n bias, n Vit, n Fwd), (F1, F2, F3)) of a filtered search: HMMER's four "Passed ... filter:" lines."""
+    ((n MSV, n bias, n Vit, n Fwd), (F1, F2, F3)) of a filtered search: HMMER's four "Passed ... filter:" lines.
+    trailer: a line behind "//" (hits_msa_trailer: what hmmsearch -A says about its file)."""
     out.append("")
     out.append("")
     out.append("Internal pipeline statistics summary:")
@@ -95,12 +100,14 @@ def _hmmsearch_tail(out, hdr, n_targets, passed=None):
         for label, n, F in (("MSV", n1, F1), ("bias", nb, F1), ("Vit", n2, F2), ("Fwd", n3, F3)):
             out.append("%-28s%15d  (%.6g); expected %.1f (%.6g)" % ("Passed %s filter:" % label, n, n / nt, F * n_targets, F))
     out.append("//")
+    if trailer is not None:
+        out.append(trailer)
     out.append("[ok]")
     return "\n".join(out) + "\n"
 
 
 def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets, domains=None, lengths=None, Z=None, domZ=None, domE=10.0,
-                     incE=0.01, incdomE=0.01, passed=None):
+                     incE=0.01, incdomE=0.01, passed=None, trailer=None):
     """rows: [(name, bits, bias_bits, n_domains)] of the REPORTED sequences.  The table is what
     evalHMMSearchOutput reads: a line starting with 'E-value', then >= 9 whitespace-separated
     fields per row (E-value, score, bias, best-domain E-value/score/bias, exp, N, name), a blank
@@ -109,15 +116,15 @@ def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets, domains=None, l
     unrounded score as a fifth element, for the E-values) they hold the
     i-Evalue, score and bias of the pair's best domain (the highest envelope score), N is the number of reportable
     domains (incE / incdomE decide the '!' marks), and HMMER's "Domain annotation for each sequence" section (its ">> name" tables, as under --noali) follows.
-    passed: the stage counts and thresholds of a filtered search (_hmmsearch_tail); None under --max."""
+    passed: the stage counts and thresholds of a filtered search (_hmmsearch_tail); None under --max.  trailer: see there."""
     if domains is not None:
-        return _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE, passed)
+        return _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE, passed, trailer)
     out, namew = _hmmsearch_head(hmm_path, fasta_path, hdr, rows)
     for name, bits, bias, ndom in sorted(rows, key=lambda r: -r[1]):
         ev = forward_evalue(bits, n_targets, hdr["ftau"], hdr["flambda"])
         out.append("  %s %6.1f %5.1f  %s %6.1f %5.1f  %5.1f %2d  %-*s " %
                    (_g(ev), bits, bias, _g(ev), bits, bias, float(max(ndom, 1)), max(ndom, 1), namew, name))
-    return _hmmsearch_tail(out, hdr, n_targets, passed)
+    return _hmmsearch_tail(out, hdr, n_targets, passed, trailer)
 
 
 # ------------------------------------------------------------------------------------------------ per-domain output
@@ -233,7 +240,8 @@ def format_domain_table(name, entries, M, L):
     return out
 
 
-def _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE, passed=None):
+def _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE, passed=None,
+                              trailer=None):
     entries = domain_entries(hdr, rows, lengths, domains, n_targets, Z, domZ, domE, incE, incdomE)
     by_name = {}
     for e in entries:
@@ -258,7 +266,7 @@ def _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domain
     out.append("Domain annotation for each sequence:")
     for row in order:
         out.extend(format_domain_table(row[0], by_name.get(row[0], []), hdr["M"], lengths[row[0]]))
-    return _hmmsearch_tail(out, hdr, n_targets, passed)
+    return _hmmsearch_tail(out, hdr, n_targets, passed, trailer)
 
 
 def stockholm_row(seq_text, cols, M, flank_at_end=False):
@@ -446,6 +454,28 @@ def format_msa(names, rows, pp_rows, pp_cons, rf, outformat="Stockholm", width=2
             out.append("")
     out.append("//")
     return "\n".join(out) + "\n"
+
+
+def format_hits_msa(names, row_recs, rows, pp_rows, pp_cons, rf, descriptions=None, notextw=False):
+    """The file of hmmsearch -A: the alignment of the included domains (EHMM.hits_msa) as HMMER 3.1b2 writes it.  names: the
+    searched records' names by query number; row_recs: per row (query, index, ali_i, ali_j).  A row is named
+    "name/ali_i-ali_j" and carries "#=GS <row> DE [subseq from] <the record's description, or its name>"; Stockholm in
+    blocks of 200 columns, with --notextw (notextw) in one block.  No rows: HMMER creates the file empty."""
+    if len(row_recs) == 0:
+        return ""
+    descriptions = descriptions or {}
+    rnames, desc = [], {}
+    for q, _, ai, aj in ((int(r[0]), int(r[1]), int(r[2]), int(r[3])) for r in row_recs):
+        rnames.append("%s/%d-%d" % (names[q], ai, aj))
+        desc[rnames[-1]] = "[subseq from] %s" % descriptions.get(names[q], names[q])
+    return format_msa(rnames, rows, pp_rows, pp_cons, rf, "Pfam" if notextw else "Stockholm", desc=desc)
+
+
+def hits_msa_trailer(n_rows, path):
+    """What hmmsearch says behind "//" about its -A file (path: as given on the command line)."""
+    if n_rows == 0:
+        return "# No hits satisfy inclusion thresholds; no alignment saved"
+    return "# Alignment of %d hits satisfying inclusion thresholds saved to: %s" % (n_rows, path)
 
 
 def decode_stockholm_row(row):

@@ -97,7 +97,11 @@ def check_hmmsearch_options(opts):
     with exit status 1 instead of being silently ignored.
     --domtblout FILE is written (per-domain records of wh_domains; --domE, -Z and --domZ apply to it and to the
     domain tables of the main output, whose '!' / '?' marks follow --incE and --incdomE; without --domtblout none of
-    these five is read - -Z and --domZ are then not even checked, as before).  Two things stay unimplemented and are accepted as no-ops: --tblout (its exp,
+    these five is read - -Z and --domZ are then not even checked, as before).
+    -A FILE is written too: the alignment of every domain that satisfies the inclusion thresholds (wh_hits_msa: --incE,
+    --incdomE, -Z and --domZ are read and checked for it as for --domtblout; --notextw: one block), and the main output
+    says so behind "//"; a backend without search_hits refuses the option by name.
+    Two things stay unimplemented and are accepted as no-ops: --tblout (its exp,
     clu and ov columns need counts the scoring kernels do not export) and the alignment display (the output is always
     that of --noali)."""
     if "--max" not in opts and "--nobias" not in opts:
@@ -116,10 +120,12 @@ def check_hmmsearch_options(opts):
                 raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
             if o == "--domE" and not v >= 0:
                 raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
+            if o in ("--incE", "--incdomE") and "-A" in opts and not v >= 0:
+                raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
             if o == "-E" and v < 1e6:
                 raise ArgError("witch-hip hmmsearch shim: -E %s would drop hits; only E >= 1e6 (WITCH: 99999999) "
                                "is supported, every sequence with a domain is reported" % opts[o])
-    for o in (("-Z", "--domZ") if "--domtblout" in opts else ()):      # (read only for the per-domain output; else ignored as before)
+    for o in (("-Z", "--domZ") if "--domtblout" in opts or "-A" in opts else ()):      # (read only for the per-domain output and -A; else ignored as before)
         if o in opts:
             try:
                 ok = float(opts[o]) > 0
@@ -192,8 +198,20 @@ class GpuBackend:
         The domains cost an alignment per envelope: only a caller that prints them asks for them.
         filters=(F1, F2, F3): behind hmmsearch's acceleration filters (without the bias filter: --nobias); the stage
         counts of the search are then in self.last_passed (n MSV, n bias, n Vit, n Fwd)."""
+        hdr, rows, domains, _ = self._search(hmm_path, records, want_domains, filters, None)
+        return (hdr, rows, domains) if want_domains else (hdr, rows)
+
+    def search_hits(self, hmm_path, records, inc, want_domains=False, filters=None):
+        """search() for hmmsearch -A: (header, rows, domains or None, hits) - hits is EHMM.hits_msa's dict, the alignment of
+        every domain that satisfies the inclusion thresholds, its rows in HMMER's hit order (formats.hit_order) and domain
+        order.  inc: {"incE", "incdomE", "Z", "domZ"} (Z / domZ None: the number of targets / of reported sequences).  The
+        rows carry the unrounded score as the tables of --domtblout do.  With want_domains the domain records come from the
+        same alignment of the envelopes (wh_hits_msa hands them back): one domain stage serves --domtblout and -A."""
+        return self._search(hmm_path, records, want_domains, filters, inc)
+
+    def _search(self, hmm_path, records, want_domains, filters, inc):
         from witch_amd.ehmm import pack_queries
-        domains = {}
+        domains, hits = {}, None
         with self.lock:
             e, hdr = self.model(hmm_path)
             seqs = [e.digitize(t.upper()) for _, t in records]     # alignment_tools.py:730-731 upper-cases
@@ -204,8 +222,26 @@ class GpuBackend:
                 deci, flags, det = e.score(res, offs, want_detail=True, filters=filters, nobias=True)
                 c = e.last_filter_counts()
                 self.last_passed = (c["msv"], c["bias"], c["vit"], c["fwd"])
-            if want_domains:
+            exact = want_domains or inc is not None
+            rows = []
+            for i, (name, _) in enumerate(records):
+                if flags[i, 0] & 1:
+                    d = det[i]
+                    bias = max(0.0, float(d.pre_score) - float(d.seq_score))
+                    rows.append((name, deci[i, 0] / 10.0, bias, int(d.nenv)) + ((float(d.seq_score),) if exact else ()))
+            recs = dom_off = None
+            if inc is not None:
+                at = {name: i for i, (name, _) in enumerate(records)}
+                first = [at[r[0]] for r in formats.hit_order(rows, hdr)]
+                order = first + sorted(set(range(len(records))) - set(first))
+                hits = e.hits_msa(res, offs, "".join(t for _, t in records), flags, det,
+                                  Z=len(records) if inc.get("Z") is None else inc["Z"],
+                                  domZ=max(len(rows), 1) if inc.get("domZ") is None else inc["domZ"],
+                                  incE=inc.get("incE", 0.01), incdomE=inc.get("incdomE", 0.01), order=order, want_domains=True)
+                recs, dom_off = hits.pop("domains"), hits.pop("dom_off")
+            elif want_domains:
                 recs, dom_off = e.domains(res, offs, flags, det)
+            if want_domains:
                 for i, (name, _) in enumerate(records):
                     lst = []
                     for r in recs[dom_off[i]:dom_off[i + 1]]:
@@ -214,13 +250,7 @@ class GpuBackend:
                         lst.append(d)
                     if lst:
                         domains[name] = lst
-        rows = []
-        for i, (name, _) in enumerate(records):
-            if flags[i, 0] & 1:
-                d = det[i]
-                bias = max(0.0, float(d.pre_score) - float(d.seq_score))
-                rows.append((name, deci[i, 0] / 10.0, bias, int(d.nenv)) + ((float(d.seq_score),) if want_domains else ()))
-        return (hdr, rows, domains) if want_domains else (hdr, rows)
+        return hdr, rows, (domains if want_domains else None), hits
 
     def align(self, jobs):
         """jobs: [(hmm_path, name, text)] -> [(M, cols, pp)]; one launch per distinct model.  pp: the posterior
@@ -316,10 +346,12 @@ class Server:
         if not os.path.exists(fa):
             raise ArgError("Error: Failed to open sequence file %s for reading" % fa)
         check_hmmsearch_options(opts)
-        records = formats.read_fasta(fa)
         F = filter_thresholds(opts)
         fkw = {} if F is None else {"filters": F}           # (a search with --max calls the backend as ever)
         passed = lambda: None if F is None else (self.backend.last_passed, F)
+        if "-A" in opts:
+            return self.run_hmmsearch_hits(opts, hmm, fa, cwd, fkw, passed)
+        records = formats.read_fasta(fa)
         if "--domtblout" in opts:
             hdr, rows, domains = self.backend.search(hmm, records, want_domains=True, **fkw)
             lengths = {n: len(t) for n, t in records}
@@ -332,6 +364,40 @@ class Server:
         else:
             hdr, rows = self.backend.search(hmm, records, **fkw)
             text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records), passed=passed())
+        if "-o" in opts:
+            with open(os.path.join(cwd, opts["-o"]), "w") as f:
+                f.write(text)
+            return ""
+        return text
+
+    def run_hmmsearch_hits(self, opts, hmm, fa, cwd, fkw, passed):
+        """hmmsearch -A FILE: the search with the alignment of all included domains written to FILE (Stockholm in blocks of
+        200 columns; --notextw: one block), with or without --domtblout in the same call.  The main output gets HMMER's line
+        about the file behind "//"; its tables are those of a call without -A."""
+        if not hasattr(self.backend, "search_hits"):
+            raise ArgError("witch-hip hmmsearch shim: -A needs a backend that aligns the included hits (search_hits); "
+                           "this one does not, and the option is not ignored")
+        desc = {}
+        records = formats.read_fasta(fa, descriptions=desc)
+        want = "--domtblout" in opts
+        kw = {"Z": float(opts["-Z"]) if "-Z" in opts else None, "domZ": float(opts["--domZ"]) if "--domZ" in opts else None}
+        inc = {"incE": float(opts.get("--incE", 0.01)), "incdomE": float(opts.get("--incdomE", 0.01))}
+        hdr, rows, domains, hits = self.backend.search_hits(hmm, records, dict(inc, **kw), want_domains=want, **fkw)
+        n_rows = len(hits["row_recs"])
+        trailer = formats.hits_msa_trailer(n_rows, opts["-A"])
+        if want:
+            lengths = {n: len(t) for n, t in records}
+            kw["domE"] = float(opts.get("--domE", 10.0))
+            text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records), domains=domains, lengths=lengths, passed=passed(),
+                                            trailer=trailer, **kw, **inc)
+            with open(os.path.join(cwd, opts["--domtblout"]), "w") as f:
+                f.write(formats.format_domtblout(hmm, fa, hdr, rows, lengths, domains, len(records), **kw))
+        else:
+            text = formats.format_hmmsearch(hmm, fa, hdr, [r[:4] for r in rows], len(records), passed=passed(), trailer=trailer)
+        with open(os.path.join(cwd, opts["-A"]), "w") as f:
+            f.write(formats.format_hits_msa([n for n, _ in records], hits["row_recs"], hits["rows"], hits["pp_rows"], hits["pp_cons"],
+                                            None if formats.hmm_has_rf(hmm) else hits["rf"], descriptions=desc,
+                                            notextw="--notextw" in opts))
         if "-o" in opts:
             with open(os.path.join(cwd, opts["-o"]), "w") as f:
                 f.write(text)
