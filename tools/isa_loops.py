@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-loop instruction mix of one kernel in a hipcc -save-temps .s file.
 
-usage: tools/isa_loops.py [--waits] FILE.s KERNEL_SUBSTRING
+usage: tools/isa_loops.py [--waits | --lds] FILE.s KERNEL_SUBSTRING
 For every innermost loop (a label that a later branch jumps back to) prints its length and how many
 scratch loads/stores, LDS reads, VALU, AGPR moves and s_waitcnt it holds - the quick check that a
 sweep's row loop is free of register spills.
@@ -11,6 +11,11 @@ compiler's own block comments here ("Inner Loop Header" / "in Loop: Header="), s
 closing branch count too.  For every innermost loop: its instructions, the s_waitcnt that name vmcnt outside the block(s)
 that issue plain (not nt) global loads - the L2 fallback of a degenerate residue code, which completes its own loads - and
 for each of them the distance in instructions back to the nearest nt load of the loop (row_waits below).
+
+--lds: the twin for lgkmcnt, the counter of LDS accesses, which return in order.  For every innermost loop: the s_waitcnt that
+name lgkmcnt outside the fallback blocks, for each the distance in instructions back to the nearest LDS instruction before it
+along the same canonical row (round the back edge where needed), and which LDS accesses each wait is the first to cover, with
+the distance from their issue (lds_waits below).
 """
 import re
 import sys
@@ -27,13 +32,15 @@ def _is_insn(l):
     return l.startswith("\t") and not l.strip().startswith((";", "."))
 
 
-def inner_loops(body):
+def inner_loops(body, fine=False):
     """Innermost loops as the compiler's comments name them: {header label: [(label, [instruction, ...]), ...]}, the
     labelled blocks of each loop in an order in which the row executes them: the layout's order, a block placed out of line
-    (behind the loop's closing branch) moved to where the loop's own control flow first reaches it."""
+    (behind the loop's closing branch) moved to where the loop's own control flow first reaches it.
+    fine: the compiler's unlabelled blocks ("; %bb.N:", reached by falling through only) are blocks of their own, named "%bb.N":
+    a fallback block that follows the loop's header without a label is then told from the header."""
     blocks, cur = [], None                     # (label, annotation, instructions), layout order
     for l in body:
-        m = re.match(r"^(\.LBB\d+_\d+):(.*)$", l)
+        m = re.match(r"^(\.LBB\d+_\d+):(.*)$", l) or (fine and re.match(r"^; (%bb\.\d+):(.*)$", l))
         if m:
             cur = [m.group(1), m.group(2), []]
             blocks.append(cur)
@@ -53,7 +60,7 @@ def inner_loops(body):
             loops[hdr].append((label, insns))
     for hdr, members in loops.items():
         loops[hdr] = _execution_order(hdr, members)
-    return loops
+    return loops                               # (row_waits and lds_waits take the members of one loop)
 
 
 def _execution_order(hdr, members):
@@ -108,11 +115,47 @@ def row_waits(members):
     return pos, dist, fallback
 
 
+def lds_waits(members):
+    """(instructions of the loop without its fallback blocks, [(position, n, distance, covered)] for every s_waitcnt lgkmcnt(n)
+    outside them, fallback blocks).  <distance>: instructions from the nearest LDS instruction before the wait to the wait, along
+    the canonical row of row_waits, round the back edge if need be (None: the loop has no LDS instruction).  <covered>: the LDS
+    accesses this wait is the first to cover, as (mnemonic, instructions since their issue).  LDS accesses return in order, so
+    lgkmcnt(n) covers all but the n youngest; the row is walked twice and the second walk is reported, so that an access issued
+    behind its wait is found round the back edge.  (A loop whose row also issues scalar loads would need lgkmcnt(0) for them:
+    none of the sweeps' row loops does, and such a wait is simply reported with what it covers.)"""
+    fallback = [label for label, insns in members if any(re.match(r"(global|buffer|flat)_load", i) and not i.endswith(" nt") for i in insns)]
+    row = [ins for label, insns in members if label not in fallback for ins in insns]
+    n_row = len(row)
+    lds = [p for p, ins in enumerate(row) if ins.startswith("ds_")]
+    out, queue = [], []
+    for walk in range(2):
+        for p, ins in enumerate(row):
+            if ins.startswith("ds_"):
+                queue.append((ins.split()[0], walk * n_row + p))
+            m = re.match(r"s_waitcnt\b.*lgkmcnt\((\d+)\)", ins)
+            if m:
+                n = int(m.group(1))
+                done = queue[:max(len(queue) - n, 0)]
+                queue = queue[len(done):]
+                if walk == 1:
+                    dist = min(((p - q - 1) % n_row) + 1 for q in lds) if lds else None
+                    out.append((p, n, dist, [(name, walk * n_row + p - at) for name, at in done]))
+    return n_row, out, fallback
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--waits"]
+    args = [a for a in sys.argv[1:] if a not in ("--waits", "--lds")]
     path, key = args[0], args[1]
     lines = open(path).read().splitlines()
     body = function_body(lines, key)
+    if "--lds" in sys.argv[1:]:
+        for hdr, members in inner_loops(body, fine=True).items():
+            n, waits, fallback = lds_waits(members)
+            print("%s loop %s: n=%4d without %d fallback block(s); lgkmcnt waits outside them: %d" % (key, hdr, n, len(fallback), len(waits)))
+            for p, cnt, dist, done in waits:
+                print("    at %4d lgkmcnt(%d): %s instructions after the nearest LDS instruction; first to cover: %s"
+                      % (p, cnt, dist, ", ".join("%s (+%d)" % d for d in done) or "nothing"))
+        return
     if "--waits" in sys.argv[1:]:
         for hdr, members in inner_loops(body).items():
             n, dist, fallback = row_waits(members)

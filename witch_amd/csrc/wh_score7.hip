@@ -93,10 +93,32 @@ constexpr bool kMaskedAcc = true;   // P4: only lanes that own a stored Forward 
 #ifndef WH_ROW_WAITS
 #define WH_ROW_WAITS (WH_K7_NEW_DEFAULT ? 3 : 0)
 #endif
+// WH_ROW_AHEAD (bits; the default object: 7; 0 = the parent's rows, what the A/B slot keeps): what a row of the two node-window
+// sweeps (sweep_backward_decode_win, sweep_backward_null2_win) waits for on lgkmcnt.  A window lane owns four cells, so a row is one
+// dependent chain, and the parent's row began with two LDS round trips that nothing could hide: the residue byte (ds_read_u8 ->
+// wait -> readfirstlane -> branch) and, behind the branch, the emission piece (ds_read_b128 -> wait -> its eight consumers).
+// 1: a row enters with the code of its residue in a scalar register: row i reads the byte of row i - 2 where it begins - always,
+// at a clamped index: a read inside a branch is waited for where the branches meet - and takes it with readfirstlane where it ends.
+// The envelope window row reads the mask word of row i - 1 the same way (always, at a clamped row; taken apart where the row
+// request is issued): inside `if (i > 1)` it was a third round trip at the row's head.
+// 2 (with 1): the emission piece of row i - 1 is requested by row i right after it has consumed its own, into the registers that
+// one leaves (one set, defined by its load alone: no copy at the loop's edge, which would wait for it) - the request is
+// unconditional at a code clamped to a canonical one; a degenerate code takes the L2 branch as before and ignores the piece.
+// 4: the multihit window row takes the words of record i - 1 that wait a row for their turn, and the residue byte, BEFORE lane 0
+// writes the row's posteriors: behind that branch the compiler cannot count the writes and waited for all of them at the back edge.
+// No address, operand, operation or order of a sum changes.  Every LDS instantiation takes all three, the 512-node windows too
+// (no scratch access in any row loop; the 256-node sweeps use 132 / 164 vector registers where they used 118 / 148, and the kernel
+// around them saves more across the calls: score_kernel7<16, 768, false> 352 -> 400 B of scratch per lane, cap 448).  Not for the long-query sweeps (SG), the four-envelope kernel's window
+// (TMPG), the objects that compile this file for its sweeps (WH_SWEEPS_ONLY) and the A/B slot.
+// tests/test_window_row_ahead_isa.py reads the compiled loops, tests/test_window_row_ahead.py compares the bits with the slot's.
+#ifndef WH_ROW_AHEAD
+#define WH_ROW_AHEAD (WH_K7_NEW_DEFAULT ? 7 : 0)
+#endif
 constexpr int kLayout = WH_SPEC_ROWS ? SPEC_ROWS : SPEC_SOA;
 constexpr bool kUni = WH_UNI != 0;
 constexpr bool kRowPairs = ((WH_ROW_PAIRS) & 1) != 0, kUniArgs = ((WH_ROW_PAIRS) & 2) != 0, kSplitSlack = WH_SPLIT_SLACK != 0;
 constexpr bool kDrain = ((WH_ROW_WAITS) & 1) != 0, kLateRequest = ((WH_ROW_WAITS) & 2) != 0;
+constexpr bool kAheadCode = ((WH_ROW_AHEAD) & 1) != 0, kAheadPiece = ((WH_ROW_AHEAD) & 3) == 3, kAheadWrites = ((WH_ROW_AHEAD) & 4) != 0;
 static_assert(kLayout == SPEC_SOA || kSlim, "a row record has six words (WH_SLIM_SPEC)");
 template <bool SG> using SpecOf = SpecAt<SG ? (int)SPEC_SOA : kLayout>;
 constexpr int kSpecTag = kSpArr | (kLayout << 8);      // what ScoreArgs::spec_arrays must say for this object
@@ -513,14 +535,30 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 
   // CARRY: the words of record i - 1 are loaded together where row i begins - beside its mask word, which the row request
   // reads there anyway - and its scale exponent is row i - 1's own one iteration later: one LDS round trip per row, not six
   int S_row = CARRY ? ldi(at(SP_S, Ld)) : 0;
+  // WH_ROW_AHEAD: <x_cur> the residue code of the row that begins, <x_nxt> of the row after it; <O_pf> the LDS emission piece of the
+  // row that begins (of a canonical code where its own is degenerate), requested by the row before
+  constexpr bool kCode = kAheadCode && !SG && !BWG, kPiece = kAheadPiece && !SG && !BWG;
+  int x_cur = 0, x_nxt = 0;
+  float4 O_pf[B4];
+  if (kCode) x_nxt = __builtin_amdgcn_readfirstlane((int)eseq[max(Ld - 1, 0)]);
+  if (kPiece) {
+#pragma unroll
+    for (int p4 = 0; p4 < B4; p4++) O_pf[p4] = make_float4(0.f, 0.f, 0.f, 0.f);      // (row Ld consumes none)
+  }
   // row i: its stored Forward cells are in <fm_c, fi_c, have>; row i - 1 is requested into <fm_n, fi_n, have_n>
   auto row = [&](int i, const float4 (&fm_c)[B4], const float4 (&fi_c)[B4], bool have, float4 (&fm_n)[B4], float4 (&fi_n)[B4], bool &have_n) {
     bool have_l = false;
-    if (kLate) {
-      if (i > 1) have_l = ((lanef < 32 ? ldu(at(kSpML, i - 1)) : ldu(at(kSpMH, i - 1))) >> (lanef & 31)) & 1u;
+    unsigned mword_l = 0;
+    if (kLate && kCode) {
+      // (read always, at a clamped row, and taken apart where the request is issued: read inside `if (i > 1)` it was waited for at once)
+      const int rl = max(i - 1, 1);
+      mword_l = lanef < 32 ? ldu(at(kSpML, rl)) : ldu(at(kSpMH, rl));
+    } else if (kLate) {
+      if (i > 1) have_l =((lanef < 32 ? ldu(at(kSpML, i - 1)) : ldu(at(kSpMH, i - 1))) >> (lanef & 31)) & 1u;
     } else if (i > 1) request_row(i - 1, false, fm_n, fi_n, have_n);
-    int S_p = 0;
+    int S_p = 0, xv = 0;
     float N_p = 0.f, J_p = 0.f, C_p = 0.f;
+    if (kCode) xv = (int)eseq[max(i - 2, 0)];      // (the last two rows read a byte nobody takes)
     if (CARRY) {
       S_p = ldi(at(SP_S, i, 1)); N_p = ldf(at(SP_N, i, 1)); C_p = ldf(at(SP_C, i, 1));
       if (!UNI) J_p = ldf(at(SP_J, i, 1));
@@ -529,7 +567,7 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 
     const int dS = S_i - (CARRY ? S_p : SG ? R.s(3, i) : ldi(at(SP_S, i, 1)));
     if (i < Ld) {
       if (UNI) mirror_scale<QB>(S_next - S_i, Mb, Ib, xC, xN); else mirror_scale<QB>(S_next - S_i, Mb, Ib, xJ, xC, xN);
-      const int x = __builtin_amdgcn_readfirstlane((int)eseq[i]);
+      const int x = kCode ? x_cur : __builtin_amdgcn_readfirstlane((int)eseq[i]);
       float part = 0.f;
       // the consumer sits inside each branch: a value live across the merge would be one flat load (wh_device.h)
       auto emit = [&](auto em_ld) {
@@ -543,8 +581,10 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 
           Mb[4 * p4 + 3] *= O.x; part = fmaf(E.w, Mb[4 * p4 + 3], part);
         }
       };
-      if (x < Klds) emit([&](int p4) { return em4L[x * (Q * 16) + fwd[p4]]; });
-      else {
+      if (x < Klds) {
+        if (kPiece) emit([&](int p4) { return O_pf[p4]; });
+        else emit([&](int p4) { return em4L[x * (Q * 16) + fwd[p4]]; });
+      } else {
         emit([&](int p4) { return em4G[(size_t)x * (Q * 16) + fwd[p4]]; });
         if (kDrain && !SG) wait_vmcnt0();
       }
@@ -552,6 +592,11 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 
       if (!UNI) xJ = fmaf(xJ, cu.loop, xB * cu.move);
       xC = xC * cu.loop;
       xN = fmaf(xN, cu.loop, xB * cu.move);
+    }
+    if (kPiece) {
+      const int xc = x_nxt < Klds ? x_nxt : 0;
+#pragma unroll
+      for (int p4 = 0; p4 < B4; p4++) O_pf[p4] = em4L[xc * (Q * 16) + fwd[p4]];
     }
     const float xE = UNI ? xC : fmaf(xC, cu.EC, xJ * cu.EJ);
     backward_cells<QB, true, false>(T, sc, Mb, Ib, xE);
@@ -574,6 +619,7 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 
       fIs = fmaf(idot, s_i, fIs);
     }
     if (kLate) {
+      if (kCode) have_l = i > 1 && ((mword_l >> (lanef & 31)) & 1u);
       have_n = have_l;
       if (have_l) {
         const float4 *rown = reinterpret_cast<const float4 *>((const float *)c.Fs) + (size_t)(i - 1) * (2 * Q4 * kWave);
@@ -587,6 +633,7 @@ __device__ __noinline__ P4Out sweep_backward_null2_win(const WaveCtx c_, lds_u8 
     S_next = S_i;
     if (CARRY) S_row = S_p;
     xfac = fmaf(nj * cu.loop, s_p, xfac);
+    if (kCode) { x_cur = x_nxt; x_nxt = __builtin_amdgcn_readfirstlane(xv); }
   };
   if (kLate) {
 #pragma unroll 1
@@ -941,14 +988,24 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c_, lds_u
   int S_row = 0;
   float E_row = 0.f, B_row = 0.f;                        // CARRY: record i's words, loaded one iteration ago
   if (CARRY) { S_row = speci[at(SP_S, L)]; E_row = spec[at(SP_E, L)]; B_row = spec[at(SP_B, L)]; }
+  // WH_ROW_AHEAD: as in sweep_backward_null2_win
+  constexpr bool kCode = kAheadCode && !TMPG && !BWG, kPiece = kAheadPiece && !TMPG && !BWG, kEarly = kAheadWrites && CARRY && !TMPG && !BWG;
+  int x_cur = 0, x_nxt = 0;
+  float4 O_pf[B4];
+  if (kCode) x_nxt = __builtin_amdgcn_readfirstlane((int)seq[max(L - 1, 0)]);
+  if (kPiece) {
+#pragma unroll
+    for (int p4 = 0; p4 < B4; p4++) O_pf[p4] = make_float4(0.f, 0.f, 0.f, 0.f);      // (row L consumes none)
+  }
 #pragma unroll 1
   for (int i = L; i >= 0; i--) {
     asm volatile("" ::: "memory");
     // (the loads that define the carried words: nothing else is assigned to them, so no copy waits for a load at the loop's edge)
     const int S_i = CARRY ? S_row : 0;
     const float E_i = CARRY ? E_row : 0.f, B_i = CARRY ? B_row : 0.f;
-    int S_p = 0;
+    int S_p = 0, xv = 0;
     float N_p = 0.f, J_p = 0.f, C_p = 0.f;
+    if (kCode) xv = (int)seq[max(i - 2, 0)];         // (the last two rows read a byte nobody takes)
     if (CARRY) {
       const int ip = i >= 1 ? i - 1 : 0;                 // (row 0 reads its own record: N(0) for the window's share, the rest unused)
       S_p = speci[at(SP_S, ip)]; N_p = spec[at(SP_N, ip)]; J_p = spec[at(SP_J, ip)]; C_p = spec[at(SP_C, ip)];
@@ -956,7 +1013,7 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c_, lds_u
       S_row = S_p;
     }
     if (i < L) {
-      const int x = __builtin_amdgcn_readfirstlane((int)seq[i]);
+      const int x = kCode ? x_cur : __builtin_amdgcn_readfirstlane((int)seq[i]);
       float part = 0.f;
       auto emit = [&](auto em_ld) {
 #pragma unroll
@@ -969,8 +1026,10 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c_, lds_u
           Mb[4 * p4 + 3] *= O.x; part = fmaf(E.w, Mb[4 * p4 + 3], part);
         }
       };
-      if (x < Klds) emit([&](int p4) { return em4L[x * (Q * 16) + fwd[p4]]; });
-      else {
+      if (x < Klds) {
+        if (kPiece) emit([&](int p4) { return O_pf[p4]; });
+        else emit([&](int p4) { return em4L[x * (Q * 16) + fwd[p4]]; });
+      } else {
         emit([&](int p4) { return em4G[(size_t)x * (Q * 16) + fwd[p4]]; });
         if (kDrain) wait_vmcnt0();
       }
@@ -978,6 +1037,11 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c_, lds_u
       xJ = fmaf(xJ, cm.loop, xB * cm.move);
       xC = xC * cm.loop;
       xN = fmaf(xN, cm.loop, xB * cm.move);
+    }
+    if (kPiece) {
+      const int xc = x_nxt < Klds ? x_nxt : 0;
+#pragma unroll
+      for (int p4 = 0; p4 < B4; p4++) O_pf[p4] = em4L[xc * (Q * 16) + fwd[p4]];
     }
     float xE = fmaf(xC, cm.EC, xJ * cm.EJ);
     if (i >= 1) backward_cells<QB, true, false>(T, sc, Mb, Ib, xE);
@@ -1003,6 +1067,9 @@ __device__ __noinline__ WinDec sweep_backward_decode_win(const WaveCtx c_, lds_u
     } else {
       ratio = (CARRY ? N_p : spec[at(SP_N, 0)]) * xN * s_i;               // N_F(0) N_B(0) / Z: the share of the paths that stay inside the window
     }
+    // (the record words that wait a row for their turn and the residue byte are taken here, in front of lane 0's writes)
+    if (kEarly) asm volatile("" : "+v"(E_row), "+v"(B_row));
+    if (kCode) { x_cur = x_nxt; x_nxt = __builtin_amdgcn_readfirstlane(xv); }
     __builtin_amdgcn_wave_barrier();
     if (TMPG) { if (lane == 0) { gE[i] = pe; gB[i] = pb; gN[i] = njc; } }
     else if (lane == 0) {
