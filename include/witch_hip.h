@@ -280,21 +280,29 @@ int wh_hmm_evparams(const char *hmm_path, float *tau, float *lambda, int32_t *pr
 /* ---- hmmsearch's acceleration filters (hmmsearch WITHOUT --max: MSV filter -> bias filter -> Viterbi filter -> Forward) ----
  * Per (query of length L, model), as HMMER 3.1b2's pipeline decides, with null1 = L ln(L / (L + 1)) + ln(1 / (L + 1)):
  *   1. MSV      P = gumbel_surv((usc - null1) / ln 2; mu_MSV, lambda)        rejected where P > F1; a filter overflow passes
- *   2. bias     NOT IMPLEMENTED (its definition could not be pinned on the reference's binary): the pipeline runs as
- *               "hmmsearch --nobias" does, filtersc = null1, and a call with nobias = 0 is refused with WH_EINVAL
+ *   2. bias     OPT-IN (nobias = WH_BIAS_FILTER_ON).  filtersc = the float32 scaled Forward score of the query on a two-state
+ *               HMM (background; the model's composition, its COMPO line, staying L1 = M / 8 residues on average) plus the
+ *               length terms of null1, as p7_bg_FilterScore computes it;  P = gumbel_surv((usc - filtersc) / ln 2; mu_MSV,
+ *               lambda), rejected where P > F1.  With nobias = 1 the pipeline runs as "hmmsearch --nobias" does:
+ *               filtersc = null1 and the stage passes with stage 1.  nobias = 0 is STILL REFUSED with WH_EINVAL: a later
+ *               change makes 0 mean WH_BIAS_FILTER_ON (HMMER's default) and retires the refusal.
  *   3. Viterbi  only where the last P > F2:  P = gumbel_surv((vfsc - filtersc) / ln 2; mu_VIT, lambda), rejected where P > F2
  *   4. Forward  P = exp_surv((fwdsc - filtersc) / ln 2; tau, lambda), rejected where P > F3 (wh_score_filtered only)
  * mu, tau, lambda: the model's three "STATS LOCAL" lines; a model without them cannot be filtered (WH_EINVAL, the message
  * names it).  The two filters are integer dynamic programmes (8-bit, 16-bit): the device's raw scores are the host's and
  * HMMER's to the bit, and every decision is a comparison of float32 scores that both sides compute with correctly
  * rounded operations alone - wh_filter and wh_filter_host agree bit for bit.
- * opts == NULL: HMMER's defaults, F1 = 0.02, F2 = 1e-3, F3 = 1e-5, nobias = 0 (so: refused until the bias filter exists; pass
- * nobias = 1).  F >= 1 switches a stage off.
+ * With the bias filter on, device and host also agree bit for bit on filtersc: one float32 recurrence without fused
+ * operations, its logarithms from + - x / on float64 alone (no libm on either side).
+ * opts == NULL: HMMER's defaults, F1 = 0.02, F2 = 1e-3, F3 = 1e-5, nobias = 0 (so: refused until the bias filter is the
+ * default; pass nobias = 1 or WH_BIAS_FILTER_ON; any other value is WH_EINVAL).  F >= 1 switches a stage off.
  * stage[nq x H], in the scoring calls' pair order: bit 0 passed MSV, 1 passed bias, 2 passed Viterbi (also set where the
  * sweep was skipped because the pair was below F2 already), 3 the Viterbi sweep ran, 4 passed Forward (wh_score_filtered
- * only).  An empty query fails every stage.  filter_bias_nats (optional) = filtersc - null1: 0 without a bias filter.
+ * only).  An empty query fails every stage.  filter_bias_nats (optional) = filtersc - null1: 0 with nobias = 1, and where
+ * the bias filter did not run (a pair rejected by the MSV stage).
  * msv_raw / vit_raw (optional): the filters' raw integer results - MSV xJ (-1: overflow), Viterbi xC (32768: overflow,
  * -32768: no path, -32769: the sweep did not run). */
+#define WH_BIAS_FILTER_ON 2   /* wh_filter_opts.nobias: run the bias filter (1: hmmsearch --nobias; 0: refused for now) */
 typedef struct wh_filter_opts { double F1, F2, F3; int32_t nobias; } wh_filter_opts;
 int wh_filter(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const wh_filter_opts *opts,
               uint8_t *stage, float *filter_bias_nats, int32_t *msv_raw, int32_t *vit_raw);
@@ -321,6 +329,9 @@ int wh_score_filtered_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *
 /* The last wh_filter / wh_score_filtered call on the handle: out[0] = pairs, [1] passed MSV, [2] passed bias, [3] passed
  * Viterbi, [4] passed Forward, [5] pairs handed to the scoring kernels ([4], [5]: 0 after wh_filter).  Waits for the device. */
 int wh_last_filter_counts(wh_ehmm *e, int64_t out[6]);
+/* Test hook of the bias filter's logarithm (float64 arithmetic alone, the same code on host and device): the number of
+ * float32 bit patterns in [first, last] on which it differs from (float) log((double) x) of the host's libm. */
+int64_t wh_filter_log_differences(uint32_t first, uint32_t last);
 
 /* Outcome classes of the last wh_align / wh_align_dev call on this handle (the call itself returns WH_OK for
  * them): n_logspace = pairs that left the float range and were redone in log space (same columns as hmmalign's

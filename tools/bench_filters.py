@@ -8,9 +8,11 @@ workload (and its first model alone, the level-0 case).  Reported, not a gate:
 
 The models are built from the family's subset alignments with this library's hmmbuild and CALIBRATED (STATS LOCAL lines
 from wh_hmmbuild_batch on the device) - bench.py's own model files carry placeholder statistics, with which a rejection
-share would mean nothing.  The filtered runs are those of hmmsearch --nobias (the bias filter is not implemented).
+share would mean nothing.  The filtered runs are those of hmmsearch --nobias; --bias times the filter kernels and the
+filtered scoring a second time with HMMER's bias filter switched on (WH_BIAS_FILTER_ON) and reports both.
 
     python tools/bench_filters.py [--nq 8192] [--nh 200] [--reps 3] [--out profiles/filters_mi355x.json]
+    python tools/bench_filters.py --bias --out profiles/filters_bias_mi355x.json
 """
 import argparse
 import ctypes as C
@@ -58,14 +60,14 @@ def timed(fn, reps):
     return statistics.median(ms), ms
 
 
-def run_case(paths, res_t, off_t, maxlen, reps, F):
+def run_case(paths, res_t, off_t, maxlen, reps, F, bias=False):
     import torch
     from witch_amd._lib import check, lib
     from witch_amd.ehmm import EHMM
     e = EHMM(paths)
     nq, H = off_t.numel() - 1, len(paths)
     dev = res_t.device
-    o = EHMM.filter_opts(F, nobias=True)
+    o = EHMM.filter_opts(F, bias=True) if bias else EHMM.filter_opts(F, nobias=True)
     stage = torch.empty((nq, H), dtype=torch.uint8, device=dev)
     deci = torch.empty((nq, H), dtype=torch.int32, device=dev)
     flags = torch.empty((nq, H), dtype=torch.uint8, device=dev)
@@ -90,11 +92,11 @@ def run_case(paths, res_t, off_t, maxlen, reps, F):
     reported = int((flags & 1).sum().item())
     e.close()
     n = float(c["pairs"])
-    return {"models": H, "queries": nq, "pairs": c["pairs"], "thresholds": list(F),
+    return {"models": H, "queries": nq, "pairs": c["pairs"], "thresholds": list(F), "bias_filter": bool(bias),
             "filter_kernels_ms": f_ms, "filter_kernels_ms_all": f_all, "filter_pairs_per_s": n / (f_ms * 1e-3),
             "wh_score_ms": p_ms, "wh_score_ms_all": p_all, "wh_score_filtered_ms": s_ms, "wh_score_filtered_ms_all": s_all,
             "filtered_over_plain": s_ms / p_ms,
-            "rejected_share": {"msv": 1 - c["msv"] / n, "viterbi": (c["bias"] - c["vit"]) / n, "forward": (c["vit"] - c["fwd"]) / n},
+            "rejected_share": {"msv": 1 - c["msv"] / n, "bias": (c["msv"] - c["bias"]) / n, "viterbi": (c["bias"] - c["vit"]) / n, "forward": (c["vit"] - c["fwd"]) / n},
             "passed": {k: c[k] for k in ("msv", "bias", "vit", "fwd")}, "pairs_scored": c["scored"],
             "reported_plain": reported_plain, "reported_filtered": reported}
 
@@ -105,6 +107,7 @@ def main():
     ap.add_argument("--nh", type=int, default=200)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--bias", action="store_true", help="also with the bias filter on (keys H200_bias, H1_bias)")
     ap.add_argument("--note", default="", help="free text stored with the result (e.g. a figure printed by the tests)")
     a = ap.parse_args()
     import torch
@@ -123,6 +126,11 @@ def main():
                "query_len": int(qlen), "calibrated_build_s": build_s, "note": a.note,
                "H200": run_case(paths, res_t, off_t, int(qlen), a.reps, F),
                "H1": run_case(paths[:1], res_t, off_t, int(qlen), a.reps, F)}
+        if a.bias:
+            out["H200_bias"] = run_case(paths, res_t, off_t, int(qlen), a.reps, F, bias=True)
+            out["H1_bias"] = run_case(paths[:1], res_t, off_t, int(qlen), a.reps, F, bias=True)
+            for k_ in ("H200", "H1"):
+                out[k_ + "_bias"]["filter_kernels_on_over_off"] = out[k_ + "_bias"]["filter_kernels_ms"] / out[k_]["filter_kernels_ms"]
     if a.out and os.path.exists(a.out):        # the key tests/test_filters_gpu.py writes into the same file stays
         try:
             old = json.load(open(a.out))

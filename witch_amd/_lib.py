@@ -16,6 +16,7 @@ CSRC = os.path.join(_HERE, "csrc")
 WH_MAX_ENVELOPES = 16
 FLAG_REPORTED, FLAG_MULTI, FLAG_OVERRIDE, FLAG_TRUNC, FLAG_EXACT = 1, 2, 4, 8, 16
 FLAG_FILTERED = 32
+BIAS_FILTER_ON = 2       # wh_filter_opts.nobias: WH_BIAS_FILTER_ON
 STAGE_MSV, STAGE_BIAS, STAGE_VIT, STAGE_VIT_RAN, STAGE_FWD = 1, 2, 4, 8, 16      # stage byte of wh_filter / wh_score_filtered
 VIT_NOT_RUN, VIT_OVERFLOW, MSV_OVERFLOW = -32769, 32768, -1
 ALPH_DNA, ALPH_RNA, ALPH_AMINO = 0, 1, 2
@@ -48,7 +49,8 @@ class Domain(C.Structure):
 
 
 class FilterOpts(C.Structure):
-    """wh_filter_opts (include/witch_hip.h): HMMER's thresholds F1, F2, F3 and --nobias."""
+    """wh_filter_opts (include/witch_hip.h): HMMER's thresholds F1, F2, F3 and nobias (1: --nobias, BIAS_FILTER_ON: the bias
+    filter runs, 0: refused for now)."""
     _fields_ = [("F1", C.c_double), ("F2", C.c_double), ("F3", C.c_double), ("nobias", C.c_int32)]
 
 
@@ -127,6 +129,7 @@ SYMBOLS = {
     "wh_score_filtered": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "wh_score_filtered_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "wh_last_filter_counts": (C.c_int, [_P, _P]),
+    "wh_filter_log_differences": (C.c_int64, [C.c_uint32, C.c_uint32]),
     "wh_ehmm_evparams": (C.c_int, [_P, _P, _P, _P]),
     "wh_hmm_evparams": (C.c_int, [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "wh_consensus": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),

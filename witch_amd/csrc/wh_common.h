@@ -46,6 +46,11 @@ struct HostHMM {
   std::vector<float> tf, matf;             // [(M+1)*7], [(M+1)*K]
   bool has_mstats = false, has_vstats = false;
   float mmu = 0.f, mlambda = 0.f, vmu = 0.f, vlambda = 0.f;
+  // the bias filter's second state emits the model's composition: the COMPO line in float32 like every other field.  A file
+  // without the line: all zero - that is what the reference's hmmsearch scores with (every stage outcome of
+  // tests/golden/filters_bias/nocompo equals a COMPO line of '*'s, and differs from the composition hmmbuild would print)
+  std::vector<float> compo;                // [K]
+  bool has_compo = false;
   // configured profile
   std::vector<double> pt;     // [(M+1)*7], node 0 and node M zeroed
   std::vector<double> entry;  // [M+2]

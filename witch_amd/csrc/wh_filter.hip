@@ -21,13 +21,32 @@
 // Models beyond 3 072 nodes: one LANE per pair runs the scalar cores themselves with rows in HBM, lane-interleaved, as
 // the calibration kernel does - no model-length limit.
 // Results leave through ordinary vector stores of lane 0.
+//
+// THE BIAS FILTER (WH_FILTER_BIAS=1: this file compiled a second time into wh_filter_bias.o, whose launchers carry the
+// suffix _bias; without it the kernels compile exactly as they did before the stage existed).  A pair past the MSV stage
+// runs the composition Forward of wh_filter.h between the MSV sweep and the stage decision - the MSV row is dead by then.
+// The two-value recurrence is wave-uniform (every lane computes it); residues are fetched 64 at a time, each lane looks
+// up its own residue's odds ratio, and v_readlane hands them out.  Lane j keeps the maximum of row base + j, so the 64
+// filter_logs of a chunk are taken in parallel; their float32 sum is then formed in row order, which makes the bits the
+// scalar function's (filter_bias_score).  The long-model kernel calls the scalar function itself.
 #include <hip/hip_runtime.h>
 
 #include "wh_filter.h"
 
+#ifndef WH_FILTER_BIAS
+#define WH_FILTER_BIAS 0
+#endif
+
 namespace whf {
 
 namespace {
+
+constexpr bool kBias = WH_FILTER_BIAS != 0;
+#if WH_FILTER_BIAS
+using KArgs = FilterBiasArgs;
+#else
+using KArgs = FilterArgs;
+#endif
 
 constexpr int kNeg = -(1 << 29);       // "no path" of the int32 D closure: below every clamped value, far from overflow
 
@@ -192,9 +211,36 @@ template <int Q> __device__ int vit_sweep(const FilterDevModel &d, const int16_t
   return xC;
 }
 
-template <int Q> __global__ __launch_bounds__(256) void filter_kernel(FilterArgs a, long long npairs) {
+#if WH_FILTER_BIAS
+// ---- bias filter: filter_bias_score's value -----------------------------------------------------------------------
+__device__ __forceinline__ float readlane_f(float x, int r) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), r)); }
+
+__device__ float bias_sweep(const FilterBias *bm, FilterBiasLen bl, const uint8_t *res, int L, int Kp, int lane) {
+  const float t10 = bm->t10, t11 = bm->t11;
+  FilterBiasRow s{0.f, 0.f};
+  float nullsc = 0.f;
+  for (int i0 = 0; i0 < L; i0 += 64) {
+    const int mine = i0 + lane < L ? min((int)res[i0 + lane], Kp - 1) : 0;      // (a code outside the alphabet must not leave the table)
+    const float myeo = bm->eo1[mine];
+    const int n = min(64, L - i0);
+    float mymx = 1.f;
+    for (int r = 0; r < n; r++) {
+      const float mx = filter_bias_row(s, i0 + r == 0, readlane_f(myeo, r), t10, t11, bl);
+      if (lane == r) mymx = mx;
+    }
+    const float lg = filter_log(mymx);
+    for (int r = 0; r < n; r++) nullsc = nullsc + readlane_f(lg, r);      // in row order
+  }
+  return filter_bias_end(nullsc, s, bl);
+}
+#endif
+
+template <int Q> __global__ __launch_bounds__(256) void filter_kernel(KArgs a, long long npairs) {
   const int lane = threadIdx.x & 63;
-  const long long p = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  // (with the bias sweep, up to 16 cells per lane: the wave's number is made known to be uniform, so that the pair's model
+  // record and settings stay in scalar registers across the three sweeps - that keeps the waves per SIMD of the kernel
+  // without the sweep for Q = 2, 4, 8; the two largest classes keep theirs without it and lose one with it)
+  const long long p = (long long)blockIdx.x * 4 + (kBias && Q <= 16 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6));
   if (p >= npairs) return;
   // consecutive waves: consecutive queries of one model
   const long long q = p % a.nq;
@@ -204,14 +250,25 @@ template <int Q> __global__ __launch_bounds__(256) void filter_kernel(FilterArgs
   const int L = (int)(a.offsets[q + 1] - o0);
   const long long out = q * a.H + h;
   int stage = 0, msv = 0, vit = kVitNotRun;
+  float bias_nats = 0.f;
   if (L > a.lmax) stage = kStageBadLen;      // (the caller's max_len is wrong: no record for this length)
   else if (L > 0) {
-    const FilterLen fl = a.lens[L];
+    FilterLen fl = a.lens[L];
     const uint8_t *res = a.residues + o0;
     msv = msv_sweep<Q>(d, a.tables + d.rb, res, L, fl.tjb, lane);
     msv = __builtin_amdgcn_readfirstlane(msv);
     bool run_vit = false;
+#if !WH_FILTER_BIAS
     stage = filter_stage12(msv, fl, d.base_b, d.scale_b, d.thr, &run_vit);
+#else
+    float usc;
+    if (filter_stage1(msv, fl, d.base_b, d.scale_b, d.thr, &usc)) {
+      const float filtersc = readlane_f(bias_sweep(a.bias + h, a.blens[L], res, L, d.Kp, lane), 0);
+      stage = filter_stage2_bias(usc, filtersc, d.thr, &run_vit);
+      bias_nats = filtersc - fl.nullsc;
+      fl.nullsc = filtersc;              // the Viterbi stage scores against it
+    }
+#endif
     if (run_vit) {
       vit = vit_sweep<Q>(d, reinterpret_cast<const int16_t *>(a.tables + d.rw), reinterpret_cast<const int16_t *>(a.tables + d.tw), res, L, fl.xmove, lane);
       vit = __builtin_amdgcn_readfirstlane(vit);
@@ -220,7 +277,7 @@ template <int Q> __global__ __launch_bounds__(256) void filter_kernel(FilterArgs
   }
   if (lane == 0) {
     a.stage[out] = (uint8_t)stage;
-    if (a.bias_nats) a.bias_nats[out] = 0.f;
+    if (a.bias_nats) a.bias_nats[out] = bias_nats;
     if (a.msv_raw) a.msv_raw[out] = msv;
     if (a.vit_raw) a.vit_raw[out] = vit;
   }
@@ -234,7 +291,7 @@ struct ClampedSeq {
 };
 
 // ---- models beyond the register classes: the scalar cores, one lane per pair, rows in HBM (lane-interleaved) --------
-__global__ __launch_bounds__(64) void filter_hbm_kernel(FilterArgs a) {
+__global__ __launch_bounds__(64) void filter_hbm_kernel(KArgs a) {
   const long long lanes = a.q1 - a.q0;
   const long long t = (long long)blockIdx.x * 64 + threadIdx.x;
   if (t >= lanes) return;
@@ -246,15 +303,27 @@ __global__ __launch_bounds__(64) void filter_hbm_kernel(FilterArgs a) {
   const int L = (int)(a.offsets[q + 1] - o0);
   const long long out = q * a.H + a.h;
   int stage = 0, msv = 0, vit = kVitNotRun;
+  float bias_nats = 0.f;
   if (L > a.lmax) stage = kStageBadLen;
   else if (L > 0) {
-    const FilterLen fl = a.lens[L];
+    FilterLen fl = a.lens[L];
     const ClampedSeq seq{a.residues + o0 - 1, d.Kp - 1};
     const CalibMSVPar mp{(uint8_t)d.base_b, (uint8_t)d.bias_b, (uint8_t)d.tbm, (uint8_t)d.tec, fl.tjb};
     const CalibRow<uint8_t> b0{a.ws + t, S};
     msv = calib_msv_core(M, mp, a.tables + d.rb, seq, L, b0, b0.plus(W));
     bool run_vit = false;
+#if !WH_FILTER_BIAS
     stage = filter_stage12(msv, fl, d.base_b, d.scale_b, d.thr, &run_vit);
+#else
+    float usc;
+    if (filter_stage1(msv, fl, d.base_b, d.scale_b, d.thr, &usc)) {
+      const FilterBias *bm = a.bias + a.h;
+      const float filtersc = filter_bias_score(bm->eo1, bm->t10, bm->t11, a.blens[L], seq, L);
+      stage = filter_stage2_bias(usc, filtersc, d.thr, &run_vit);
+      bias_nats = filtersc - fl.nullsc;
+      fl.nullsc = filtersc;
+    }
+#endif
     if (run_vit) {
       const CalibVitPar vp{(int16_t)d.base_w, (int16_t)d.xE_loop, (int16_t)d.xE_move, fl.xmove};
       const CalibRow<int16_t> w0{reinterpret_cast<int16_t *>(a.ws + 2 * W * S) + t, S};
@@ -264,11 +333,12 @@ __global__ __launch_bounds__(64) void filter_hbm_kernel(FilterArgs a) {
     }
   }
   a.stage[out] = (uint8_t)stage;
-  if (a.bias_nats) a.bias_nats[out] = 0.f;
+  if (a.bias_nats) a.bias_nats[out] = bias_nats;
   if (a.msv_raw) a.msv_raw[out] = msv;
   if (a.vit_raw) a.vit_raw[out] = vit;
 }
 
+#if !WH_FILTER_BIAS
 __global__ __launch_bounds__(256) void filter_count_kernel(const uint8_t *stage, long long n, unsigned long long *counts) {
   unsigned c1 = 0, c2 = 0, c3 = 0;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
@@ -284,7 +354,9 @@ __global__ __launch_bounds__(256) void filter_count_kernel(const uint8_t *stage,
   if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&counts[0], (unsigned long long)n);
 }
 
-template <int Q> int launch_q(const FilterArgs &a, long long npairs, hipStream_t s) {
+#endif
+
+template <int Q> int launch_q(const KArgs &a, long long npairs, hipStream_t s) {
   const long long blocks = (npairs + 3) / 4;
   hipLaunchKernelGGL(filter_kernel<Q>, dim3((unsigned)blocks), dim3(256), 0, s, a, npairs);
   return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -292,7 +364,12 @@ template <int Q> int launch_q(const FilterArgs &a, long long npairs, hipStream_t
 
 }  // namespace
 
-int launch_filter_class(int cls, const FilterArgs &a, long long npairs, void *stream) {
+#if WH_FILTER_BIAS
+#define launch_filter_class launch_filter_class_bias
+#define launch_filter_hbm launch_filter_hbm_bias
+#endif
+
+int launch_filter_class(int cls, const KArgs &a, long long npairs, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   if (npairs <= 0) return 0;
   if ((npairs + 3) / 4 > 0x7FFFFFFFll) return -1;
@@ -307,18 +384,20 @@ int launch_filter_class(int cls, const FilterArgs &a, long long npairs, void *st
   return -1;
 }
 
-int launch_filter_hbm(const FilterArgs &a, void *stream) {
+int launch_filter_hbm(const KArgs &a, void *stream) {
   const long long lanes = a.q1 - a.q0;
   if (lanes <= 0) return 0;
   hipLaunchKernelGGL(filter_hbm_kernel, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+#if !WH_FILTER_BIAS
 int launch_filter_count(const uint8_t *stage, long long n, unsigned long long *counts, void *stream) {
   if (n <= 0) return 0;
   const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
   hipLaunchKernelGGL(filter_count_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, stage, n, counts);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+#endif
 
 }  // namespace whf

@@ -135,7 +135,14 @@ int parse_hmm_file(const std::string &path, HostHMM &h) {
   };
   if (!next_tokens(f, tok)) return bad("transition header", 0);
   if (!next_tokens(f, tok)) return bad("node 0", 0);
-  if (!tok.empty() && tok[0] == "COMPO") { if (!next_tokens(f, tok)) return bad("node 0", 0); }
+  if (!tok.empty() && tok[0] == "COMPO") {
+    if ((int)tok.size() >= K + 1) {      // (a short line counts as none)
+      h.compo.resize((size_t)K);
+      for (int x = 0; x < K; x++) h.compo[(size_t)x] = tok_probf(tok[1 + x]);
+      h.has_compo = true;
+    }
+    if (!next_tokens(f, tok)) return bad("node 0", 0);
+  }
   // tok = node-0 insert emissions (insert odds are hardwired to 1 by the profile: ignored)
   if (!next_tokens(f, tok) || tok.size() < 7) return bad("node-0 transitions", 0);
   for (int x = 0; x < 7; x++) { h.t[x] = tok_prob(tok[x]); h.tf[x] = tok_probf(tok[x]); }
@@ -147,6 +154,7 @@ int parse_hmm_file(const std::string &path, HostHMM &h) {
     if (!next_tokens(f, tok) || tok.size() < 7) return bad("transition line", k);
     for (int x = 0; x < 7; x++) { h.t[(size_t)k * 7 + x] = tok_prob(tok[x]); h.tf[(size_t)k * 7 + x] = tok_probf(tok[x]); }
   }
+  if (!h.has_compo) h.compo.assign((size_t)K, 0.f);
   configure_profile(h);
   return WH_OK;
 }

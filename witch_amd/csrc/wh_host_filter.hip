@@ -18,6 +18,11 @@ struct FilterState {
   size_t list_off[kFilterClasses] = {0, 0, 0, 0, 0, 0};
   DevBuf d_tables, d_desc, d_lens, d_list, d_ws, d_counts;
   size_t lens_on_device = 0;
+  // the bias filter: per model (uploaded with the tables), per length (uploaded by the first call that runs the stage)
+  std::vector<FilterBias> bias;
+  std::vector<FilterBiasLen> blens;
+  DevBuf d_biasm, d_blens;
+  size_t blens_on_device = 0;
   int64_t handed = 0;                        // wh_score_filtered: pairs handed to the scoring kernels
   bool scored = false;                       // the last filtering call was wh_score_filtered
   // wh_score_filtered: stage / bias of the call, the kept queries, the compacted batch and its results
@@ -37,6 +42,10 @@ int options_of(const wh_filter_opts *o, FilterOpts &fo, const char *what) {
   if (o) { fo.F1 = o->F1; fo.F2 = o->F2; fo.F3 = o->F3; fo.nobias = o->nobias; }
   if (!fo.nobias) {
     set_error("%s: the bias filter is not implemented; filtered search needs nobias = 1 (hmmsearch --nobias)", what);
+    return WH_EINVAL;
+  }
+  if (fo.nobias != 1 && fo.nobias != WH_BIAS_FILTER_ON) {
+    set_error("%s: nobias = %d is neither 1 (hmmsearch --nobias) nor WH_BIAS_FILTER_ON", what, fo.nobias);
     return WH_EINVAL;
   }
   if (!(fo.F1 == fo.F1) || !(fo.F2 == fo.F2) || !(fo.F3 == fo.F3)) { set_error("%s: a threshold is not a number", what); return WH_EINVAL; }
@@ -59,11 +68,13 @@ int state_of(wh_ehmm *e, FilterState **out) {
   const int H = (int)e->hmms.size();
   f->models.resize((size_t)H);
   f->desc.resize((size_t)H);
+  f->bias.resize((size_t)H);
   std::vector<unsigned char> tab;
   for (int h = 0; h < H; h++) {
     FilterModel &fm = f->models[(size_t)h];
     const int rc = model_of(e->hmms[(size_t)h], e->degen, fm);
     if (rc) return rc;
+    f->bias[(size_t)h] = fm.bias;
     FilterDevModel &d = f->desc[(size_t)h];
     memset(&d, 0, sizeof d);
     const int M = fm.M, Kp = fm.Kp, cls = filter_class(M);
@@ -98,9 +109,10 @@ int state_of(wh_ehmm *e, FilterState **out) {
   std::vector<int> all;
   for (int c = 0; c < kFilterClasses; c++) { f->list_off[c] = all.size(); all.insert(all.end(), f->lists[c].begin(), f->lists[c].end()); }
   if (f->d_tables.ensure(tab.size() + 16) || f->d_desc.ensure(sizeof(FilterDevModel) * (size_t)H) || f->d_list.ensure(sizeof(int) * (all.size() + 1)) ||
-      f->d_counts.ensure(8 * sizeof(unsigned long long)))
+      f->d_counts.ensure(8 * sizeof(unsigned long long)) || f->d_biasm.ensure(sizeof(FilterBias) * (size_t)H))
     return WH_ENOMEM;
   if (hipMemcpy(f->d_tables.p, tab.data(), tab.size(), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(f->d_biasm.p, f->bias.data(), sizeof(FilterBias) * (size_t)H, hipMemcpyHostToDevice) != hipSuccess ||
       (all.size() && hipMemcpy(f->d_list.p, all.data(), sizeof(int) * all.size(), hipMemcpyHostToDevice) != hipSuccess)) {
     set_error("wh_filter: uploading the filter tables failed");
     return WH_EHIP;
@@ -183,9 +195,20 @@ int run_filters(wh_ehmm *e, FilterState *f, const FilterOpts &fo, const uint8_t 
     HIPCHK(hipMemcpy(f->d_lens.p, f->lens.data(), sizeof(FilterLen) * f->lens.size(), hipMemcpyHostToDevice));
     f->lens_on_device = f->lens.size();
   }
+  // the bias filter's per-length records, to the same length as the others: only for a call that runs the stage
+  const bool bias = fo.bias();
+  if (bias && f->blens_on_device < f->lens_on_device) {
+    const size_t old = f->blens.size();
+    f->blens.resize(f->lens_on_device);
+    for (size_t L = old; L < f->blens.size(); L++) f->blens[L] = filter_bias_len((int)std::max<size_t>(L, 1));
+    HIPCHK(hipStreamSynchronize(s));
+    if (f->d_blens.ensure(sizeof(FilterBiasLen) * f->blens.size())) return WH_ENOMEM;
+    HIPCHK(hipMemcpy(f->d_blens.p, f->blens.data(), sizeof(FilterBiasLen) * f->blens.size(), hipMemcpyHostToDevice));
+    f->blens_on_device = f->blens.size();
+  }
   for (int h = 0; h < H; h++) f->desc[(size_t)h].thr = filter_thresholds(f->models[(size_t)h].evp, fo);
   HIPCHK(hipMemcpyAsync(f->d_desc.p, f->desc.data(), sizeof(FilterDevModel) * (size_t)H, hipMemcpyHostToDevice, s));
-  FilterArgs a;
+  FilterBiasArgs a;
   memset(&a, 0, sizeof a);
   a.models = (const FilterDevModel *)f->d_desc.p;
   a.tables = (const unsigned char *)f->d_tables.p;
@@ -193,10 +216,12 @@ int run_filters(wh_ehmm *e, FilterState *f, const FilterOpts &fo, const uint8_t 
   a.lmax = (int)f->lens_on_device - 1;
   a.residues = d_res; a.offsets = (const long long *)d_off; a.nq = nq; a.H = H;
   a.stage = d_stage; a.bias_nats = d_bias; a.msv_raw = d_msv; a.vit_raw = d_vit;
+  a.bias = (const FilterBias *)f->d_biasm.p; a.blens = (const FilterBiasLen *)f->d_blens.p;
   for (int c = 0; c < kFilterClasses; c++) {
     if (f->lists[c].empty()) continue;
     a.list = (const int *)f->d_list.p + f->list_off[c];
-    if (launch_filter_class(c, a, (long long)nq * (long long)f->lists[c].size(), s)) { set_error("wh_filter: launching the filter kernel failed: %s", hipGetErrorString(hipGetLastError())); return WH_EHIP; }
+    const long long np = (long long)nq * (long long)f->lists[c].size();
+    if (bias ? launch_filter_class_bias(c, a, np, s) : launch_filter_class(c, a, np, s)) { set_error("wh_filter: launching the filter kernel failed: %s", hipGetErrorString(hipGetLastError())); return WH_EHIP; }
   }
   // models beyond the register classes: one lane per pair, rows in HBM, in chunks of queries that fit the row budget
   for (int h : f->big) {
@@ -208,7 +233,7 @@ int run_filters(wh_ehmm *e, FilterState *f, const FilterOpts &fo, const uint8_t 
     if (f->d_ws.ensure((size_t)lanes * per_lane + 16)) return WH_ENOMEM;
     for (int64_t q0 = 0; q0 < nq; q0 += lanes) {
       a.ws = (unsigned char *)f->d_ws.p; a.q0 = q0; a.q1 = std::min(nq, q0 + lanes); a.h = h;
-      if (launch_filter_hbm(a, s)) { set_error("wh_filter: launching the long-model filter kernel failed: %s", hipGetErrorString(hipGetLastError())); return WH_EHIP; }
+      if (bias ? launch_filter_hbm_bias(a, s) : launch_filter_hbm(a, s)) { set_error("wh_filter: launching the long-model filter kernel failed: %s", hipGetErrorString(hipGetLastError())); return WH_EHIP; }
     }
   }
   HIPCHK(hipMemsetAsync(f->d_counts.p, 0, 8 * sizeof(unsigned long long), s));
@@ -285,7 +310,7 @@ int wh_filter_host(const char *const *hmm_paths, int n, const uint8_t *residues,
   int64_t c[4] = {nq * n, 0, 0, 0};
   for (int64_t q = 0; q < nq; q++)
     for (int h = 0; h < n; h++) {
-      const FilterPairOut r = filter_pair_host(models[(size_t)h], thr[(size_t)h], residues + offsets[q], (int)(offsets[q + 1] - offsets[q]), rows.data());
+      const FilterPairOut r = filter_pair_host(models[(size_t)h], thr[(size_t)h], residues + offsets[q], (int)(offsets[q + 1] - offsets[q]), rows.data(), fo.bias());
       const size_t p = (size_t)q * n + h;
       stage[p] = (uint8_t)r.stage;
       if (filter_bias_nats) filter_bias_nats[p] = r.bias_nats;
@@ -386,6 +411,20 @@ int wh_score_filtered(wh_ehmm *e, const uint8_t *residues, const int64_t *offset
   uint8_t *d_stage = st.out(stage, np);
   if (st.rc) return st.rc;
   return st.finish(wh_score_filtered_dev(e, d_res, d_off, nq, total, max_query_len(offsets, nq), opts, d_deci, d_flags, d_fwd, d_det, d_stage, nullptr));
+}
+
+/* test hook: how many float32 bit patterns in [first, last] have filter_log(x) != (float) log((double) x) of the host's libm */
+int64_t wh_filter_log_differences(uint32_t first, uint32_t last) {
+  int64_t n = 0;
+  for (uint64_t u = first; u <= last; u++) {
+    const uint32_t b = (uint32_t)u;
+    float x, a, c;
+    memcpy(&x, &b, 4);
+    a = filter_log(x);
+    c = (float)std::log((double)x);
+    n += memcmp(&a, &c, 4) != 0;
+  }
+  return n;
 }
 
 int wh_last_filter_counts(wh_ehmm *e, int64_t out[6]) {

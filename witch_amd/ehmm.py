@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import DOMAIN_FIELDS, FilterOpts, PairDetail, WitchHipError, check, lib
+from ._lib import BIAS_FILTER_ON, DOMAIN_FIELDS, FilterOpts, PairDetail, WitchHipError, check, lib
 
 
 def pack_queries(seqs):
@@ -203,22 +203,27 @@ class EHMM:
         return int(n)
 
     @staticmethod
-    def filter_opts(filters=True, nobias=False) -> FilterOpts:
-        """wh_filter_opts from filters = True (HMMER's defaults F1 = 0.02, F2 = 1e-3, F3 = 1e-5) or (F1, F2, F3)."""
+    def filter_opts(filters=True, nobias=False, bias=False) -> FilterOpts:
+        """wh_filter_opts from filters = True (HMMER's defaults F1 = 0.02, F2 = 1e-3, F3 = 1e-5) or (F1, F2, F3).
+        bias=True: HMMER's bias filter runs (WH_BIAS_FILTER_ON; opt-in for now, the default later); nobias=True: it does
+        not (hmmsearch --nobias); neither: the library refuses the call; both: ValueError."""
         F = (0.02, 1e-3, 1e-5) if filters is True else tuple(float(x) for x in filters)
         if len(F) != 3:
             raise ValueError("filters: True or (F1, F2, F3)")
-        return FilterOpts(F[0], F[1], F[2], 1 if nobias else 0)
+        if bias and nobias:
+            raise ValueError("bias=True (the bias filter runs) and nobias=True (hmmsearch --nobias) exclude each other")
+        return FilterOpts(F[0], F[1], F[2], BIAS_FILTER_ON if bias else 1 if nobias else 0)
 
-    def filter(self, residues, offsets, filters=True, nobias=False, want_raw=False):
+    def filter(self, residues, offsets, filters=True, nobias=False, want_raw=False, bias=False):
         """hmmsearch's acceleration filters over every (query, model) pair (include/witch_hip.h: wh_filter): stage uint8
         [nq, H] (bit 0 passed MSV, 1 passed bias, 2 passed Viterbi, 3 the Viterbi sweep ran) and filter_bias_nats float32
-        [nq, H]; with want_raw also the two filters' raw integer scores, int32 [nq, H] each.  The bias filter is not
-        implemented: nobias=False is refused (WitchHipError), as hmmsearch without --nobias is by the level-0 program."""
+        [nq, H]; with want_raw also the two filters' raw integer scores, int32 [nq, H] each.  The bias filter is an
+        opt-in: bias=True runs it; without it nobias=False is still refused (WitchHipError), as hmmsearch without --nobias
+        is by the level-0 program unless its server is told to run the stage."""
         residues = np.ascontiguousarray(residues, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         nq = len(offsets) - 1
-        o = self.filter_opts(filters, nobias)
+        o = self.filter_opts(filters, nobias, bias)
         stage = np.zeros((nq, self.H), dtype=np.uint8)
         bias = np.zeros((nq, self.H), dtype=np.float32)
         msv = np.zeros((nq, self.H), dtype=np.int32) if want_raw else None
@@ -235,10 +240,10 @@ class EHMM:
         check(lib().wh_last_filter_counts(self._h, c.ctypes.data), "wh_last_filter_counts")
         return dict(zip(("pairs", "msv", "bias", "vit", "fwd", "scored"), (int(v) for v in c)))
 
-    def score(self, residues, offsets, want_fwd=False, want_detail=False, filters=None, nobias=False, want_stage=False):
+    def score(self, residues, offsets, want_fwd=False, want_detail=False, filters=None, nobias=False, want_stage=False, bias=False):
         """filters=None: hmmsearch --max, as ever.  filters=True or (F1, F2, F3): behind hmmsearch's acceleration filters
         (wh_score_filtered): a pair that a stage rejects comes back with FLAG_FILTERED and without FLAG_REPORTED;
-        want_stage appends the stage bytes [nq, H]."""
+        want_stage appends the stage bytes [nq, H].  bias=True: with HMMER's bias filter (filter_opts)."""
         residues = np.ascontiguousarray(residues, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         nq = len(offsets) - 1
@@ -248,13 +253,13 @@ class EHMM:
         det = (PairDetail * (nq * self.H))() if want_detail else None
         stage = np.zeros((nq, self.H), dtype=np.uint8) if want_stage else None
         if filters is None or filters is False:
-            if nobias or want_stage:
-                raise ValueError("nobias / want_stage belong to a filtered call (filters=True or (F1, F2, F3))")
+            if nobias or want_stage or bias:
+                raise ValueError("nobias / bias / want_stage belong to a filtered call (filters=True or (F1, F2, F3))")
             check(lib().wh_score(self._h, residues.ctypes.data, offsets.ctypes.data, nq, deci.ctypes.data,
                                  flags.ctypes.data, None if fwd is None else fwd.ctypes.data,
                                  None if det is None else C.addressof(det)), "wh_score")
         else:
-            o = self.filter_opts(filters, nobias)
+            o = self.filter_opts(filters, nobias, bias)
             check(lib().wh_score_filtered(self._h, residues.ctypes.data, offsets.ctypes.data, nq, C.byref(o), deci.ctypes.data,
                                           flags.ctypes.data, None if fwd is None else fwd.ctypes.data,
                                           None if det is None else C.addressof(det),

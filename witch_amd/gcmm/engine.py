@@ -79,7 +79,7 @@ class QueryAlignmentEngine:
     def run(cls, index_to_hmm, unaligned, num_hmms: int, device: int = 0, multidomain_policy: str = "resolve",
             subset_to_retained_columns=None, subset_to_nongaps_per_column=None, backbone_length=None,
             world: int = 1, rank: int = 0, group=None, chunk: int = 20000, keep_scores: bool = True, filters=False,
-            nobias: bool = False):
+            nobias: bool = False, bias: bool = False):
         """Score, weight and align every query of ``unaligned`` ({taxon: sequence text} or a list of
         (taxon, text)) against every HMM of ``index_to_hmm``.
 
@@ -97,9 +97,9 @@ class QueryAlignmentEngine:
         ``filters``: the reference's ``self.filters`` (algorithm.py:526-532: hmmsearch without --max).  False: every pair
         is scored, as hmmsearch --max does.  True or (F1, F2, F3): hmmsearch's MSV, Viterbi and Forward filters run in
         front of the scoring kernels (EHMM.score(filters=...)); a pair a stage rejects is not reported, as it has no line
-        in hmmsearch's table.  HMMER's bias filter is not implemented, and a filtered run never drops the stage silently:
-        the caller says ``nobias=True`` (the run is then that of hmmsearch --nobias, NOT of the reference's filtered
-        command line, which keeps the bias stage); without it a filtered run is refused (WitchHipError), like EHMM.score.
+        in hmmsearch's table.  HMMER's bias filter is an opt-in (the default later): ``bias=True`` runs it, which is the
+        reference's filtered command line; ``nobias=True`` is hmmsearch --nobias; both together are a ValueError, and a
+        filtered run never drops the stage silently: with neither it is refused (WitchHipError), like EHMM.score.
         ``self.filter_counts`` sums the stage counts of the chunks."""
         import time
         import warnings
@@ -158,7 +158,7 @@ class QueryAlignmentEngine:
             if filters is False or filters is None:
                 deci, flags = e.score(cres, coffs)
             else:
-                deci, flags = e.score(cres, coffs, filters=filters, nobias=nobias)
+                deci, flags = e.score(cres, coffs, filters=filters, nobias=nobias, bias=bias)
                 for k_, v_ in e.last_filter_counts().items():
                     self.filter_counts[k_] = self.filter_counts.get(k_, 0) + v_
             self.long_list_pairs += e.last_long_list_pairs()

@@ -87,12 +87,19 @@ def filter_thresholds(opts):
     return tuple(F)
 
 
+def bias_filter_enabled():
+    """WITCH_HIP_BIAS_FILTER=1 in the server's environment: HMMER's bias filter runs for a filtered search without
+    --nobias (WITCH's own filtered command line).  An opt-in for now; it becomes the default later."""
+    return os.environ.get("WITCH_HIP_BIAS_FILTER", "") == "1"
+
+
 def check_hmmsearch_options(opts):
     """The GPU path computes what WITCH's own command lines ask for (algorithm.py:526-532): a reporting threshold that
     lets every hit through, and either `--max` (no filters) or the filtered search of WITCH's `filters` switch - the MSV,
     Viterbi and Forward stages at --F1 --F2 --F3 (HMMER's defaults 0.02, 1e-3, 1e-5; wh_score_filtered).  ONE gap remains:
     the bias filter is not implemented, so a filtered search must say --nobias; plain filtered search (no --max, no
-    --nobias) is refused with a message that says exactly this.  With --max the four options are ignored, as in HMMER.
+    --nobias) is refused with a message that says exactly this - unless the server's environment has
+    WITCH_HIP_BIAS_FILTER=1: the bias filter then runs (bias_filter_enabled).  With --max the four options are ignored, as in HMMER.
     Anything else that would change the reported set in HMMER (a real E-value / score cut-off, no null2) is refused
     with exit status 1 instead of being silently ignored.
     --domtblout FILE is written (per-domain records of wh_domains; --domE, -Z and --domZ apply to it and to the
@@ -104,7 +111,7 @@ def check_hmmsearch_options(opts):
     Two things stay unimplemented and are accepted as no-ops: --tblout (its exp,
     clu and ov columns need counts the scoring kernels do not export) and the alignment display (the output is always
     that of --noali)."""
-    if "--max" not in opts and "--nobias" not in opts:
+    if "--max" not in opts and "--nobias" not in opts and not bias_filter_enabled():
         raise ArgError("witch-hip hmmsearch shim: the filtered search is implemented without HMMER's bias filter only: "
                        "pass --nobias (MSV, Viterbi and Forward filters at --F1 --F2 --F3), or --max (no filters; "
                        "WITCH passes --max unless its filters are switched on)")
@@ -192,24 +199,24 @@ class GpuBackend:
             self.cache.move_to_end(rp)
         return hit[1], hit[2]
 
-    def search(self, hmm_path, records, want_domains=False, filters=None):
+    def search(self, hmm_path, records, want_domains=False, filters=None, bias=False):
         """records: [(name, text)] -> (header, [(name, bits, bias_bits, n_domains)] of reported sequences); with
         want_domains also {name: [domain records]}: the fields of wh_domain (EHMM.domains) and the envelope's envsc.
         The domains cost an alignment per envelope: only a caller that prints them asks for them.
         filters=(F1, F2, F3): behind hmmsearch's acceleration filters (without the bias filter: --nobias); the stage
-        counts of the search are then in self.last_passed (n MSV, n bias, n Vit, n Fwd)."""
-        hdr, rows, domains, _ = self._search(hmm_path, records, want_domains, filters, None)
+        counts of the search are then in self.last_passed (n MSV, n bias, n Vit, n Fwd).  bias=True: with the bias filter."""
+        hdr, rows, domains, _ = self._search(hmm_path, records, want_domains, filters, None, bias)
         return (hdr, rows, domains) if want_domains else (hdr, rows)
 
-    def search_hits(self, hmm_path, records, inc, want_domains=False, filters=None):
+    def search_hits(self, hmm_path, records, inc, want_domains=False, filters=None, bias=False):
         """search() for hmmsearch -A: (header, rows, domains or None, hits) - hits is EHMM.hits_msa's dict, the alignment of
         every domain that satisfies the inclusion thresholds, its rows in HMMER's hit order (formats.hit_order) and domain
         order.  inc: {"incE", "incdomE", "Z", "domZ"} (Z / domZ None: the number of targets / of reported sequences).  The
         rows carry the unrounded score as the tables of --domtblout do.  With want_domains the domain records come from the
         same alignment of the envelopes (wh_hits_msa hands them back): one domain stage serves --domtblout and -A."""
-        return self._search(hmm_path, records, want_domains, filters, inc)
+        return self._search(hmm_path, records, want_domains, filters, inc, bias)
 
-    def _search(self, hmm_path, records, want_domains, filters, inc):
+    def _search(self, hmm_path, records, want_domains, filters, inc, bias=False):
         from witch_amd.ehmm import pack_queries
         domains, hits = {}, None
         with self.lock:
@@ -219,7 +226,7 @@ class GpuBackend:
             if filters is None:
                 deci, flags, det = e.score(res, offs, want_detail=True)
             else:
-                deci, flags, det = e.score(res, offs, want_detail=True, filters=filters, nobias=True)
+                deci, flags, det = e.score(res, offs, want_detail=True, filters=filters, nobias=not bias, bias=bias)
                 c = e.last_filter_counts()
                 self.last_passed = (c["msv"], c["bias"], c["vit"], c["fwd"])
             exact = want_domains or inc is not None
@@ -348,6 +355,8 @@ class Server:
         check_hmmsearch_options(opts)
         F = filter_thresholds(opts)
         fkw = {} if F is None else {"filters": F}           # (a search with --max calls the backend as ever)
+        if F is not None and "--nobias" not in opts:        # (accepted above only where the bias filter is switched on)
+            fkw["bias"] = True
         passed = lambda: None if F is None else (self.backend.last_passed, F)
         if "-A" in opts:
             return self.run_hmmsearch_hits(opts, hmm, fa, cwd, fkw, passed)
