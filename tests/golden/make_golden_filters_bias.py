@@ -17,6 +17,9 @@ Stored under tests/golden/filters_bias/<case>.json.gz:
              run over ALL queries, "counts_nobias" the same with --nobias
   per model and query: "out" {"default": [4 x 0/1], "alt": [...]}, "T1", "Tb", "T2b", "T3b"
 Only program output and these settings are stored.
+
+classes_dna, classes_amino: the seeded models and the queries of make_golden_filters.py's fixtures of these names (one
+model per size class of wh_filter.hip, tests/filters_classes_common.py), with the same records per pair.
 """
 import gzip
 import json
@@ -32,7 +35,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 from tests.conftest import load_case  # noqa: E402
-from make_golden_filters import ALT, DEFAULT, LN_LO, MAX_SKIP, bisect, degenerate_copies, low_complexity, run, stats_of  # noqa: E402
+from make_golden_filters import ALT, DEFAULT, LN_LO, MAX_SKIP, bisect, classes_setup, degenerate_copies, low_complexity, run, stats_of, write_fasta  # noqa: E402
+from tests.filters_classes_common import CLASSES  # noqa: E402
 
 OUT = os.path.join(HERE, "filters_bias")
 
@@ -85,10 +89,42 @@ CASES = {
 }
 
 
+def main_classes(fname, tmp):
+    """classes_dna, classes_amino: the models and queries of make_golden_filters.py's fixtures of these names, with the
+    bias filter on"""
+    alphabet, shared, todo = classes_setup(fname, tmp)
+    with Pool(8) as pool:
+        flat = pool.map(one_pair, [(hp, s) for _, hp, queries in todo for _, s in queries], chunksize=1)
+    models = []
+    fa_all = os.path.join(tmp, fname + ".fa")
+    for rec, hp, queries in todo:
+        pairs, flat = flat[:len(queries)], flat[len(queries):]
+        write_fasta(fa_all, queries)
+        rec.update({"mu_lambda": stats_of(hp),
+                    "counts": {"default": run(hp, fa_all, DEFAULT, nobias=False), "alt": run(hp, fa_all, ALT, nobias=False)},
+                    "counts_nobias": {"default": run(hp, fa_all, DEFAULT), "alt": run(hp, fa_all, ALT)}, "pairs": pairs})
+        for key in ("default", "alt"):
+            assert [sum(p["out"][key][s] for p in pairs) for s in range(4)] == rec["counts"][key], (fname, rec["M"], rec["variant"], key)
+        models.append(rec)
+    allp = [p for m in models for p in m["pairs"]]
+    for key, F in (("default", DEFAULT), ("alt", ALT)):
+        near = sum(1 for p in allp if any(p[t][0] <= math.log(F[i]) <= p[t][1] and p[t][1] > LN_LO for i, t in enumerate(("Tb", "T2b", "T3b"))))
+        assert near <= MAX_SKIP * len(allp), (fname, key, near)
+    decided = sum(1 for p in allp if p["Tb"][0] > p["T1"][1])
+    path = os.path.join(OUT, fname + ".json.gz")
+    with gzip.GzipFile(path, "wb", mtime=0) as f:
+        f.write(json.dumps({"fixture": fname, "alphabet": alphabet, "shared_queries": shared, "thresholds": {"default": DEFAULT, "alt": ALT},
+                            "ln_lo": LN_LO, "models": models}, separators=(",", ":")).encode())
+    print("%s: %d models, %d pairs, the bias stage's P above the MSV stage's on %d, %d bytes" % (fname, len(models), len(allp), decided, os.path.getsize(path)), flush=True)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     tmp = tempfile.mkdtemp(prefix="golden_filters_bias_")
     only = sys.argv[1:]
+    for fname in CLASSES:
+        if not only or fname in only:
+            main_classes(fname, tmp)
     for fname, (qmake, mlist, must_differ) in CASES.items():
         if only and fname not in only:
             continue

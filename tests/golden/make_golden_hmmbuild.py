@@ -3,8 +3,8 @@
 
 RUNS ONLY IN THE BUILD CONTAINER (needs /root/reference): small hand-shaped alignments through the reference's
 bundled hmmbuild 3.1b2 with the reference's command line (witch_msa/gcmm/algorithm.py:463-470).  Stores ONLY
-data under tests/golden/hmmbuild_cases/: <case>.afa (the input alignment) and <case>.hmm (hmmbuild's output,
-DATE line dropped).  The cases probe what the big golden models do not: fragments (first..last residue span
+data under tests/golden/hmmbuild_cases/ (and hmmbuild_tiny/): <case>.afa (the input alignment) and <case>.hmm
+(hmmbuild's output, DATE line dropped).  The cases probe what the big golden models do not: fragments (first..last residue span
 below / at / above half the alignment), degenerate residues, lower case, '.' gaps, U in DNA, RNA, amino with
 B/Z/X, one sequence, duplicated sequences, all-gap columns, and entropy weighting on a conserved family.
 """
@@ -16,7 +16,8 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HMMER = "/root/reference/witch_msa/tools/magus/tools/hmmer"
-OUT = os.path.join(HERE, "hmmbuild_cases")
+OUT_CASES = os.path.join(HERE, "hmmbuild_cases")
+OUT_TINY = os.path.join(HERE, "hmmbuild_tiny")
 
 
 def hmmbuild(mol, hmm, afa):
@@ -38,7 +39,7 @@ def family(rng, alphabet, n, L, sub):
 
 
 def main():
-    os.makedirs(OUT, exist_ok=True)
+    os.makedirs(OUT_CASES, exist_ok=True)
     rng = np.random.default_rng(20251301)
     cases = {}
     # 1. fragments: alen 40; spans 19 (fragment), 20 (exactly half: not < 0.5 alen), 21, full
@@ -111,7 +112,14 @@ def main():
         if all(c == "-" for r in rows for c in r[:1]):
             rows[0][0] = alpha[mol][0]
         cases["random_%02d_%s" % (t, mol)] = (mol, rows)
-    for name, (mol, rows) in cases.items():
+    # 9. one and two nodes, kept in a folder of their own (hmmbuild_tiny: the tests that walk hmmbuild_cases stay as they
+    #    are).  Of the 200 random sequences that calibrate the MSV filter a good share holds no W (no W or C): no residue
+    #    scores 0 or better on any node, and the filter's score is the empty diagonal's (wh_calibrate.h, calib_msv_floor) -
+    #    which moves the printed MSV mu by 2.0 and 1.7 bits
+    tiny = {"amino_w1": ("amino", [["W"]] * 4), "amino_wc2": ("amino", [list("WC")] * 4)}
+    os.makedirs(OUT_TINY, exist_ok=True)
+    for name, (mol, rows) in list(cases.items()) + list(tiny.items()):
+        OUT = OUT_TINY if name in tiny else OUT_CASES
         afa = os.path.join(OUT, name + ".afa")
         with open(afa, "w") as f:
             for i, r in enumerate(rows):

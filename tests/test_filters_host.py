@@ -2,8 +2,10 @@
 of the reference's bundled hmmsearch (tests/golden/filters, written by tests/golden/make_golden_filters.py), its error
 paths, and the level-0 hmmsearch's filtered command line.
 
-The bias filter is not implemented: the fixtures' outcomes are those of hmmsearch --nobias, and
-the bias tests of the fixtures ("Tb", "bias_nats", "counts_bias") have no test here."""
+These fixtures' outcomes are those of hmmsearch --nobias.  The bias filter is an explicit opt-in (WH_BIAS_FILTER_ON,
+DESIGN.md section 4.11) with fixtures and tests of its own (tests/golden/filters_bias, tests/test_filters_bias_host.py, which
+also reads the "Tb" and "bias_nats" recorded here); what is tested below is that nobias = 0 stays refused.  Models at
+every size class of wh_filter.hip: tests/test_filters_classes_host.py."""
 import os
 
 import numpy as np

@@ -90,6 +90,21 @@ def test_edge_cases_against_hmmbuild(case):
     assert text2.splitlines().index(stats_lines(text2)[0]) == [l.split()[0] for l in text2.splitlines()].index("CKSUM") + 1
 
 
+@pytest.mark.parametrize("case", ["amino_w1", "amino_wc2"])
+def test_calibration_of_one_and_two_nodes_scores_the_empty_diagonal(case):
+    """Models of one node (W) and two (WC): a good share of the 200 random sequences that calibrate the MSV filter holds
+    no residue that scores 0 or better on a node, and HMMER's MSV filter then answers with the empty diagonal
+    (wh_calibrate.h, calib_msv_floor).  hmmbuild's printed MSV mu says so: -6.0050 and -5.1735, where a filter that always
+    pays for one residue gives -7.9881 and -6.8797.  The whole file is hmmbuild's, as for every other case."""
+    d = os.path.join(GOLD, "hmmbuild_tiny")
+    rows = [l.strip() for l in open(os.path.join(d, case + ".afa")) if not l.startswith(">")]
+    gold = read(os.path.join(d, case + ".hmm"))
+    text, M, neff = hmmbuild_text(rows, "amino", case, stats=True)
+    assert M == len(rows[0]) <= 2
+    assert stats_lines(text) == stats_lines(gold) and len(stats_lines(gold)) == 3, (case, stats_lines(text), stats_lines(gold))
+    assert_same(text, gold, case)
+
+
 @pytest.mark.parametrize("case,args,mol", [
     ("dna_hmmbuild", ("dna", 11, 120, 32, 8, 0.04, 0.004), "dna"),          # entropy weighting active: Neff 1.9 .. 3.8
     ("amino_hmmbuild", ("amino", 13, 90, 16, 4, 0.08, 0.004), "amino"),      # nine-component mixture prior, Neff ~1

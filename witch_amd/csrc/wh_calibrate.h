@@ -188,9 +188,21 @@ WH_HD inline uint8_t sat_subu8(uint8_t a, uint8_t b) { return a > b ? (uint8_t)(
 // the filter's scalars, as the sweep takes them
 struct CalibMSVPar { uint8_t base, bias, tbm, tec, tjb; };
 
+// The empty diagonal.  HMMER 3.1b2 answers the MSV filter from a single-hit pre-filter over ungapped diagonals wherever
+// that can stand for it, and the pre-filter's best diagonal may be the EMPTY one, worth 0: xE is then xB itself,
+// base - tjb - tbm, where the sweep below always pays for at least one emitted residue.  The two differ only on a query
+// no residue of which scores 0 or better on any node; every other outcome of the pre-filter (a hit that J could extend, an
+// overflow) is the sweep's own.  The pre-filter stands aside where tjb + tbm + tec + bias >= 127 - a condition on the model
+// AND the query's length: the sweep's value is then final.  Read off the bundled hmmsearch alone: the recovered integers of
+// tests/golden/filters/classes_* ("the empty diagonal").  0 where the rule does not apply.
+WH_HD inline int calib_msv_floor(int base, int bias, int tbm, int tec, int tjb) {
+  const int cost = tjb + tbm + tec;
+  return cost + bias >= 127 ? 0 : base - cost;
+}
+
 // The sweep: rb [K][M+1] (any pointer: host memory, LDS, HBM), dsq residues 1 .. L, two rows r0 / r1 of M+1 bytes that
-// it ping-pongs (the loads of row i-1 never alias the stores of row i).  Returns xJ, or -1 where the filter overflows
-// (p7_MSVMu then takes the filter's ceiling: calib_msv_score).
+// it ping-pongs (the loads of row i-1 never alias the stores of row i).  Returns xJ - at least the empty diagonal's
+// (calib_msv_floor) -, or -1 where the filter overflows (p7_MSVMu then takes the filter's ceiling: calib_msv_score).
 template <class Tab, class Seq, class Row>
 WH_HD inline int calib_msv_core(int M, CalibMSVPar om, Tab rb, Seq dsq, int L, Row r0, Row r1) {
   for (int k = 0; k <= M; k++) r0.set(k, 0);
@@ -221,7 +233,7 @@ WH_HD inline int calib_msv_core(int M, CalibMSVPar om, Tab rb, Seq dsq, int L, R
     xB = sat_subu8(xB, tjbm);
     const Row t = r0; r0 = r1; r1 = t;
   }
-  return (int)xJ;
+  return calib_max((int)xJ, calib_msv_floor(om.base, om.bias, om.tbm, om.tec, om.tjb));
 }
 
 // score in nats; overflow returns the filter's ceiling like p7_MSVMu does

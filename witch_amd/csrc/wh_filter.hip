@@ -129,7 +129,7 @@ template <int Q> __device__ int msv_sweep(const FilterDevModel &d, const unsigne
       xB = max(max(base, xJ) - tjbm, 0);
     }
   }
-  return xJ;
+  return max(xJ, calib_msv_floor(base, bias, d.tbm, tec, tjb));      // the empty diagonal (wh_calibrate.h)
 }
 
 // ---- Viterbi filter: calib_viterbi_core's values ---------------------------------------------------------------------
