@@ -20,6 +20,8 @@
  *                     users of the hmmsearch program the library replaces
  *   wh_hits_msa*   <- "hmmsearch -A FILE": the alignment of all domains that satisfy the inclusion thresholds (HMMER's
  *                     p7_tophits_Alignment); no reference code asks for it either
+ *   wh_seq_table*  <- "hmmsearch --tblout FILE": the per-sequence table (HMMER's p7_tophits_TabularTargets), its exp, reg and
+ *                     clu columns from wh_seq_expect*; no reference code asks for it either
  *
  * Conventions: plain pointers and sizes; the caller owns every input and output
  * buffer; the library owns wh_ehmm handles and its device workspace.  Functions
@@ -596,6 +598,69 @@ int wh_hits_msa_dev(wh_ehmm *e, const uint8_t *d_text, const int64_t *d_offsets,
                     const int32_t *d_cols, const float *d_pp, int32_t h, const int32_t *d_order, const wh_hits_opts *opts,
                     int32_t msa_flags, int64_t *out_nrows, wh_hit_row **out_rows_rec, int64_t *out_W, uint8_t **out_rows,
                     uint8_t **out_pp_rows, uint8_t **out_pp_cons, uint8_t **out_rf, int32_t **out_matmap, void *stream);
+
+/* ---- hmmsearch --tblout: the per-sequence table -------------------------------------------------------------------------
+ * Three of its columns are counts of HMMER's domain definition that the scoring kernels do not export: exp, the expected
+ * number of domains (the B state's posterior occupancy summed over the sequence, btot[L]); reg, the regions of the
+ * rt1 = 0.25 / rt2 = 0.10 scan; clu, how many of them met the multidomain test (rt3 = 0.20) and went to stochastic clustering.
+ * wh_seq_expect[_dev] recomputes the two full-width multihit sweeps they come from for the pairs of pair_list alone
+ * (pair_list[t] = q * H + h, any order, a pair may repeat): out[t] = { exp, reg, clu }.  One wavefront per pair, float32 in
+ * HMMER's arithmetic for models of up to 3 072 nodes (the DP row in registers, the special states of every row in a
+ * per-wave HBM workspace sized from max_len: no limit on the query length); longer models: float64, the row in HBM.  A pair
+ * whose Forward score is not finite, or an empty query: { 0, 0, 0 }.  The _dev variant reads the pair list back (it waits
+ * for the stream once) to order the work by model.  wh_seq_expect_host: the same sweeps in float64 as plain scalar code
+ * over the n model files - no handle, no HIP call; thresholds and profile construction are the kernels'. */
+typedef struct wh_seq_expect_rec { float exp; int32_t reg, clu; } wh_seq_expect_rec;
+int wh_seq_expect(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_list,
+                  int64_t n_pairs, wh_seq_expect_rec *out);
+int wh_seq_expect_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
+                      int32_t max_len, const int64_t *d_pair_list, int64_t n_pairs, wh_seq_expect_rec *d_out, void *stream);
+int wh_seq_expect_host(const char *const *hmm_paths, int n, const uint8_t *residues, const int64_t *offsets, int64_t nq,
+                       const int64_t *pair_list, int64_t n_pairs, wh_seq_expect_rec *out);
+/* One row per pair with WH_FLAG_REPORTED, in pair order, from the flags and detail records of a scoring call over the same
+ * queries.  Z <= 0: nq; domZ <= 0: the number of reported pairs (as HMMER sets them).  Returns the number of rows (>= 0) or a
+ * negative WH_E* code; WH_ERANGE: more rows than <cap> (nothing is written).
+ *   seq_bits, seq_bias_bits   the sequence's score and bias: detail.seq_score, max(0, pre_score - seq_score)
+ *   seq_lnP                   min(0, -lambda (seq_score - tau)) in double from the float32 fields; NaN without a STATS line
+ *   exp, clu                  from the sweep (wh_seq_expect)
+ *   reg                       detail.nregions, the count the score was built from (the sweep's own count is compared:
+ *                             wh_last_seq_table_status)
+ *   env, dom                  the envelopes the detail record lists (min(nenv, WH_MAX_ENVELOPES))
+ *   ov                        listed envelopes d >= 1 with env_i[d] <= env_j[d - 1]
+ *   best ...                  the listed envelope with the largest bits (a tie: the first), its bits, bias and lnP by the
+ *                             formula above wh_domain
+ *   rep, inc                  listed domains with exp(lnP) domZ <= domE on a sequence with E-value <= E; ... <= incdomE on
+ *                             a sequence with E-value <= incE (a model without STATS lines: every listed domain)
+ *   capped                    1 where nenv == WH_MAX_ENVELOPES or nregions > WH_MAX_ENVELOPES: env, dom, ov, rep, inc and
+ *                             the best domain are then lower bounds (see wh_domain_counts)
+ * Two small kernels around wh_seq_expect_dev: the first compacts the reported pairs into the pair list, the second fills
+ * one record per lane.  The _dev variant waits for the stream twice (the row count, the pair list). */
+typedef struct wh_seq_table_opts { double Z, domZ, E, domE, incE, incdomE; } wh_seq_table_opts;
+typedef struct wh_seq_row {
+  int64_t pair;
+  double  seq_lnP;
+  float   seq_bits, seq_bias_bits;
+  float   exp;
+  int32_t reg, clu, ov, env, dom, rep, inc;
+  int32_t best;
+  float   best_bits, best_bias_bits, best_lnP;
+  int32_t capped;
+  int32_t reserved;        /* 0 (the record is 80 bytes) */
+} wh_seq_row;
+int wh_seq_table(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const uint8_t *flags,
+                 const wh_pair_detail *detail, const wh_seq_table_opts *opts, wh_seq_row *out, int64_t cap);
+int wh_seq_table_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
+                     int32_t max_len, const uint8_t *d_flags, const wh_pair_detail *d_detail, const wh_seq_table_opts *opts,
+                     wh_seq_row *d_out, int64_t cap, void *stream);
+/* The assembly alone on host arrays, without a handle or a device (the same inline code the kernel runs): rows from the
+ * records and the sweep's results expect[t] of the reported pairs in pair order (t-th reported pair); tau / lambda [H] as
+ * wh_ehmm_evparams gives them.  lengths[nq]: the queries' lengths.  Returns the row count or WH_ERANGE. */
+int wh_seq_table_host(int H, const float *tau, const float *lambda, const int64_t *lengths, int64_t nq, const uint8_t *flags,
+                      const wh_pair_detail *detail, const wh_seq_expect_rec *expect, const wh_seq_table_opts *opts,
+                      wh_seq_row *out, int64_t cap);
+/* The last wh_seq_table[_dev] call: out[0] = rows, [1] = rows with capped set, [2] = rows whose sweep counted other regions
+ * than detail.nregions, [3] = pairs the sweep served on the any-size float64 path. */
+int wh_last_seq_table_status(wh_ehmm *e, int64_t out[4]);
 
 /* ---- eHMM construction (host code, no GPU needed) -------------------------------
  * Replaces the reference's per-subset call

@@ -59,6 +59,17 @@ class HitsOpts(C.Structure):
     _fields_ = [("Z", C.c_double), ("domZ", C.c_double), ("incE", C.c_double), ("incdomE", C.c_double)]
 
 
+class SeqTableOpts(C.Structure):
+    """wh_seq_table_opts (include/witch_hip.h): the search space sizes (<= 0: the number of targets / of reported sequences)
+    and the reporting and inclusion thresholds of hmmsearch --tblout."""
+    _fields_ = [("Z", C.c_double), ("domZ", C.c_double), ("E", C.c_double), ("domE", C.c_double), ("incE", C.c_double),
+                ("incdomE", C.c_double)]
+
+
+SEQ_EXPECT_FIELDS = [("exp", "<f4"), ("reg", "<i4"), ("clu", "<i4")]      # wh_seq_expect_rec
+SEQ_ROW_FIELDS = [("pair", "<i8"), ("seq_lnP", "<f8"), ("seq_bits", "<f4"), ("seq_bias_bits", "<f4"), ("exp", "<f4"), ("reg", "<i4"),
+                  ("clu", "<i4"), ("ov", "<i4"), ("env", "<i4"), ("dom", "<i4"), ("rep", "<i4"), ("inc", "<i4"), ("best", "<i4"),
+                  ("best_bits", "<f4"), ("best_bias_bits", "<f4"), ("best_lnP", "<f4"), ("capped", "<i4"), ("reserved", "<i4")]      # wh_seq_row
 HIT_ROW_FIELDS = [("query", "<i4"), ("index", "<i4"), ("ali_i", "<i4"), ("ali_j", "<i4")]      # wh_hit_row
 DOMAIN_FIELDS = [("pair", "<i8"), ("index", "<i4"), ("of", "<i4"), ("env_i", "<i4"), ("env_j", "<i4"), ("ali_i", "<i4"),
                  ("ali_j", "<i4"), ("hmm_i", "<i4"), ("hmm_j", "<i4"), ("bits", "<f4"), ("bias_bits", "<f4"), ("oasc", "<f4"),
@@ -130,6 +141,13 @@ SYMBOLS = {
     "wh_score_filtered_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "wh_last_filter_counts": (C.c_int, [_P, _P]),
     "wh_filter_log_differences": (C.c_int64, [C.c_uint32, C.c_uint32]),
+    "wh_seq_expect": (C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "wh_seq_expect_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, _P, _P]),
+    "wh_seq_expect_host": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    "wh_seq_table": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64]),
+    "wh_seq_table_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, C.c_int64, _P]),
+    "wh_seq_table_host": (C.c_int, [C.c_int, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int64]),
+    "wh_last_seq_table_status": (C.c_int, [_P, _P]),
     "wh_ehmm_evparams": (C.c_int, [_P, _P, _P, _P]),
     "wh_hmm_evparams": (C.c_int, [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "wh_consensus": (C.c_int, [_P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P]),

@@ -1,6 +1,6 @@
 // Internal header of the host side of libwitch_hip.so: what wh_api.hip (handles, options, getters, host-pointer entry
 // points), wh_host_score.hip (wh_score_dev), wh_host_resolve.hip (its resolver stage), wh_host_align.hip (wh_align_dev),
-// wh_host_domains.hip (wh_domains_dev), wh_host_msa.hip (wh_msa_dev), wh_host_hits.hip (wh_hits_msa_dev) and wh_host_filter.hip (the filters) share: the handle, the d_counter slots, the
+// wh_host_domains.hip (wh_domains_dev), wh_host_msa.hip (wh_msa_dev), wh_host_hits.hip (wh_hits_msa_dev), wh_host_seqtab.hip (wh_seq_table_dev) and wh_host_filter.hip (the filters) share: the handle, the d_counter slots, the
 // staging of the host-pointer entry points.  No kernel file includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -67,6 +67,7 @@ static_assert(kSlotScorePath + kScorePathInts <= kSlotWideScore && kSlotWideScor
               "d_counter slots overlap or leave the buffer, the resolver's feedback does not fill its range, or a list's address is not 8-byte aligned");
 
 struct FilterState;      // private to wh_host_filter.hip
+struct SeqTabState;      // private to wh_host_seqtab.hip
 
 struct wh_ehmm {
   Knobs knobs;
@@ -132,6 +133,9 @@ struct wh_ehmm {
   // acceleration filters (wh_host_filter.hip, which alone knows the type): tables, per-length settings, last counts; made by the first wh_filter call
   struct FilterStateDelete { void operator()(FilterState *f) const; };
   std::unique_ptr<FilterState, FilterStateDelete> filter;
+  // hmmsearch --tblout (wh_host_seqtab.hip, which alone knows the type): work lists, workspaces, last status; made by the first wh_seq_expect / wh_seq_table call
+  struct SeqTabStateDelete { void operator()(SeqTabState *f) const; };
+  std::unique_ptr<SeqTabState, SeqTabStateDelete> seqtab;
   bool timing = false;
   KernelTimer timers[9];                    // wh_last_kernel_ms: 0 scoring, 1 topk, 2 align, 3 consensus, 4 resolver, 5 domain stage, 6 alignment assembly (wh_msa_dev), 7 --mapali mapping (wh_msa_mapali_dev), 8 hit selection (wh_hits_msa_dev)
   int max_M = 0;

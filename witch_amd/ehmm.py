@@ -37,6 +37,44 @@ def alignment_checksum(molecule, rows):
     return int(out.value)
 
 
+def seq_expect_host(hmm_paths, residues, offsets, pairs):
+    """The counts of hmmsearch --tblout without a device (wh_seq_expect_host: float64 scalar code over the model files): a
+    structured array (exp, reg, clu), one record per entry of pairs (q * H + h)."""
+    residues = np.ascontiguousarray(residues, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+    n = len(hmm_paths)
+    arr = (C.c_char_p * n)(*[str(p).encode() for p in hmm_paths])
+    out = np.zeros(len(pairs), dtype=np.dtype(_lib.SEQ_EXPECT_FIELDS))
+    check(lib().wh_seq_expect_host(arr, n, residues.ctypes.data, offsets.ctypes.data, len(offsets) - 1, pairs.ctypes.data, len(pairs),
+                                   out.ctypes.data), "wh_seq_expect_host")
+    return out
+
+
+def seq_table_opts(Z=None, domZ=None, E=10.0, domE=10.0, incE=0.01, incdomE=0.01) -> _lib.SeqTableOpts:
+    return _lib.SeqTableOpts(0.0 if Z is None else float(Z), 0.0 if domZ is None else float(domZ), float(E), float(domE), float(incE),
+                             float(incdomE))
+
+
+def seq_table_host(tau, lam, lengths, flags, detail, expect, Z=None, domZ=None, E=10.0, domE=10.0, incE=0.01, incdomE=0.01):
+    """The row assembly of hmmsearch --tblout on host arrays, without a handle or a device (wh_seq_table_host): tau, lam
+    float32 [H]; lengths int64 [nq]; flags uint8 [nq, H]; detail: PairDetail records; expect: (exp, reg, clu) of the reported
+    pairs in pair order.  Returns the rows (SEQ_ROW_FIELDS)."""
+    tau = np.ascontiguousarray(tau, dtype=np.float32)
+    lam = np.ascontiguousarray(lam, dtype=np.float32)
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    flags = np.ascontiguousarray(flags, dtype=np.uint8)
+    expect = np.ascontiguousarray(expect, dtype=np.dtype(_lib.SEQ_EXPECT_FIELDS))
+    H, nq = len(tau), len(lengths)
+    cap = int((flags.reshape(-1) & 1).sum())
+    out = np.zeros(cap, dtype=np.dtype(_lib.SEQ_ROW_FIELDS))
+    o = seq_table_opts(Z, domZ, E, domE, incE, incdomE)
+    n = lib().wh_seq_table_host(H, tau.ctypes.data, lam.ctypes.data, lengths.ctypes.data, nq, flags.ctypes.data, C.addressof(detail),
+                                expect.ctypes.data, C.byref(o), out.ctypes.data, cap)
+    check(min(n, 0), "wh_seq_table_host")
+    return out[:n]
+
+
 class EHMM:
     def __init__(self, hmm_paths, hmm_index=None, nseq=None, device: int = 0):
         L = lib()
@@ -382,6 +420,39 @@ class EHMM:
         check(lib().wh_ehmm_evparams(self._h, tau.ctypes.data, lam.ctypes.data, present.ctypes.data), "wh_ehmm_evparams")
         return tau, lam, present.astype(bool)
 
+    def seq_expect(self, residues, offsets, pairs):
+        """exp, reg, clu of hmmsearch --tblout for the pairs q * H + h (include/witch_hip.h: wh_seq_expect): the two
+        full-width multihit sweeps recomputed on the device; a structured array (exp, reg, clu)."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+        out = np.zeros(len(pairs), dtype=np.dtype(_lib.SEQ_EXPECT_FIELDS))
+        check(lib().wh_seq_expect(self._h, residues.ctypes.data, offsets.ctypes.data, len(offsets) - 1, pairs.ctypes.data, len(pairs),
+                                  out.ctypes.data), "wh_seq_expect")
+        return out
+
+    def seq_table(self, residues, offsets, flags, detail, Z=None, domZ=None, E=10.0, domE=10.0, incE=0.01, incdomE=0.01):
+        """The rows of hmmsearch's per-sequence table (--tblout), one per reported pair in pair order, from the flags and
+        detail records of score(want_detail=True): a structured array with the fields of wh_seq_row (include/witch_hip.h:
+        wh_seq_table).  Z / domZ None: the number of queries / of reported pairs."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        nq = len(offsets) - 1
+        cap = int((flags.reshape(-1) & 1).sum())
+        out = np.zeros(cap, dtype=np.dtype(_lib.SEQ_ROW_FIELDS))
+        o = seq_table_opts(Z, domZ, E, domE, incE, incdomE)
+        n = lib().wh_seq_table(self._h, residues.ctypes.data, offsets.ctypes.data, nq, flags.ctypes.data, C.addressof(detail),
+                               C.byref(o), out.ctypes.data, cap)
+        check(min(n, 0), "wh_seq_table")
+        return out[:n]
+
+    def last_seq_table_status(self):
+        """The last seq_table call: {"rows", "capped", "reg_mismatch", "any_size"} (wh_last_seq_table_status)."""
+        c = np.zeros(4, dtype=np.int64)
+        check(lib().wh_last_seq_table_status(self._h, c.ctypes.data), "wh_last_seq_table_status")
+        return dict(zip(("rows", "capped", "reg_mismatch", "any_size"), (int(v) for v in c)))
+
     def domain_counts(self, flags, detail):
         """(counts int32 [nq, H], n_unlisted int32 [nq, H]) from the flags and detail records of score(want_detail=True)
         (include/witch_hip.h: wh_domain_counts)."""
@@ -630,6 +701,30 @@ class EHMM:
                                int(cols_t.numel()), int(h), flags, C.byref(W), *[C.byref(p) for p in ptrs], C.byref(npl),
                                self._stream()), "wh_msa_dev")
         return self._msa_collect(nq, int(h), W, npl, ptrs)
+
+    def seq_expect_t(self, residues_t, offsets_t, max_len: int, pairs_t):
+        """seq_expect() on torch tensors resident on the device (wh_seq_expect_dev on torch's current stream): a uint8
+        tensor [n, 12], the (exp, reg, clu) records - view it on the host with numpy's SEQ_EXPECT_FIELDS dtype."""
+        import torch
+        n = int(pairs_t.numel())
+        out = torch.zeros((n, 12), dtype=torch.uint8, device=residues_t.device)
+        check(lib().wh_seq_expect_dev(self._h, residues_t.data_ptr(), offsets_t.data_ptr(), offsets_t.numel() - 1, residues_t.numel(),
+                                      int(max_len), pairs_t.data_ptr(), n, out.data_ptr(), self._stream()), "wh_seq_expect_dev")
+        return out
+
+    def seq_table_t(self, residues_t, offsets_t, max_len: int, flags_t, detail_t, cap=None, Z=None, domZ=None, E=10.0, domE=10.0,
+                    incE=0.01, incdomE=0.01):
+        """seq_table() on torch tensors resident on the device (wh_seq_table_dev): detail_t as for domains_dev.  Returns the
+        rows as a uint8 tensor [n, 80] (numpy's SEQ_ROW_FIELDS dtype).  cap: room for so many rows (default: every pair)."""
+        import torch
+        nq = offsets_t.numel() - 1
+        cap = nq * self.H if cap is None else int(cap)
+        out = torch.zeros((cap, 80), dtype=torch.uint8, device=residues_t.device)
+        o = seq_table_opts(Z, domZ, E, domE, incE, incdomE)
+        n = lib().wh_seq_table_dev(self._h, residues_t.data_ptr(), offsets_t.data_ptr(), nq, residues_t.numel(), int(max_len),
+                                   flags_t.data_ptr(), detail_t.data_ptr(), C.byref(o), out.data_ptr(), cap, self._stream())
+        check(min(n, 0), "wh_seq_table_dev")
+        return out[:n]
 
     def domains_dev(self, residues_t, offsets_t, max_len: int, flags_t, detail_t):
         """domains() on torch tensors resident on the device (wh_domain_counts_dev, wh_domains_dev on torch's current

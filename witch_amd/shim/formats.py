@@ -216,6 +216,91 @@ def format_domtblout(hmm_path, fasta_path, hdr, rows, lengths, domains, n_target
     return "\n".join(out) + "\n"
 
 
+# ------------------------------------------------------------------------------------------------ per-sequence table
+TBL_COLUMNS = ["target", "tacc", "query", "qacc", "evalue", "score", "bias", "best_evalue", "best_score", "best_bias", "exp", "reg",
+               "clu", "ov", "env", "dom", "rep", "inc", "desc"]
+
+
+def _pvalue(lnp):
+    """exp(lnP) as the reference's hmmsearch binary evaluates it: its SSE build runs with flush-to-zero and
+    denormals-are-zero set, so a P-value below the smallest NORMAL double (2.2e-308) prints as 0.  NaN (no STATS line): 0."""
+    if lnp != lnp:
+        return 0.0
+    p = math.exp(lnp)
+    return p if p >= 2.2250738585072014e-308 else 0.0
+
+
+def seq_table_entries(hdr, names, table, n_targets, H=1, Z=None, descriptions=None):
+    """One dict per row of EHMM.seq_table (TBL_COLUMNS as numbers, plus "capped"), in HMMER's hit order.  names: the
+    searched records' names by query number; Z defaults to the number of targets.  A model without STATS lines has no
+    E-values: 0, as in the main output."""
+    Z = float(n_targets if Z is None else Z)
+    descriptions = descriptions or {}
+    rows = {}
+    for r in table:
+        name = names[int(r["pair"]) // H]
+        lnp, blnp = float(r["seq_lnP"]), float(r["best_lnP"])
+        rows[name] = {"target": name, "tacc": "-", "query": hdr["name"], "qacc": "-",
+                      "evalue": _pvalue(lnp) * Z, "score": float(r["seq_bits"]),
+                      "bias": float(r["seq_bias_bits"]), "best_evalue": _pvalue(blnp) * Z,
+                      "best_score": float(r["best_bits"]), "best_bias": float(r["best_bias_bits"]), "exp": float(r["exp"]),
+                      "reg": int(r["reg"]), "clu": int(r["clu"]), "ov": int(r["ov"]), "env": int(r["env"]), "dom": int(r["dom"]),
+                      "rep": int(r["rep"]), "inc": int(r["inc"]), "desc": descriptions.get(name, "-"), "capped": bool(r["capped"])}
+    order = hit_order([(n, e["score"], e["bias"], e["dom"], e["score"]) for n, e in rows.items()], hdr)
+    return [rows[o[0]] for o in order]
+
+
+def _tbl_widths(entries):
+    return (max([20] + [len(e["target"]) for e in entries]), max([20] + [len(e["query"]) for e in entries]),
+            max([10] + [len(e["tacc"]) for e in entries]), max([10] + [len(e["qacc"]) for e in entries]))
+
+
+def format_tblout_header(widths=(20, 20, 10, 10)):
+    """The three comment lines in front of HMMER 3.1b2's --tblout rows; the name columns grow with the longest name."""
+    tw, qw, taw, qaw = widths
+    return ["#%*s %22s %22s %33s" % (tw + qw + taw + qaw + 2, "", "--- full sequence ----", "--- best 1 domain ----",
+                                     "--- domain number estimation ----"),
+            "#%-*s %-*s %-*s %-*s %9s %6s %5s %9s %6s %5s %5s %3s %3s %3s %3s %3s %3s %3s %s" %
+            (tw - 1, " target name", taw, "accession", qw, "query name", qaw, "accession", "  E-value", " score", " bias",
+             "  E-value", " score", " bias", "exp", "reg", "clu", " ov", "env", "dom", "rep", "inc", "description of target"),
+            "#%s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s %s" %
+            ("-" * (tw - 1), "-" * taw, "-" * qw, "-" * qaw, "---------", "------", "-----", "---------", "------", "-----",
+             "  ---", "---", "---", "---", "---", "---", "---", "---", "---------------------")]
+
+
+def format_tblout_lines(entries, widths=None):
+    """HMMER 3.1b2's --tblout line for each entry (TBL_COLUMNS as numbers)."""
+    tw, qw, taw, qaw = widths or _tbl_widths(entries)
+    return ["%-*s %-*s %-*s %-*s %9.2g %6.1f %5.1f %9.2g %6.1f %5.1f %5.1f %3d %3d %3d %3d %3d %3d %3d %s" %
+            (tw, e["target"], taw, e["tacc"], qw, e["query"], qaw, e["qacc"], e["evalue"], e["score"], e["bias"], e["best_evalue"],
+             e["best_score"], e["best_bias"], e["exp"], e["reg"], e["clu"], e["ov"], e["env"], e["dom"], e["rep"], e["inc"],
+             e.get("desc") or "-") for e in entries]
+
+
+def format_tblout(hmm_path, fasta_path, hdr, entries, option_settings=None, cwd=None, date=None):
+    """The --tblout file in HMMER 3.1b2's layout: three header lines, one line per reported sequence in hit order, the
+    trailer's comment lines (program, version, pipeline mode, the two files; the command line, the directory and the date -
+    date: time.ctime()'s text, as HMMER writes it - where the caller gives them; [ok]).  A row whose record is capped
+    (EHMM.seq_table: more envelopes than a detail record lists) is written as it is, and one extra comment line in front of
+    the trailer names those sequences: their env, dom, ov, rep, inc and best domain are lower bounds."""
+    widths = _tbl_widths(entries) if entries else (20, max(20, len(hdr["name"])), 10, 10)
+    out = format_tblout_header(widths) + format_tblout_lines(entries, widths)
+    capped = [e["target"] for e in entries if e.get("capped")]
+    if capped:
+        out.append("# witch-hip: env, dom, ov, rep, inc and the best domain are lower bounds (more envelopes than are listed) for: %s" %
+                   " ".join(capped))
+    out += ["#", "# Program:         hmmsearch", "# Version:         3.1b2 (February 2015)", "# Pipeline mode:   SEARCH",
+            "# Query file:      %s" % hmm_path, "# Target file:     %s" % fasta_path]
+    if option_settings is not None:
+        out.append("# Option settings: %s" % option_settings)
+    if cwd is not None:
+        out.append("# Current dir:     %s" % cwd)
+    if date is not None:
+        out.append("# Date:            %s" % date)
+    out.append("# [ok]")
+    return "\n".join(out) + "\n"
+
+
 def format_domain_table(name, entries, M, L):
     """HMMER's ">> name" section of one reported sequence (as printed under --noali): its reportable domains."""
     out = [">> %s  " % name]

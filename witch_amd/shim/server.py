@@ -108,9 +108,11 @@ def check_hmmsearch_options(opts):
     -A FILE is written too: the alignment of every domain that satisfies the inclusion thresholds (wh_hits_msa: --incE,
     --incdomE, -Z and --domZ are read and checked for it as for --domtblout; --notextw: one block), and the main output
     says so behind "//"; a backend without search_hits refuses the option by name.
-    Two things stay unimplemented and are accepted as no-ops: --tblout (its exp,
-    clu and ov columns need counts the scoring kernels do not export) and the alignment display (the output is always
-    that of --noali)."""
+    --tblout FILE is written as well: the per-sequence table of wh_seq_table, alone or together with --domtblout and -A
+    (-Z, --domZ, -E, --domE, --incE and --incdomE are read and checked for it as for --domtblout); a backend without
+    search_table refuses the option by name.
+    One thing stays unimplemented and is accepted as a no-op: the alignment display (the output is always that of
+    --noali)."""
     if "--max" not in opts and "--nobias" not in opts and not bias_filter_enabled():
         raise ArgError("witch-hip hmmsearch shim: the filtered search is implemented without HMMER's bias filter only: "
                        "pass --nobias (MSV, Viterbi and Forward filters at --F1 --F2 --F3), or --max (no filters; "
@@ -127,12 +129,12 @@ def check_hmmsearch_options(opts):
                 raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
             if o == "--domE" and not v >= 0:
                 raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
-            if o in ("--incE", "--incdomE") and "-A" in opts and not v >= 0:
+            if o in ("--incE", "--incdomE") and ("-A" in opts or "--tblout" in opts) and not v >= 0:
                 raise ArgError("witch-hip hmmsearch shim: bad value for %s" % o)
             if o == "-E" and v < 1e6:
                 raise ArgError("witch-hip hmmsearch shim: -E %s would drop hits; only E >= 1e6 (WITCH: 99999999) "
                                "is supported, every sequence with a domain is reported" % opts[o])
-    for o in (("-Z", "--domZ") if "--domtblout" in opts or "-A" in opts else ()):      # (read only for the per-domain output and -A; else ignored as before)
+    for o in (("-Z", "--domZ") if "--domtblout" in opts or "-A" in opts or "--tblout" in opts else ()):      # (read only for the per-domain output, -A and --tblout; else ignored as before)
         if o in opts:
             try:
                 ok = float(opts[o]) > 0
@@ -205,7 +207,7 @@ class GpuBackend:
         The domains cost an alignment per envelope: only a caller that prints them asks for them.
         filters=(F1, F2, F3): behind hmmsearch's acceleration filters (without the bias filter: --nobias); the stage
         counts of the search are then in self.last_passed (n MSV, n bias, n Vit, n Fwd).  bias=True: with the bias filter."""
-        hdr, rows, domains, _ = self._search(hmm_path, records, want_domains, filters, None, bias)
+        hdr, rows, domains = self._search(hmm_path, records, want_domains, filters, None, bias)[:3]
         return (hdr, rows, domains) if want_domains else (hdr, rows)
 
     def search_hits(self, hmm_path, records, inc, want_domains=False, filters=None, bias=False):
@@ -214,11 +216,18 @@ class GpuBackend:
         order.  inc: {"incE", "incdomE", "Z", "domZ"} (Z / domZ None: the number of targets / of reported sequences).  The
         rows carry the unrounded score as the tables of --domtblout do.  With want_domains the domain records come from the
         same alignment of the envelopes (wh_hits_msa hands them back): one domain stage serves --domtblout and -A."""
-        return self._search(hmm_path, records, want_domains, filters, inc, bias)
+        return self._search(hmm_path, records, want_domains, filters, inc, bias)[:4]
 
-    def _search(self, hmm_path, records, want_domains, filters, inc, bias=False):
+    def search_table(self, hmm_path, records, table, want_domains=False, filters=None, bias=False, inc=None):
+        """search() for hmmsearch --tblout: (header, rows, domains or None, hits or None, table rows) from ONE scoring call.
+        table: {"Z", "domZ", "E", "domE", "incE", "incdomE"} (Z / domZ None: the number of targets / of reported sequences);
+        the table rows are EHMM.seq_table's records (wh_seq_table).  inc: as for search_hits, when -A is asked for as well.
+        The rows carry the unrounded score, as for --domtblout."""
+        return self._search(hmm_path, records, want_domains, filters, inc, bias, table)
+
+    def _search(self, hmm_path, records, want_domains, filters, inc, bias=False, table=None):
         from witch_amd.ehmm import pack_queries
-        domains, hits = {}, None
+        domains, hits, tbl = {}, None, None
         with self.lock:
             e, hdr = self.model(hmm_path)
             seqs = [e.digitize(t.upper()) for _, t in records]     # alignment_tools.py:730-731 upper-cases
@@ -229,7 +238,7 @@ class GpuBackend:
                 deci, flags, det = e.score(res, offs, want_detail=True, filters=filters, nobias=not bias, bias=bias)
                 c = e.last_filter_counts()
                 self.last_passed = (c["msv"], c["bias"], c["vit"], c["fwd"])
-            exact = want_domains or inc is not None
+            exact = want_domains or inc is not None or table is not None
             rows = []
             for i, (name, _) in enumerate(records):
                 if flags[i, 0] & 1:
@@ -257,7 +266,9 @@ class GpuBackend:
                         lst.append(d)
                     if lst:
                         domains[name] = lst
-        return hdr, rows, (domains if want_domains else None), hits
+            if table is not None:
+                tbl = e.seq_table(res, offs, flags, det, **table)
+        return hdr, rows, (domains if want_domains else None), hits, tbl
 
     def align(self, jobs):
         """jobs: [(hmm_path, name, text)] -> [(M, cols, pp)]; one launch per distinct model.  pp: the posterior
@@ -358,6 +369,8 @@ class Server:
         if F is not None and "--nobias" not in opts:        # (accepted above only where the bias filter is switched on)
             fkw["bias"] = True
         passed = lambda: None if F is None else (self.backend.last_passed, F)
+        if "--tblout" in opts:
+            return self.run_hmmsearch_table(opts, hmm, fa, cwd, fkw, passed, argv)
         if "-A" in opts:
             return self.run_hmmsearch_hits(opts, hmm, fa, cwd, fkw, passed)
         records = formats.read_fasta(fa)
@@ -407,6 +420,49 @@ class Server:
             f.write(formats.format_hits_msa([n for n, _ in records], hits["row_recs"], hits["rows"], hits["pp_rows"], hits["pp_cons"],
                                             None if formats.hmm_has_rf(hmm) else hits["rf"], descriptions=desc,
                                             notextw="--notextw" in opts))
+        if "-o" in opts:
+            with open(os.path.join(cwd, opts["-o"]), "w") as f:
+                f.write(text)
+            return ""
+        return text
+
+    def run_hmmsearch_table(self, opts, hmm, fa, cwd, fkw, passed, argv):
+        """hmmsearch --tblout FILE: the search with the per-sequence table written to FILE, alone or together with
+        --domtblout and -A, from one scoring call.  The main output and the other files are those of the same call
+        without --tblout."""
+        if not hasattr(self.backend, "search_table"):
+            raise ArgError("witch-hip hmmsearch shim: --tblout needs a backend that assembles the per-sequence table "
+                           "(search_table); this one does not, and the option is not ignored")
+        if "-A" in opts and not hasattr(self.backend, "search_hits"):
+            raise ArgError("witch-hip hmmsearch shim: -A needs a backend that aligns the included hits (search_hits); "
+                           "this one does not, and the option is not ignored")
+        desc = {}
+        records = formats.read_fasta(fa, descriptions=desc)
+        want = "--domtblout" in opts
+        kw = {"Z": float(opts["-Z"]) if "-Z" in opts else None, "domZ": float(opts["--domZ"]) if "--domZ" in opts else None}
+        inc = {"incE": float(opts.get("--incE", 0.01)), "incdomE": float(opts.get("--incdomE", 0.01))}
+        table = dict(kw, E=float(opts.get("-E", 10.0)), domE=float(opts.get("--domE", 10.0)), **inc)
+        hdr, rows, domains, hits, tbl = self.backend.search_table(hmm, records, table, want_domains=want,
+                                                                  inc=dict(inc, **kw) if "-A" in opts else None, **fkw)
+        trailer = formats.hits_msa_trailer(len(hits["row_recs"]), opts["-A"]) if "-A" in opts else None
+        if want:
+            lengths = {n: len(t) for n, t in records}
+            kw["domE"] = float(opts.get("--domE", 10.0))
+            text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records), domains=domains, lengths=lengths, passed=passed(),
+                                            trailer=trailer, **kw, **inc)
+            with open(os.path.join(cwd, opts["--domtblout"]), "w") as f:
+                f.write(formats.format_domtblout(hmm, fa, hdr, rows, lengths, domains, len(records), **kw))
+        else:
+            text = formats.format_hmmsearch(hmm, fa, hdr, [r[:4] for r in rows], len(records), passed=passed(), trailer=trailer)
+        if "-A" in opts:
+            with open(os.path.join(cwd, opts["-A"]), "w") as f:
+                f.write(formats.format_hits_msa([n for n, _ in records], hits["row_recs"], hits["rows"], hits["pp_rows"], hits["pp_cons"],
+                                                None if formats.hmm_has_rf(hmm) else hits["rf"], descriptions=desc,
+                                                notextw="--notextw" in opts))
+        entries = formats.seq_table_entries(hdr, [n for n, _ in records], tbl, len(records), Z=table["Z"], descriptions=desc)
+        with open(os.path.join(cwd, opts["--tblout"]), "w") as f:
+            f.write(formats.format_tblout(hmm, fa, hdr, entries, option_settings="hmmsearch " + " ".join(argv), cwd=cwd,
+                                          date=time.ctime()))
         if "-o" in opts:
             with open(os.path.join(cwd, opts["-o"]), "w") as f:
                 f.write(text)
