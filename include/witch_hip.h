@@ -22,6 +22,8 @@
  *                     p7_tophits_Alignment); no reference code asks for it either
  *   wh_seq_table*  <- "hmmsearch --tblout FILE": the per-sequence table (HMMER's p7_tophits_TabularTargets), its exp, reg and
  *                     clu columns from wh_seq_expect*; no reference code asks for it either
+ *   wh_domain_display* <- hmmsearch's default output, the alignment of every reported domain (HMMER's p7_alidisplay_Create);
+ *                     no reference code asks for it either
  *
  * Conventions: plain pointers and sizes; the caller owns every input and output
  * buffer; the library owns wh_ehmm handles and its device workspace.  Functions
@@ -441,7 +443,8 @@ int wh_consensus_dev(wh_ehmm *e, const int64_t *d_offsets, int64_t nq, int32_t m
  * gather and summary kernels and the alignment launches between them; which = 2 then holds the alignment launches alone),
  * 6 the alignment assembly (wh_msa_dev: widths, layout, render and PP_cons kernels, and the host's one wait between them),
  * 7 the --mapali mapping (wh_msa_mapali_dev: count and map kernels, and the host's one wait between them),
- * 8 the hit selection of hmmsearch -A (wh_hits_msa_dev: mark, scan, place and slice kernels, and the host's one wait between them). */
+ * 8 the hit selection of hmmsearch -A (wh_hits_msa_dev: mark, scan, place and slice kernels, and the host's one wait between them),
+ * 9 the alignment display (wh_domain_display_dev: count, scan and render kernels, and the host's one wait between count and render). */
 int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches);
 /* Timing mode only: the scoring launches of the last wh_score[_dev] call, in launch order - the cells-per-lane class of the
  * launch's models (16 = models of 961..1024 nodes ...), the kernel family (0 phase-call wh::k7::score_kernel7, 1
@@ -598,6 +601,58 @@ int wh_hits_msa_dev(wh_ehmm *e, const uint8_t *d_text, const int64_t *d_offsets,
                     const int32_t *d_cols, const float *d_pp, int32_t h, const int32_t *d_order, const wh_hits_opts *opts,
                     int32_t msa_flags, int64_t *out_nrows, wh_hit_row **out_rows_rec, int64_t *out_W, uint8_t **out_rows,
                     uint8_t **out_pp_rows, uint8_t **out_pp_cons, uint8_t **out_rf, int32_t **out_matmap, void *stream);
+
+/* ---- hmmsearch's alignment display: the four lines under "== domain N" -------------------------------------------------
+ * wh_domain_display[_dev] replaces what HMMER 3.1b2's p7_alidisplay_Create writes for every reported domain: the model's
+ * consensus line, the match line, the target line and the posterior (PP) line, one character per alignment column from the
+ * domain's first match state (ali_i / hmm_i) to its last (ali_j / hmm_j).  The caller wraps them into blocks and adds names
+ * and coordinates (witch_amd/shim/formats.py: format_alidisplay).  Per column:
+ *   match state   model: the node's consensus letter as the model file prints it; target: the alphabet's symbol of the
+ *                 residue's digital code, upper case; match line: the consensus letter where the residue's code equals the
+ *                 letter's code, else '+' where the float32 match odds of that residue at that node exceed 1.0, else ' '
+ *   insert state  model '.', match line ' ', target: the symbol in lower case
+ *   delete state  (a node between two consecutive match states of the path) model: its consensus letter, match line ' ',
+ *                 target '-', PP '.'
+ *   PP            match and insert: HMMER's p7_alidisplay_EncodePostProb of the float32 posterior, in double:
+ *                 '*' where p + 0.05 >= 1.0, else '0' + (int)((p + 0.05) * 10.0)
+ * A domain is SELECTED where its pair is WH_FLAG_REPORTED and of model h, it has a path (ali_i != 0) and is reportable:
+ * lnP <= ln(domE / domZ), the logarithm taken once on the host (domE = 0 selects nothing; lnP NaN - a model without a STATS
+ * line - selects every domain with a path).  The selected domains keep record order.
+ * The model needs "CONS yes" in its header and neither "RF yes" nor "CS yes" (HMMER prints extra lines for those): any
+ * other model is refused with WH_EINVAL, wh_last_error naming the entry point and the header key.  The model's display table
+ * (float32 match odds per node and residue code, degenerate codes included, from the values the scoring tables are built
+ * from; the consensus letters and their codes) is built and uploaded at the first display call of that model, not at load.
+ * Inputs: residues / offsets / nq / flags of the scoring call, dom_off, and the records, env_off, cols, pp of
+ * wh_domain_paths_dev.  Outputs of _dev, the CALLER's device arrays: d_disp_off[ndom + 1] (the first nsel + 1 entries are
+ * written), d_recs[ndom] (nsel written: the query and the domain's index within its pair), and four byte arrays of cap
+ * bytes each, of which the first disp_off[nsel] are written, each exactly once; nothing beyond is touched.  cap >= the sum
+ * over all domains of (M + envelope length) always suffices.  *out_nsel, *out_total = disp_off[nsel]; WH_ERANGE (nothing
+ * rendered, *out_total set) where total > cap.  The records are checked against dom_off, their envelopes, their queries and
+ * their own paths (nodes rising from hmm_i to hmm_j): WH_EINVAL otherwise.  Three kernels - count (one wavefront per domain),
+ * a two-level scan, render (one wavefront per domain) - and one wait of the host between count and render, after a first
+ * one for dom_off's last entry.  wh_last_kernel_ms(9): these kernels with that wait.
+ * The PP line encodes the posteriors it is given: wh_domain_paths_dev's are hmmalign's, under the length model of the envelope,
+ * where hmmsearch decodes an envelope under the length model of its whole sequence (the level-0 server passes those:
+ * DESIGN.md section 4.15).
+ * wh_domain_display takes host pointers and runs wh_domain_paths_dev first (wh_last_kernel_ms(5): that domain stage);
+ * out_dom (optional, [dom_off[nq x H]]) receives the wh_domain records; *out_disp_off, *out_recs and the four lines are
+ * malloc'ed (release with wh_free_text; NULL where nothing is selected).
+ * wh_ehmm_consensus: the consensus letters of model h as its file prints them (the CONS column of the match lines), M
+ * characters without a terminator; *present = 0 and nothing written where the header does not say "CONS yes". */
+typedef struct wh_display_rec { int32_t query, index; } wh_display_rec;
+int wh_ehmm_consensus(const wh_ehmm *e, int h, char *out /* [M] */, int32_t *present);
+/* The same for one model file, through the same parser, without a handle (wh_ehmm_load needs a device, this does not): the
+ * first min(cap, M) letters, *out_M = M (optional), *present = 1 (CONS yes) | 2 (RF yes) | 4 (CS yes). */
+int wh_hmm_consensus(const char *hmm_path, char *out, int32_t cap, int32_t *out_M, int32_t *present);
+int wh_domain_display(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const uint8_t *flags,
+                      const wh_pair_detail *detail, const int64_t *dom_off, int32_t h, double domE, double domZ,
+                      wh_domain *out_dom, int64_t *out_nsel, int64_t **out_disp_off, wh_display_rec **out_recs,
+                      uint8_t **out_model, uint8_t **out_match, uint8_t **out_target, uint8_t **out_pp);
+int wh_domain_display_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, const uint8_t *d_flags,
+                          const int64_t *d_dom_off, const wh_domain *d_dom, const int64_t *d_env_off, const int32_t *d_cols,
+                          const float *d_pp, int32_t h, double domE, double domZ, int64_t cap, int64_t *d_disp_off,
+                          wh_display_rec *d_recs, uint8_t *d_model, uint8_t *d_match, uint8_t *d_target, uint8_t *d_ppline,
+                          int64_t *out_nsel, int64_t *out_total, void *stream);
 
 /* ---- hmmsearch --tblout: the per-sequence table -------------------------------------------------------------------------
  * Three of its columns are counts of HMMER's domain definition that the scoring kernels do not export: exp, the expected

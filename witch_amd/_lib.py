@@ -71,6 +71,7 @@ SEQ_ROW_FIELDS = [("pair", "<i8"), ("seq_lnP", "<f8"), ("seq_bits", "<f4"), ("se
                   ("clu", "<i4"), ("ov", "<i4"), ("env", "<i4"), ("dom", "<i4"), ("rep", "<i4"), ("inc", "<i4"), ("best", "<i4"),
                   ("best_bits", "<f4"), ("best_bias_bits", "<f4"), ("best_lnP", "<f4"), ("capped", "<i4"), ("reserved", "<i4")]      # wh_seq_row
 HIT_ROW_FIELDS = [("query", "<i4"), ("index", "<i4"), ("ali_i", "<i4"), ("ali_j", "<i4")]      # wh_hit_row
+DISPLAY_REC_FIELDS = [("query", "<i4"), ("index", "<i4")]      # wh_display_rec
 DOMAIN_FIELDS = [("pair", "<i8"), ("index", "<i4"), ("of", "<i4"), ("env_i", "<i4"), ("env_j", "<i4"), ("ali_i", "<i4"),
                  ("ali_j", "<i4"), ("hmm_i", "<i4"), ("hmm_j", "<i4"), ("bits", "<f4"), ("bias_bits", "<f4"), ("oasc", "<f4"),
                  ("lnP", "<f4")]
@@ -134,6 +135,12 @@ SYMBOLS = {
                               C.POINTER(C.c_void_p), C.POINTER(C.c_int64)] + [C.POINTER(C.c_void_p)] * 5),
     "wh_hits_msa_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(C.c_int64),
                                   C.POINTER(C.c_void_p), C.POINTER(C.c_int64)] + [C.POINTER(C.c_void_p)] * 5 + [_P]),
+    "wh_ehmm_consensus": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int32)]),
+    "wh_hmm_consensus": (C.c_int, [C.c_char_p, _P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "wh_domain_display": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, C.c_double, C.c_double, _P, C.POINTER(C.c_int64)] +
+                          [C.POINTER(C.c_void_p)] * 6),
+    "wh_domain_display_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_double, C.c_double, C.c_int64,
+                                        _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     "wh_filter": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "wh_filter_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "wh_filter_host": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P]),

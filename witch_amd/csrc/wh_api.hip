@@ -340,7 +340,7 @@ int wh_last_score_launches(wh_ehmm *e, int32_t *cells_per_lane, int32_t *kind, d
 }
 
 int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches) {
-  if (!e || which < 0 || which > 8) return WH_EINVAL;
+  if (!e || which < 0 || which >= wh_ehmm::kTimers) return WH_EINVAL;
   KernelTimer &t = e->timers[which];
   if (t.pending) {
     HIPCHK(hipEventSynchronize(t.e1));

@@ -51,6 +51,10 @@ struct HostHMM {
   // tests/golden/filters_bias/nocompo equals a COMPO line of '*'s, and differs from the composition hmmbuild would print)
   std::vector<float> compo;                // [K]
   bool has_compo = false;
+  // the alignment display (wh_domain_display): the header's "CONS", "RF" and "CS" lines, and with "CONS yes" the consensus
+  // letter of every node in the file's own case ([M+1], node 0 unused; empty without the line)
+  bool has_cons = false, has_rf = false, has_cs = false;
+  std::vector<char> cons;
   // configured profile
   std::vector<double> pt;     // [(M+1)*7], node 0 and node M zeroed
   std::vector<double> entry;  // [M+2]

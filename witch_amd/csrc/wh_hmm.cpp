@@ -105,6 +105,9 @@ int parse_hmm_file(const std::string &path, HostHMM &h) {
     else if (key == "LENG" && tok.size() > 1) h.M = atoi(tok[1].c_str());
     else if (key == "NSEQ" && tok.size() > 1) h.nseq = atoi(tok[1].c_str());
     else if (key == "MAP" && tok.size() > 1) h.has_map = tok[1] == "yes";
+    else if (key == "CONS" && tok.size() > 1) h.has_cons = tok[1] == "yes";
+    else if (key == "RF" && tok.size() > 1) h.has_rf = tok[1] == "yes";
+    else if (key == "CS" && tok.size() > 1) h.has_cs = tok[1] == "yes";
     else if (key == "CKSUM" && tok.size() > 1) { h.has_cksum = true; h.cksum = (uint32_t)strtoul(tok[1].c_str(), nullptr, 10); }
     else if (key == "ALPH" && tok.size() > 1) {
       std::string a = tok[1];
@@ -127,6 +130,7 @@ int parse_hmm_file(const std::string &path, HostHMM &h) {
   h.t.assign((size_t)(M + 1) * 7, 0.0);
   h.mat.assign((size_t)(M + 1) * K, 0.0);
   h.map.assign((size_t)M + 1, 0);
+  if (h.has_cons) h.cons.assign((size_t)M + 1, '-');
   h.tf.assign((size_t)(M + 1) * 7, 0.f);
   h.matf.assign((size_t)(M + 1) * K, 0.f);
   auto bad = [&](const char *what, int k) {
@@ -150,11 +154,18 @@ int parse_hmm_file(const std::string &path, HostHMM &h) {
     if (!next_tokens(f, tok) || (int)tok.size() < K + 1 || atoi(tok[0].c_str()) != k) return bad("match line", k);
     for (int x = 0; x < K; x++) { h.mat[(size_t)k * K + x] = tok_prob(tok[1 + x]); h.matf[(size_t)k * K + x] = tok_probf(tok[1 + x]); }
     if ((int)tok.size() > K + 1 && tok[K + 1][0] != '-') h.map[k] = atoi(tok[K + 1].c_str());
+    // the annotation behind the MAP field: CONS, RF, MM, CS - one character each; a file that says "CONS yes" and leaves
+    // the column out has no consensus line to display
+    if (h.has_cons) {
+      if ((int)tok.size() > K + 2 && tok[K + 2].size() == 1) h.cons[(size_t)k] = tok[K + 2][0];
+      else h.has_cons = false;
+    }
     if (!next_tokens(f, tok)) return bad("insert line", k);
     if (!next_tokens(f, tok) || tok.size() < 7) return bad("transition line", k);
     for (int x = 0; x < 7; x++) { h.t[(size_t)k * 7 + x] = tok_prob(tok[x]); h.tf[(size_t)k * 7 + x] = tok_probf(tok[x]); }
   }
   if (!h.has_compo) h.compo.assign((size_t)K, 0.f);
+  if (!h.has_cons) h.cons.clear();
   configure_profile(h);
   return WH_OK;
 }

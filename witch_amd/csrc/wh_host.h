@@ -1,6 +1,6 @@
 // Internal header of the host side of libwitch_hip.so: what wh_api.hip (handles, options, getters, host-pointer entry
 // points), wh_host_score.hip (wh_score_dev), wh_host_resolve.hip (its resolver stage), wh_host_align.hip (wh_align_dev),
-// wh_host_domains.hip (wh_domains_dev), wh_host_msa.hip (wh_msa_dev), wh_host_hits.hip (wh_hits_msa_dev), wh_host_seqtab.hip (wh_seq_table_dev) and wh_host_filter.hip (the filters) share: the handle, the d_counter slots, the
+// wh_host_domains.hip (wh_domains_dev), wh_host_msa.hip (wh_msa_dev), wh_host_hits.hip (wh_hits_msa_dev), wh_host_display.hip (wh_domain_display_dev), wh_host_seqtab.hip (wh_seq_table_dev) and wh_host_filter.hip (the filters) share: the handle, the d_counter slots, the
 // staging of the host-pointer entry points.  No kernel file includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -68,6 +68,7 @@ static_assert(kSlotScorePath + kScorePathInts <= kSlotWideScore && kSlotWideScor
 
 struct FilterState;      // private to wh_host_filter.hip
 struct SeqTabState;      // private to wh_host_seqtab.hip
+struct DisplayState;     // private to wh_host_display.hip
 
 struct wh_ehmm {
   Knobs knobs;
@@ -136,8 +137,12 @@ struct wh_ehmm {
   // hmmsearch --tblout (wh_host_seqtab.hip, which alone knows the type): work lists, workspaces, last status; made by the first wh_seq_expect / wh_seq_table call
   struct SeqTabStateDelete { void operator()(SeqTabState *f) const; };
   std::unique_ptr<SeqTabState, SeqTabStateDelete> seqtab;
+  // hmmsearch's alignment display (wh_host_display.hip, which alone knows the type): the models' display tables, scan workspace, the host-pointer call's outputs; made by the first wh_domain_display call
+  struct DisplayStateDelete { void operator()(DisplayState *f) const; };
+  std::unique_ptr<DisplayState, DisplayStateDelete> display;
   bool timing = false;
-  KernelTimer timers[9];                    // wh_last_kernel_ms: 0 scoring, 1 topk, 2 align, 3 consensus, 4 resolver, 5 domain stage, 6 alignment assembly (wh_msa_dev), 7 --mapali mapping (wh_msa_mapali_dev), 8 hit selection (wh_hits_msa_dev)
+  static const int kTimers = 10;
+  KernelTimer timers[kTimers];              // wh_last_kernel_ms: 0 scoring, 1 topk, 2 align, 3 consensus, 4 resolver, 5 domain stage, 6 alignment assembly (wh_msa_dev), 7 --mapali mapping (wh_msa_mapali_dev), 8 hit selection (wh_hits_msa_dev), 9 alignment display (wh_domain_display_dev)
   int max_M = 0;
   int max_Q = 4;                              // largest cells-per-lane of any model (sizes the float64 slabs)
   int last_align_redo = 0;          // pairs of the last wh_align call that went through the log-space pass

@@ -472,6 +472,42 @@ hipError_t launch_hits_place(const HitsArgs &a, hipStream_t s);
 hipError_t launch_hits_slice(const HitsArgs &a, hipStream_t s);
 int64_t hits_scan_blocks(int64_t nq);
 
+// wh_domain_display_dev (wh_display.hip): the four text lines of hmmsearch's alignment display for the reportable domains of
+// model h.  The domain records, the envelope CSR and the per-residue columns / posteriors are wh_domain_paths_dev's; <tab_*>:
+// the model's display table (wh_host_display.hip builds it at the first call).
+struct DisplayArgs {
+  const uint8_t *flags;        // [npairs]
+  const int64_t *dom_off;      // [npairs + 1]
+  const wh_domain *dom;        // [ndom]
+  int64_t npairs, ndom, nq;
+  int H, h, M, Kp;
+  const uint8_t *residues;     // the residue codes of the scoring call ...
+  const int64_t *offsets;      // ... [nq + 1]
+  const int64_t *env_off;      // [ndom + 1]
+  const int32_t *cols;         // per envelope residue: 0-based node or -1 ...
+  const float *pp;             // ... and the posterior of its state
+  const float *tab_odds;       // [(M + 1) x Kp] float32 match odds of (node, residue code), degenerate codes included
+  const uint8_t *tab_cons;     // [M + 1] consensus letter of the node as the file prints it ...
+  const uint8_t *tab_code;     // ... and its digital code
+  const uint8_t *tab_sym;      // [32] the alphabet's symbol of every code (upper case)
+  double ln_rep_dom;           // ln(domE / domZ)
+  int32_t *len;                // count kernel: [ndom] columns of a selected domain, 0: not selected
+  int *bad;                    // ... set when a record does not fit dom_off, its envelope, its query or its own path
+  int64_t nblk;                // workgroups of the scan
+  int32_t *pos_sel;            // scan: [ndom] the selected domains in front of the domain inside its workgroup ...
+  long long *pos_len;          // ... and their columns
+  long long *blk_sel, *blk_len;   // [nblk] the workgroups' sums, then their exclusive scan
+  long long *totals;           // [2] selected domains, columns
+  int64_t nsel, total;         // ... as the host read them back
+  int64_t *disp_off;           // render kernel: [nsel + 1] the CSR of the lines ...
+  wh_display_rec *recs;        // ... [nsel] the domain of each ...
+  uint8_t *model, *match, *target, *ppline;   // ... and the four lines, total bytes each
+};
+hipError_t launch_display_count(const DisplayArgs &a, hipStream_t s);
+hipError_t launch_display_scan(const DisplayArgs &a, hipStream_t s);
+hipError_t launch_display_render(const DisplayArgs &a, hipStream_t s);
+int64_t display_scan_blocks(int64_t ndom);
+
 struct TopkArgs {
   const int32_t *decibits;
   const uint8_t *flags;

@@ -75,6 +75,31 @@ def seq_table_host(tau, lam, lengths, flags, detail, expect, Z=None, domZ=None, 
     return out[:n]
 
 
+def hmm_consensus(hmm_path):
+    """(the CONS column of a model file or None, {"CONS", "RF", "CS": bool} of its header) through the library's parser,
+    without a handle or a device (wh_hmm_consensus)."""
+    M, present = C.c_int32(0), C.c_int32(0)
+    check(lib().wh_hmm_consensus(str(hmm_path).encode(), None, 0, C.byref(M), C.byref(present)), "wh_hmm_consensus")
+    out = C.create_string_buffer(int(M.value) + 1)
+    check(lib().wh_hmm_consensus(str(hmm_path).encode(), out, int(M.value), None, C.byref(present)), "wh_hmm_consensus")
+    keys = {"CONS": bool(present.value & 1), "RF": bool(present.value & 2), "CS": bool(present.value & 4)}
+    return (out.raw[:int(M.value)].decode("ascii") if keys["CONS"] else None), keys
+
+
+class DevView:
+    """An array in the library's device workspace, where a torch tensor is expected by the *_t methods: its address and its
+    element count."""
+
+    def __init__(self, ptr, n):
+        self._ptr, self._n = ptr, int(n)
+
+    def data_ptr(self):
+        return self._ptr
+
+    def numel(self):
+        return self._n
+
+
 class EHMM:
     def __init__(self, hmm_paths, hmm_index=None, nseq=None, device: int = 0):
         L = lib()
@@ -582,6 +607,153 @@ class EHMM:
                                     _lib.WH_MSA_NO_LDS if no_lds else 0, C.byref(nrows), C.byref(recs), C.byref(W),
                                     *[C.byref(p) for p in ptrs], self._stream()), "wh_hits_msa_dev")
         return self._hits_collect(int(h), nrows, recs, W, ptrs)
+
+    def consensus_letters(self, h=0):
+        """The consensus letters of model h as its file prints them (the CONS column), None where the header does not say
+        "CONS yes" (include/witch_hip.h: wh_ehmm_consensus)."""
+        out = C.create_string_buffer(int(self.M[h]) + 1)
+        present = C.c_int32(0)
+        check(lib().wh_ehmm_consensus(self._h, int(h), out, C.byref(present)), "wh_ehmm_consensus")
+        return out.raw[:int(self.M[h])].decode("ascii") if present.value else None
+
+    @staticmethod
+    def _display_result(nsel, off, recs, lines):
+        """(disp_off int64 [nsel + 1], records, four uint8 arrays) -> domain_display's dict."""
+        return {"nsel": int(nsel), "disp_off": off, "recs": recs, "model": lines[0], "match": lines[1], "target": lines[2], "pp": lines[3]}
+
+    @staticmethod
+    def display_lines(disp, names, H=1):
+        """domain_display's dict as {name: {domain index within its pair: (model, match, target, pp) as str}}."""
+        out = {}
+        off = disp["disp_off"]
+        for r, rec in enumerate(disp["recs"]):
+            a, b = int(off[r]), int(off[r + 1])
+            out.setdefault(names[int(rec["query"])], {})[int(rec["index"])] = tuple(
+                disp[k][a:b].tobytes().decode("ascii") for k in ("model", "match", "target", "pp"))
+        return out
+
+    def domain_display(self, residues, offsets, flags, detail, domE=10.0, domZ=None, h=0, want_domains=False):
+        """hmmsearch's alignment display (include/witch_hip.h: wh_domain_display): the envelopes are aligned
+        (wh_domain_paths_dev) and the four lines under "== domain N" - model consensus, match line, target, PP - of every
+        reportable domain of model h are rendered on the device.  flags, detail: what score(want_detail=True) returned;
+        domZ None: the number of reported pairs of model h.  Returns {"nsel", "disp_off" int64 [nsel + 1], "recs" (query,
+        index) per selected domain, "model", "match", "target", "pp": uint8 arrays of disp_off[nsel] characters};
+        want_domains: also "domains" and "dom_off", what domains() returns - from the same alignment of the envelopes."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        nq = len(offsets) - 1
+        if domZ is None:
+            domZ = max(int((flags.reshape(nq, self.H)[:, int(h)] & 1).sum()), 1) if nq else 1
+        counts, _ = self.domain_counts(flags, detail)
+        dom_off = np.zeros(nq * self.H + 1, dtype=np.int64)
+        np.cumsum(counts.reshape(-1), out=dom_off[1:])
+        dom = np.zeros(int(dom_off[-1]), dtype=np.dtype(DOMAIN_FIELDS))
+        nsel = C.c_int64(0)
+        ptrs = [C.c_void_p(None) for _ in range(6)]
+        check(lib().wh_domain_display(self._h, residues.ctypes.data, offsets.ctypes.data, nq, flags.ctypes.data,
+                                      C.addressof(detail) if nq else None, dom_off.ctypes.data, int(h), float(domE), float(domZ),
+                                      dom.ctypes.data if len(dom) else None, C.byref(nsel), *[C.byref(p) for p in ptrs]), "wh_domain_display")
+        n = int(nsel.value)
+        off = self._take(ptrs[0], n + 1, np.int64) if n else np.zeros(1, dtype=np.int64)
+        recs = self._take(ptrs[1], 2 * n, np.int32).view(np.dtype(_lib.DISPLAY_REC_FIELDS))
+        total = int(off[-1])
+        m = self._display_result(n, off, recs, [self._take(p, total, np.uint8) for p in ptrs[2:]])
+        if want_domains:
+            m["domains"], m["dom_off"] = dom, dom_off
+        return m
+
+    def sequence_model_posteriors(self, residues, offsets, recs, env_off, cols, pp, h=0):
+        """The posteriors hmmsearch prints in a domain's PP line, for the domains of model h among the records of
+        domain_paths(): hmmsearch decodes an envelope under the unihit length model of the WHOLE sequence's L residues, where
+        domain_paths (hmmalign on the envelope alone: wh_align_pp) uses the envelope's own Ld.  The same kernels give the
+        former exactly when the envelope is followed by L - Ld residues that no match state can emit (the alphabet's gap
+        code: match odds 0): they can only sit in the C flank, where each multiplies EVERY path by the same loop
+        probability, which cancels in a posterior, and the length model is that of Ld + (L - Ld) = L residues.  One
+        wh_align_pp call on the padded envelopes whose sequence is longer than they are; a residue takes the new posterior
+        where that alignment puts it in the state the domain's own path has (everywhere, on the fixtures' strong domains),
+        else it keeps the old one.  Returns a copy of pp with those values replaced."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        out = np.array(pp, dtype=np.float32, copy=True)
+        gap = 20 if self.alphabet == _lib.ALPH_AMINO else 4
+        q = recs["pair"] // self.H
+        L = offsets[q + 1] - offsets[q]
+        Ld = (recs["env_j"] - recs["env_i"] + 1).astype(np.int64)
+        pick = np.nonzero((recs["pair"] % self.H == int(h)) & (recs["ali_i"] != 0) & (L > Ld))[0]
+        if len(pick) == 0:
+            return out
+        parts = []
+        for d in pick:
+            a = int(offsets[q[d]]) + int(recs["env_i"][d]) - 1
+            parts.append(residues[a:a + int(Ld[d])])
+            parts.append(np.full(int(L[d] - Ld[d]), gap, dtype=np.uint8))
+        poffs = np.zeros(len(pick) + 1, dtype=np.int64)
+        np.cumsum(L[pick], out=poffs[1:])
+        cols2, co, pp2 = self.align(np.concatenate(parts), poffs, np.arange(len(pick)), np.full(len(pick), int(h), dtype=np.int32), want_pp=True)
+        for i, d in enumerate(pick):
+            a, b, n = int(env_off[d]), int(co[i]), int(Ld[d])
+            same = (cols2[b:b + n] == cols[a:a + n]) & np.isfinite(pp2[b:b + n])
+            out[a:a + n][same] = pp2[b:b + n][same]
+        return out
+
+    def domain_paths_t(self, residues_t, offsets_t, max_len: int, flags_t, detail_t):
+        """domain_paths() on torch tensors resident on the device (wh_domain_counts_dev, wh_domain_paths_dev): (records as
+        a uint8 tensor [n, 56], dom_off int64 [nq * H + 1], env_off int64 [n + 1], cols int32, pp float32).  The last three
+        are DevView's of the handle's workspace (data_ptr(), numel()), valid until the next domains, domain_paths or hits_msa
+        call on the handle: what hits_msa_t and domain_display_t take."""
+        import torch
+        nq = offsets_t.numel() - 1
+        dev = residues_t.device
+        counts = torch.empty((nq, self.H), dtype=torch.int32, device=dev)
+        dom_off = torch.zeros(nq * self.H + 1, dtype=torch.int64, device=dev)
+        if nq:
+            check(lib().wh_domain_counts_dev(self._h, flags_t.data_ptr(), detail_t.data_ptr(), nq, counts.data_ptr(), None, self._stream()),
+                  "wh_domain_counts_dev")
+            dom_off[1:] = torch.cumsum(counts.reshape(-1), 0)
+        n = int(dom_off[-1].item())
+        out = torch.zeros((n, np.dtype(DOMAIN_FIELDS).itemsize), dtype=torch.uint8, device=dev)
+        p_env, p_cols, p_pp, total = C.c_void_p(None), C.c_void_p(None), C.c_void_p(None), C.c_int64(0)
+        if nq:
+            check(lib().wh_domain_paths_dev(self._h, residues_t.data_ptr(), offsets_t.data_ptr(), nq, residues_t.numel(), int(max_len),
+                                            flags_t.data_ptr(), detail_t.data_ptr(), dom_off.data_ptr(), out.data_ptr(), C.byref(p_env),
+                                            C.byref(p_cols), C.byref(p_pp), C.byref(total), self._stream()), "wh_domain_paths_dev")
+        t = int(total.value)
+        return out, dom_off, DevView(p_env.value, n + 1), DevView(p_cols.value, t), DevView(p_pp.value, t)
+
+    def domain_display_t(self, residues_t, offsets_t, flags_t, dom_off_t, dom_t, env_off_t, cols_t, pp_t, domE=10.0, domZ=1.0, h=0,
+                         cap=None, poison=None):
+        """The display stage alone (wh_domain_display_dev) on torch tensors resident on the device: the scoring call's residues,
+        offsets and flags, dom_off int64 [nq * H + 1], the wh_domain records (uint8 [n, 56]), the envelope CSR int64 [n + 1]
+        with its columns int32 and posteriors float32.  cap: bytes of each line array (default: n x M + the envelope
+        residues, which always suffices).  Returns domain_display's dict (numpy arrays); with poison (a byte value the output
+        arrays are filled with before the call) also "raw": the four whole arrays, disp_off and the records as numpy, for a
+        caller that checks what was NOT written."""
+        import torch
+        nq = offsets_t.numel() - 1
+        n = int(dom_t.shape[0])
+        dev = offsets_t.device
+        cap = n * (int(self.M[h]) if 0 <= int(h) < self.H else 0) + int(cols_t.numel()) if cap is None else int(cap)
+        fill = 0 if poison is None else int(poison)
+        off = torch.full((n + 1,), -1 if poison is not None else 0, dtype=torch.int64, device=dev)
+        recs = torch.full((max(n, 1), 8), fill, dtype=torch.uint8, device=dev)
+        lines = torch.full((4, max(cap, 1)), fill, dtype=torch.uint8, device=dev)
+        nsel, total = C.c_int64(0), C.c_int64(0)
+        check(lib().wh_domain_display_dev(self._h, residues_t.data_ptr(), offsets_t.data_ptr(), nq, flags_t.data_ptr(), dom_off_t.data_ptr(),
+                                          dom_t.data_ptr(), env_off_t.data_ptr(), cols_t.data_ptr(), pp_t.data_ptr(), int(h), float(domE),
+                                          float(domZ), cap, off.data_ptr(), recs.data_ptr(), lines[0].data_ptr(), lines[1].data_ptr(),
+                                          lines[2].data_ptr(), lines[3].data_ptr(), C.byref(nsel), C.byref(total), self._stream()),
+              "wh_domain_display_dev")
+        torch.cuda.current_stream().synchronize()
+        ns, tot = int(nsel.value), int(total.value)
+        keep = slice(None) if poison is not None else slice(0, tot)      # (the whole arrays only for a caller that inspects them)
+        h_off, h_recs, h_lines = off.cpu().numpy(), recs.cpu().numpy(), lines[:, keep].cpu().numpy()
+        m = self._display_result(ns, h_off[:ns + 1].copy(), h_recs[:ns].reshape(-1).view(np.dtype(_lib.DISPLAY_REC_FIELDS)).copy(),
+                                 [h_lines[t, :tot].copy() for t in range(4)])
+        m["total"] = tot
+        if poison is not None:
+            m["raw"] = {"disp_off": h_off, "recs": h_recs, "lines": h_lines, "cap": cap}
+        return m
 
     def last_align_status(self):
         """(pairs redone in log space, pair numbers the last align call returned UNALIGNED - all columns -1 -

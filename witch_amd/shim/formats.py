@@ -107,7 +107,7 @@ def _hmmsearch_tail(out, hdr, n_targets, passed=None, trailer=None):
 
 
 def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets, domains=None, lengths=None, Z=None, domZ=None, domE=10.0,
-                     incE=0.01, incdomE=0.01, passed=None, trailer=None):
+                     incE=0.01, incdomE=0.01, passed=None, trailer=None, display=None):
     """rows: [(name, bits, bias_bits, n_domains)] of the REPORTED sequences.  The table is what
     evalHMMSearchOutput reads: a line starting with 'E-value', then >= 9 whitespace-separated
     fields per row (E-value, score, bias, best-domain E-value/score/bias, exp, N, name), a blank
@@ -116,9 +116,11 @@ def format_hmmsearch(hmm_path, fasta_path, hdr, rows, n_targets, domains=None, l
     unrounded score as a fifth element, for the E-values) they hold the
     i-Evalue, score and bias of the pair's best domain (the highest envelope score), N is the number of reportable
     domains (incE / incdomE decide the '!' marks), and HMMER's "Domain annotation for each sequence" section (its ">> name" tables, as under --noali) follows.
-    passed: the stage counts and thresholds of a filtered search (_hmmsearch_tail); None under --max.  trailer: see there."""
+    passed: the stage counts and thresholds of a filtered search (_hmmsearch_tail); None under --max.  trailer: see there.
+    display (with <domains> only): the alignment display, see _format_hmmsearch_domains; None: the output of --noali."""
     if domains is not None:
-        return _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE, passed, trailer)
+        return _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE, passed, trailer,
+                                         display)
     out, namew = _hmmsearch_head(hmm_path, fasta_path, hdr, rows)
     for name, bits, bias, ndom in sorted(rows, key=lambda r: -r[1]):
         ev = forward_evalue(bits, n_targets, hdr["ftau"], hdr["flambda"])
@@ -152,7 +154,8 @@ def hit_order(rows, hdr):
 
 def domain_entries(hdr, rows, lengths, domains, n_targets, Z=None, domZ=None, domE=10.0, incE=0.01, incdomE=0.01):
     """One dict per domain of every reported sequence, in HMMER's output order, with the 22 columns of a --domtblout
-    line as numbers (DOMTBL_COLUMNS) plus "reportable" (c-Evalue <= domE) and "included" (the '!' of a domain table: the
+    line as numbers (DOMTBL_COLUMNS) plus "c_evalue_ftz" (the c-Evalue as the reference's binary evaluates it, a P-value below
+    the smallest normal double flushed to 0: _pvalue; the alignment display's header prints it), "reportable" (c-Evalue <= domE) and "included" (the '!' of a domain table: the
     sequence's E-value <= incE and the domain's c-Evalue <= incdomE, hmmsearch's --incE / --incdomE, default 0.01).
     domains: {name: [records]}, a record having index, of, env_i, env_j, ali_i, ali_j, hmm_i, hmm_j, bits, bias_bits, oasc,
     lnP (the fields of wh_domain).  Z defaults to the number of targets, domZ to the number of reported sequences; "#" and
@@ -172,7 +175,7 @@ def domain_entries(hdr, rows, lengths, domains, n_targets, Z=None, domZ=None, do
                         "dom_score": float(d["bits"]), "dom_bias": float(d["bias_bits"]),
                         "hmm_from": int(d["hmm_i"]), "hmm_to": int(d["hmm_j"]), "ali_from": int(d["ali_i"]),
                         "ali_to": int(d["ali_j"]), "env_from": int(d["env_i"]), "env_to": int(d["env_j"]),
-                        "acc": float(d["oasc"]) / Ld, "reportable": p * domZ <= domE,
+                        "acc": float(d["oasc"]) / Ld, "c_evalue_ftz": _pvalue(float(d["lnP"])) * domZ, "reportable": p * domZ <= domE,
                         "included": ev <= incE and p * domZ <= incdomE})
     return out
 
@@ -325,8 +328,68 @@ def format_domain_table(name, entries, M, L):
     return out
 
 
+def format_alidisplay(hmm_name, seq_name, hmm_from, ali_from, model, mline, aseq, ppline, textw=120):
+    """The lines of one domain's alignment under its "== domain" header, as HMMER 3.1b2's p7_alidisplay_Print lays them out.
+    model, mline, aseq, ppline: the four lines of EHMM.domain_display, one character per column (str, bytes or uint8 arrays).
+    Names are right-aligned to the longer of the two; the start coordinates are right-aligned and the end coordinates
+    left-aligned to the widest of the domain's four coordinates.  The columns are wrapped into blocks of
+    textw - name width - 2 x coordinate width - 5 columns (at least 40 where that does not hold the whole alignment), a blank
+    line between two blocks, each block with the coordinates of its own first and last node and residue; textw None
+    (--notextw): one block.  A block whose target line holds no residue has "-" for both target coordinates."""
+    model, mline, aseq, ppline = _text(model), _text(mline), _text(aseq), _text(ppline)
+    N = len(model)
+    hmm_to = hmm_from + sum(1 for c in model if c != ".") - 1
+    ali_to = ali_from + sum(1 for c in aseq if c != "-") - 1
+    namew = max(len(hmm_name), len(seq_name))
+    cw = max(len(str(v)) for v in (hmm_from, hmm_to, ali_from, ali_to))
+    aliw = N if textw is None else textw - namew - 2 * cw - 5
+    if aliw < N and aliw < 40:
+        aliw = 40
+    out, k1, i1 = [], hmm_from, ali_from
+    for pos in range(0, N, max(aliw, 1)):
+        if pos:
+            out.append("")
+        mo, aq = model[pos:pos + aliw], aseq[pos:pos + aliw]
+        nk, ni = sum(1 for c in mo if c != "."), sum(1 for c in aq if c != "-")
+        out.append("  %*s %*d %s %-*d" % (namew, hmm_name, cw, k1, mo, cw, k1 + nk - 1))
+        out.append("  %*s %*s %s" % (namew, " ", cw, " ", mline[pos:pos + aliw]))
+        if ni > 0:
+            out.append("  %*s %*d %s %-*d" % (namew, seq_name, cw, i1, aq, cw, i1 + ni - 1))
+        else:
+            out.append("  %*s %*s %s %*s" % (namew, seq_name, cw, "-", aq, cw, "-"))
+        out.append("  %*s %*s %s PP" % (namew, "", cw, "", ppline[pos:pos + aliw]))
+        k1 += nk
+        i1 += ni
+    return out
+
+
+def format_domain_alignments(hmm_name, seq_name, entries, lines, textw=120):
+    """The "Alignments for each domain:" part behind one sequence's domain table: per reportable domain its header (its
+    number among the sequence's REPORTABLE domains, as HMMER counts them; "%.1f" score, "%.2g" conditional E-value),
+    format_alidisplay's lines and a blank line.  entries: the
+    sequence's domain_entries; lines: {domain number - 1: (model, mline, aseq, ppline)}.  A sequence without a reportable
+    domain gets nothing (its table says so already).  A reportable domain without lines - one the alignment gave no path -
+    keeps its header and says so in brackets."""
+    shown = [e for e in entries if e["reportable"]]
+    if not shown:
+        return []
+    out = ["  Alignments for each domain:"]
+    for nd, e in enumerate(shown, 1):
+        out.append("  == domain %d  score: %.1f bits;  conditional E-value: %.2g" % (nd, e["dom_score"], e.get("c_evalue_ftz", e["c_evalue"])))
+        four = lines.get(e["num"] - 1)
+        if four is None:
+            out.append("   [No alignment is displayed for this domain: it has no path]")
+        else:
+            out.extend(format_alidisplay(hmm_name, seq_name, e["hmm_from"], e["ali_from"], *four, textw=textw))
+        out.append("")
+    return out
+
+
 def _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domains, lengths, Z, domZ, domE, incE, incdomE, passed=None,
-                              trailer=None):
+                              trailer=None, display=None):
+    """display: None (the output of --noali), or {"lines": {name: {domain index: (model, mline, aseq, ppline)}}, "textw":
+    the text width or None}: the section's title says "(and alignments)" and every domain table is followed by
+    format_domain_alignments."""
     entries = domain_entries(hdr, rows, lengths, domains, n_targets, Z, domZ, domE, incE, incdomE)
     by_name = {}
     for e in entries:
@@ -348,9 +411,12 @@ def _format_hmmsearch_domains(hmm_path, fasta_path, hdr, rows, n_targets, domain
                    (_g(ev), bits, bias, _g(bev), bsc, bbias, float(max(ndom, 1)), nrep, namew, name))
     out.append("")
     out.append("")
-    out.append("Domain annotation for each sequence:")
+    out.append("Domain annotation for each sequence:" if display is None else "Domain annotation for each sequence (and alignments):")
     for row in order:
         out.extend(format_domain_table(row[0], by_name.get(row[0], []), hdr["M"], lengths[row[0]]))
+        if display is not None:
+            out.extend(format_domain_alignments(hdr["name"], row[0], by_name.get(row[0], []), display["lines"].get(row[0], {}),
+                                                display.get("textw", 120)))
     return _hmmsearch_tail(out, hdr, n_targets, passed, trailer)
 
 
@@ -398,6 +464,23 @@ def hmm_has_rf(path):
             if w and w[0] == "HMM":
                 break
     return False
+
+
+def hmm_display_keys(path):
+    """{"CONS", "RF", "CS": bool} of a model file's header: what decides whether its alignments can be displayed."""
+    keys = {"CONS": False, "RF": False, "CS": False}
+    opener = open
+    if str(path).endswith(".gz"):
+        import gzip
+        opener = gzip.open
+    with opener(path, "rt") as f:
+        for line in f:
+            w = line.split()
+            if w and w[0] in keys:
+                keys[w[0]] = len(w) > 1 and w[1].lower() == "yes"
+            if w and w[0] == "HMM":
+                break
+    return keys
 
 
 def stockholm_pp_lines(row, pp, rf=True):

@@ -93,6 +93,29 @@ def bias_filter_enabled():
     return os.environ.get("WITCH_HIP_BIAS_FILTER", "") == "1"
 
 
+def alidisplay_enabled():
+    """WITCH_HIP_ALIDISPLAY=1 in the server's environment: a line without --noali gets hmmsearch's alignment display (the
+    four lines under "== domain N" of every reported domain, rendered on the GPU: wh_domain_display).  An opt-in for now, as
+    the bias filter is; it becomes the default later.  Unset, every line is answered as with --noali."""
+    return os.environ.get("WITCH_HIP_ALIDISPLAY", "") == "1"
+
+
+def display_textw(opts):
+    """The text width of the alignment display: --textw N (HMMER refuses N < 120, so does this), --notextw: None (one
+    block), else 120."""
+    if "--notextw" in opts:
+        return None
+    if "--textw" not in opts:
+        return 120
+    try:
+        w = int(opts["--textw"])
+    except ValueError:
+        raise ArgError("Failed to parse command line: option --textw takes integer arg; got %s" % opts["--textw"])
+    if w < 120:
+        raise ArgError("Failed to parse command line: option --textw takes integer arg in range n>=120; got %s on cmdline" % opts["--textw"])
+    return w
+
+
 def check_hmmsearch_options(opts):
     """The GPU path computes what WITCH's own command lines ask for (algorithm.py:526-532): a reporting threshold that
     lets every hit through, and either `--max` (no filters) or the filtered search of WITCH's `filters` switch - the MSV,
@@ -111,8 +134,11 @@ def check_hmmsearch_options(opts):
     --tblout FILE is written as well: the per-sequence table of wh_seq_table, alone or together with --domtblout and -A
     (-Z, --domZ, -E, --domE, --incE and --incdomE are read and checked for it as for --domtblout); a backend without
     search_table refuses the option by name.
-    One thing stays unimplemented and is accepted as a no-op: the alignment display (the output is always that of
-    --noali)."""
+    The alignment display - what hmmsearch prints by default under every domain table - is written where the server's
+    environment has WITCH_HIP_ALIDISPLAY=1 and the line has no --noali (alidisplay_enabled; --textw N and --notextw apply,
+    --domE, -Z and --domZ are read and checked for it as for --domtblout; a backend without search_display refuses such a
+    line by name; a model with "RF yes", "CS yes" or without "CONS yes" is refused by the library).  Without the variable the
+    display stays a no-op: the output is that of --noali, as before."""
     if "--max" not in opts and "--nobias" not in opts and not bias_filter_enabled():
         raise ArgError("witch-hip hmmsearch shim: the filtered search is implemented without HMMER's bias filter only: "
                        "pass --nobias (MSV, Viterbi and Forward filters at --F1 --F2 --F3), or --max (no filters; "
@@ -134,7 +160,10 @@ def check_hmmsearch_options(opts):
             if o == "-E" and v < 1e6:
                 raise ArgError("witch-hip hmmsearch shim: -E %s would drop hits; only E >= 1e6 (WITCH: 99999999) "
                                "is supported, every sequence with a domain is reported" % opts[o])
-    for o in (("-Z", "--domZ") if "--domtblout" in opts or "-A" in opts or "--tblout" in opts else ()):      # (read only for the per-domain output, -A and --tblout; else ignored as before)
+    shown = alidisplay_enabled() and "--noali" not in opts
+    if shown:
+        display_textw(opts)
+    for o in (("-Z", "--domZ") if "--domtblout" in opts or "-A" in opts or "--tblout" in opts or shown else ()):      # (read only for the per-domain output, -A and --tblout; else ignored as before)
         if o in opts:
             try:
                 ok = float(opts[o]) > 0
@@ -225,9 +254,17 @@ class GpuBackend:
         The rows carry the unrounded score, as for --domtblout."""
         return self._search(hmm_path, records, want_domains, filters, inc, bias, table)
 
-    def _search(self, hmm_path, records, want_domains, filters, inc, bias=False, table=None):
+    def search_display(self, hmm_path, records, display, inc=None, table=None, filters=None, bias=False):
+        """search() for a line that shows the alignments: (header, rows, domains, hits or None, table rows or None, lines).
+        display: {"domE", "domZ"} (domZ None: the number of reported sequences); lines: {name: {domain index: (model, match
+        line, target, PP)}} of the reportable domains (EHMM.display_lines).  inc / table: as for search_hits / search_table,
+        when -A / --tblout are asked for on the same line.  There is ONE domain stage (wh_domain_paths_dev): the domain
+        records, the display and the rows of -A all come from that one domain stage."""
+        return self._search(hmm_path, records, True, filters, inc, bias, table, display)
+
+    def _search(self, hmm_path, records, want_domains, filters, inc, bias=False, table=None, display=None):
         from witch_amd.ehmm import pack_queries
-        domains, hits, tbl = {}, None, None
+        domains, hits, tbl, lines = {}, None, None, None
         with self.lock:
             e, hdr = self.model(hmm_path)
             seqs = [e.digitize(t.upper()) for _, t in records]     # alignment_tools.py:730-731 upper-cases
@@ -246,7 +283,9 @@ class GpuBackend:
                     bias = max(0.0, float(d.pre_score) - float(d.seq_score))
                     rows.append((name, deci[i, 0] / 10.0, bias, int(d.nenv)) + ((float(d.seq_score),) if exact else ()))
             recs = dom_off = None
-            if inc is not None:
+            if display is not None:
+                recs, dom_off, hits, lines = self._shared_domain_stage(e, hdr, records, res, offs, flags, det, rows, inc, display)
+            elif inc is not None:
                 at = {name: i for i, (name, _) in enumerate(records)}
                 first = [at[r[0]] for r in formats.hit_order(rows, hdr)]
                 order = first + sorted(set(range(len(records))) - set(first))
@@ -268,7 +307,38 @@ class GpuBackend:
                         domains[name] = lst
             if table is not None:
                 tbl = e.seq_table(res, offs, flags, det, **table)
-        return hdr, rows, (domains if want_domains else None), hits, tbl
+        return (hdr, rows, (domains if want_domains else None), hits, tbl) + (() if display is None else (lines,))
+
+    def _shared_domain_stage(self, e, hdr, records, res, offs, flags, det, rows, inc, display):
+        """ONE domain stage (EHMM.domain_paths), then the stages that read its records, columns and posteriors on the device:
+        the display, and the hit selection of -A where it is asked for.  The display's PP line takes hmmsearch's own
+        posteriors, decoded under the whole sequence's length model (EHMM.sequence_model_posteriors: one more alignment
+        launch over the envelopes that are shorter than their sequence); the domain records and -A keep the stage's.
+        Returns (domain records, dom_off, hits or None, display lines)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+        nq = len(records)
+        recs, dom_off, env_off, cols, pp = e.domain_paths(res, offs, flags, det)
+        pp_seq = e.sequence_model_posteriors(res, offs, recs, env_off, cols, pp, h=0)
+        with torch.cuda.device(dev):
+            res_t, offs_t, flags_t = up(res), up(offs), up(np.asarray(flags).reshape(-1))
+            dom_t, dom_off_t = up(recs.view(np.uint8).reshape(len(recs), -1)), up(dom_off)
+            env_t, cols_t = up(env_off), up(cols)
+            domZ = max(len(rows), 1) if display.get("domZ") is None else display["domZ"]
+            disp = e.domain_display_t(res_t, offs_t, flags_t, dom_off_t, dom_t, env_t, cols_t, up(pp_seq), domE=display.get("domE", 10.0),
+                                      domZ=domZ, h=0)
+            hits = None
+            if inc is not None:
+                at = {name: i for i, (name, _) in enumerate(records)}
+                first = [at[r[0]] for r in formats.hit_order(rows, hdr)]
+                order = first + sorted(set(range(nq)) - set(first))
+                text_t = up(np.frombuffer("".join(t for _, t in records).encode(), dtype=np.uint8).copy())
+                det_t = up(np.frombuffer(bytes(det), dtype=np.uint8).copy())
+                hits = e.hits_msa_t(text_t, offs_t, flags_t, det_t, dom_off_t, dom_t, env_t, cols_t, up(pp),
+                                    Z=nq if inc.get("Z") is None else inc["Z"], domZ=max(len(rows), 1) if inc.get("domZ") is None else inc["domZ"],
+                                    incE=inc.get("incE", 0.01), incdomE=inc.get("incdomE", 0.01), h=0, order_t=up(np.array(order, dtype=np.int32)))
+        return recs, dom_off, hits, e.display_lines(disp, [n for n, _ in records])
 
     def align(self, jobs):
         """jobs: [(hmm_path, name, text)] -> [(M, cols, pp)]; one launch per distinct model.  pp: the posterior
@@ -369,6 +439,8 @@ class Server:
         if F is not None and "--nobias" not in opts:        # (accepted above only where the bias filter is switched on)
             fkw["bias"] = True
         passed = lambda: None if F is None else (self.backend.last_passed, F)
+        if alidisplay_enabled() and "--noali" not in opts:
+            return self.run_hmmsearch_display(opts, hmm, fa, cwd, fkw, passed, argv)
         if "--tblout" in opts:
             return self.run_hmmsearch_table(opts, hmm, fa, cwd, fkw, passed, argv)
         if "-A" in opts:
@@ -386,6 +458,54 @@ class Server:
         else:
             hdr, rows = self.backend.search(hmm, records, **fkw)
             text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records), passed=passed())
+        if "-o" in opts:
+            with open(os.path.join(cwd, opts["-o"]), "w") as f:
+                f.write(text)
+            return ""
+        return text
+
+    def run_hmmsearch_display(self, opts, hmm, fa, cwd, fkw, passed, argv):
+        """A line without --noali where the display is switched on (alidisplay_enabled): the main output carries hmmsearch's
+        "(and alignments)" section - every domain table followed by the alignment of its reportable domains, wrapped to
+        --textw N (default 120; --notextw: one block).  --domtblout, -A and --tblout on the same line are written as they are
+        without the display, and share its one alignment of the envelopes."""
+        if not hasattr(self.backend, "search_display"):
+            raise ArgError("witch-hip hmmsearch shim: the alignment display (WITCH_HIP_ALIDISPLAY=1, no --noali) needs a backend "
+                           "that renders the domain alignments (search_display); this one does not, and the request is not ignored: "
+                           "pass --noali")
+        textw = display_textw(opts)
+        keys = formats.hmm_display_keys(hmm)
+        for k, want, why in (("CONS", True, "has no consensus line to print"), ("RF", False, "has a reference line, which HMMER prints above the alignment"),
+                             ("CS", False, "has a consensus structure line, which HMMER prints above the alignment")):
+            if keys[k] != want:
+                raise ArgError("witch-hip hmmsearch shim: the alignment display is implemented for models with CONS yes, RF no and CS no; "
+                               "%s says %s %s (it %s): pass --noali" % (hmm, k, "yes" if keys[k] else "no", why))
+        desc = {}
+        records = formats.read_fasta(fa, descriptions=desc)
+        kw = {"Z": float(opts["-Z"]) if "-Z" in opts else None, "domZ": float(opts["--domZ"]) if "--domZ" in opts else None}
+        inc = {"incE": float(opts.get("--incE", 0.01)), "incdomE": float(opts.get("--incdomE", 0.01))}
+        domE = float(opts.get("--domE", 10.0))
+        table = dict(kw, E=float(opts.get("-E", 10.0)), domE=domE, **inc) if "--tblout" in opts else None
+        hdr, rows, domains, hits, tbl, lines = self.backend.search_display(hmm, records, {"domE": domE, "domZ": kw["domZ"]},
+                                                                           inc=dict(inc, **kw) if "-A" in opts else None, table=table, **fkw)
+        trailer = formats.hits_msa_trailer(len(hits["row_recs"]), opts["-A"]) if "-A" in opts else None
+        lengths = {n: len(t) for n, t in records}
+        kw["domE"] = domE
+        text = formats.format_hmmsearch(hmm, fa, hdr, rows, len(records), domains=domains, lengths=lengths, passed=passed(),
+                                        trailer=trailer, display={"lines": lines, "textw": textw}, **kw, **inc)
+        if "--domtblout" in opts:
+            with open(os.path.join(cwd, opts["--domtblout"]), "w") as f:
+                f.write(formats.format_domtblout(hmm, fa, hdr, rows, lengths, domains, len(records), **kw))
+        if "-A" in opts:
+            with open(os.path.join(cwd, opts["-A"]), "w") as f:
+                f.write(formats.format_hits_msa([n for n, _ in records], hits["row_recs"], hits["rows"], hits["pp_rows"], hits["pp_cons"],
+                                                None if formats.hmm_has_rf(hmm) else hits["rf"], descriptions=desc,
+                                                notextw="--notextw" in opts))
+        if "--tblout" in opts:
+            entries = formats.seq_table_entries(hdr, [n for n, _ in records], tbl, len(records), Z=table["Z"], descriptions=desc)
+            with open(os.path.join(cwd, opts["--tblout"]), "w") as f:
+                f.write(formats.format_tblout(hmm, fa, hdr, entries, option_settings="hmmsearch " + " ".join(argv), cwd=cwd,
+                                              date=time.ctime()))
         if "-o" in opts:
             with open(os.path.join(cwd, opts["-o"]), "w") as f:
                 f.write(text)
