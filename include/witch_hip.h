@@ -220,6 +220,21 @@ int wh_align_pp64_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_of
                       int64_t total_residues, int32_t max_len,
                       const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
                       const int64_t *d_col_offsets, int32_t *d_cols, double *d_pp, void *stream);
+/* wh_align_pp[_dev] under a length model of the caller's choice: cfg_len[nq] (int32, >= 1) is, per query, the number of
+ * residues the unihit length model of its pairs is configured for - the N and C loops are cfg_len / (cfg_len + 2) where
+ * wh_align_pp takes the query's own length.  That is how hmmsearch aligns an envelope: as Ld residues under the length model
+ * of the whole sequence of L (cfg_len = L), which equals aligning the envelope followed by L - Ld residues that every state
+ * emits with odds 1.  Only the length configuration changes: rows, workspace, launch planning, node windows and the
+ * hand-overs follow the residues given, and the precision is wh_align_pp's.  cfg_len == NULL is wh_align_pp[_dev] itself,
+ * bit for bit.  The host-pointer variant refuses an entry < 1 (WH_EINVAL, wh_last_error names the query); the _dev variant
+ * does not read the array on the host, and its kernels take an entry < 1 as 1. */
+int wh_align_pp_len(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq,
+                    const int64_t *pair_q, const int32_t *pair_h, int64_t npairs,
+                    const int64_t *col_offsets, int32_t *cols, float *pp, const int32_t *cfg_len);
+int wh_align_pp_len_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq,
+                        int64_t total_residues, int32_t max_len,
+                        const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
+                        const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, const int32_t *d_cfg_len, void *stream);
 
 /* ---- per-domain results (hmmsearch's "Domain annotation for each sequence" section and --domtblout; no reference code
  * calls either - witch_msa reads the per-sequence table alone) -------------------------------------------------------
@@ -228,6 +243,10 @@ int wh_align_pp64_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_of
  * alignment under the unihit length model of Ld = env_j - env_i + 1 residues.  On domains that HMMER prints with an
  * accuracy of 0.95 or more that is hmmsearch's own alignment, coordinate for coordinate; on weaker ones hmmsearch usually
  * prints the same alignment with columns trimmed at an end (the agreement per stratum).
+ * That is the default, WH_LENMODEL_ENVELOPE.  Under wh_set_domain_length_model(e, WH_LENMODEL_SEQUENCE) the envelope is aligned
+ * under the length model of its whole sequence of L residues (wh_align_pp_len with cfg_len = L), as hmmsearch does it: ali_*,
+ * hmm_*, oasc, the columns and the posteriors are then hmmsearch's on the weak domains too; env_*, bits, bias_bits and lnP do
+ * not depend on the alignment and are the same bits under either setting.
  * bits, bias_bits and lnP follow HMMER's float32 arithmetic (L: the query's length):
  *   bits = (envsc + (L - Ld) ln(L / (L + 3)) - nullsc - dombias) / ln 2,  nullsc = L ln(L / (L + 1)) + ln(1 / (L + 1)),
  *   dombias = logsum(0, ln(1 / 256) + domcorr),  bias_bits = dombias / ln 2,  lnP = min(0, -lambda (bits - tau))
@@ -274,6 +293,16 @@ int wh_domains_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offse
                    int64_t total_residues, int32_t max_len,
                    const uint8_t *d_flags, const wh_pair_detail *d_detail, const int64_t *d_dom_off, wh_domain *d_out,
                    void *stream);
+/* The length model the domain stage aligns an envelope under - handle state, for production use (no development knob):
+ * WH_LENMODEL_ENVELOPE (the default): the envelope's own Ld residues, hmmalign's alignment of the envelope;
+ * WH_LENMODEL_SEQUENCE: the L residues of the envelope's sequence, hmmsearch's own alignment.  Under the latter the stage's
+ * list kernel also writes each domain's sequence length, and the stage's one alignment call passes that array as d_cfg_len.
+ * Everything behind that call follows: wh_domains*, wh_domain_paths*, wh_hits_msa and wh_domain_display.  Any other value:
+ * WH_EINVAL.  wh_get_domain_length_model returns the setting (WH_EINVAL for a null handle).  Neither needs the device. */
+#define WH_LENMODEL_ENVELOPE 0
+#define WH_LENMODEL_SEQUENCE 1
+int wh_set_domain_length_model(wh_ehmm *e, int model);
+int wh_get_domain_length_model(const wh_ehmm *e);
 /* The Forward E-value parameters of every model, from its "STATS LOCAL FORWARD tau lambda" line (hmmbuild writes it, as
  * does wh_hmmbuild2 / wh_hmmbuild_batch with WH_BUILD_STATS): tau[H], lambda[H], present[H] (each optional); a model without
  * the line loads as before and has present = 0, tau = lambda = NaN.  Needs no device. */
@@ -631,9 +660,10 @@ int wh_hits_msa_dev(wh_ehmm *e, const uint8_t *d_text, const int64_t *d_offsets,
  * their own paths (nodes rising from hmm_i to hmm_j): WH_EINVAL otherwise.  Three kernels - count (one wavefront per domain),
  * a two-level scan, render (one wavefront per domain) - and one wait of the host between count and render, after a first
  * one for dom_off's last entry.  wh_last_kernel_ms(9): these kernels with that wait.
- * The PP line encodes the posteriors it is given: wh_domain_paths_dev's are hmmalign's, under the length model of the envelope,
- * where hmmsearch decodes an envelope under the length model of its whole sequence (the level-0 server passes those:
- * DESIGN.md section 4.15).
+ * The PP line encodes the posteriors it is given.  Under WH_LENMODEL_ENVELOPE (the default) wh_domain_paths_dev's are
+ * hmmalign's, under the length model of the envelope, where hmmsearch decodes an envelope under the length model of its whole
+ * sequence (the level-0 server then passes those from a second alignment launch: DESIGN.md section 4.15).  Under
+ * WH_LENMODEL_SEQUENCE the stage's path and posteriors are hmmsearch's already.
  * wh_domain_display takes host pointers and runs wh_domain_paths_dev first (wh_last_kernel_ms(5): that domain stage);
  * out_dom (optional, [dom_off[nq x H]]) receives the wh_domain records; *out_disp_off, *out_recs and the four lines are
  * malloc'ed (release with wh_free_text; NULL where nothing is selected).

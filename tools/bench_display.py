@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--nq", type=int, default=2000)
     ap.add_argument("--nh", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--length-model", default="envelope", choices=("envelope", "sequence"),
+                    help="the domain stage's length model (EHMM.set_domain_length_model)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -48,6 +50,7 @@ def main():
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")      # noqa: E731
     res_t, offs_t = up(res), up(offs)
     max_len = int(np.diff(offs).max())
+    e.set_domain_length_model(args.length_model)
     e.set_timing(True)
     runs = []
     for r in range(args.repeats + 1):                            # the first pass loads the code objects: reported apart

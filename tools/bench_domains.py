@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--nq", type=int, default=2000)
     ap.add_argument("--nh", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--length-model", default="envelope", choices=("envelope", "sequence"),
+                    help="the domain stage's length model (EHMM.set_domain_length_model)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -45,6 +47,7 @@ def main():
         _, seqs = synth.make_queries(fam, seed + 1, args.nq, qlen)
         e = EHMM(eh.paths, hmm_index=eh.index, nseq=eh.nseq)
     res, offs = pack_queries([s.astype(np.uint8) for s in seqs])
+    e.set_domain_length_model(args.length_model)
     e.set_timing(True)
     runs = []
     for r in range(args.repeats + 1):                            # the first pass loads the code objects: reported apart

@@ -23,6 +23,7 @@ ALPH_DNA, ALPH_RNA, ALPH_AMINO = 0, 1, 2
 WH_OK, WH_EINVAL, WH_EIO, WH_ENODEV, WH_EHIP, WH_ERANGE, WH_ENOMEM = 0, -1, -2, -3, -4, -5, -6      # include/witch_hip.h
 WH_BUILD_STATS, WH_BUILD_CALIB_NO_LDS = 1, 4
 WH_MSA_TRIM, WH_MSA_NO_LDS, WH_MSA_CONS_HMMER = 1, 2, 4
+WH_LENMODEL_ENVELOPE, WH_LENMODEL_SEQUENCE = 0, 1
 PATH_P2_WIN, PATH_P2_FULL, PATH_P4_W256, PATH_P4_W512, PATH_P4_WFAIL, PATH_P4_FULL, PATH_DENSE, PATH_MULTI = 1, 2, 4, 8, 16, 32, 64, 128
 
 
@@ -124,6 +125,10 @@ SYMBOLS = {
     "wh_align_pp_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "wh_align_pp64": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P]),
     "wh_align_pp64_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "wh_align_pp_len": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "wh_align_pp_len_dev": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    "wh_set_domain_length_model": (C.c_int, [_P, C.c_int]),
+    "wh_get_domain_length_model": (C.c_int, [_P]),
     "wh_domain_counts": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P]),
     "wh_domain_counts_dev": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P]),
     "wh_domains": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P]),

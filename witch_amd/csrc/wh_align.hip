@@ -608,6 +608,9 @@ __global__ __launch_bounds__(SWAP ? 256 : 512) void align_kernel(KArgs a) {
       const int64_t qi = active ? a.pair_q[pair] : 0;
       const int64_t off = a.offsets[qi];
       const int L = active ? (int)(a.offsets[qi + 1] - off) : 0;
+      // the length the pair's length model is configured for: the query's own, or the caller's (hmmsearch configures the
+      // profile for the whole sequence and aligns its envelopes under that).  Rows, slabs and the window decision keep L.
+      const int Lcfg = a.cfg_len ? max(a.cfg_len[qi], 1) : (L > 0 ? L : 1);
       int32_t *cols = a.cols + (active ? a.col_offsets[pair] : 0);
       WH_PP(const PPOut pp(a.pp, a.pp64, active ? a.col_offsets[pair] : 0);)
       for (int t = lane; t < L; t += kWave) cols[t] = -1;
@@ -618,7 +621,7 @@ __global__ __launch_bounds__(SWAP ? 256 : 512) void align_kernel(KArgs a) {
         seq[t] = (uint8_t)(c < a.Kp ? c : a.Kp - 1);
       }
       __builtin_amdgcn_wave_barrier();
-      const LenCfg cu = len_config(L > 0 ? L : 1, false);
+      const LenCfg cu = len_config(Lcfg, false);
       const long long t_pair = a.wcyc ? (long long)__builtin_readcyclecounter() : 0;
 
       // ---------------- unihit Forward, rows spilled to slab A: sparsely for the node-window attempt (a query short

@@ -488,11 +488,19 @@ int wh_align(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_
 }
 
 static int align_host(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
-                      const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols, void *pp, bool pp_is64);
+                      const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols, void *pp, bool pp_is64, const int32_t *cfg_len = nullptr);
 
 int wh_align_pp(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
                 const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols, float *pp) {
   return align_host(e, residues, offsets, nq, pair_q, pair_h, npairs, col_offsets, cols, pp, false);
+}
+
+int wh_align_pp_len(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
+                    const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols, float *pp, const int32_t *cfg_len) {
+  // (checked before anything else: the refusal needs neither a handle nor a device)
+  for (int64_t q = 0; cfg_len && q < nq; q++)
+    if (cfg_len[q] < 1) { set_error("wh_align_pp_len: cfg_len[%lld] = %d: the length model of query %lld needs a length of 1 or more", (long long)q, cfg_len[q], (long long)q); return WH_EINVAL; }
+  return align_host(e, residues, offsets, nq, pair_q, pair_h, npairs, col_offsets, cols, pp, false, cfg_len);
 }
 
 int wh_align_pp64(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
@@ -501,7 +509,7 @@ int wh_align_pp64(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, i
 }
 
 static int align_host(wh_ehmm *e, const uint8_t *residues, const int64_t *offsets, int64_t nq, const int64_t *pair_q,
-                      const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols, void *pp, bool pp_is64) {
+                      const int32_t *pair_h, int64_t npairs, const int64_t *col_offsets, int32_t *cols, void *pp, bool pp_is64, const int32_t *cfg_len) {
   const size_t ppw = pp_is64 ? sizeof(double) : sizeof(float);
   if (!e || !residues || !offsets || !pair_q || !pair_h || !col_offsets || !cols || nq < 0 || npairs < 0) {
     set_error("wh_align: bad argument");
@@ -523,7 +531,9 @@ static int align_host(wh_ehmm *e, const uint8_t *residues, const int64_t *offset
   const int64_t *d_co = st.in(col_offsets, sizeof(int64_t) * (size_t)(npairs + 1));
   int32_t *d_cols = st.out(cols, sizeof(int32_t) * (size_t)ncols, 16);
   void *d_pp = st.inout(pp, ppw * (size_t)ncols, 16);      // what lies between the pairs' ranges comes back as given
+  const int32_t *d_cfg = st.in(cfg_len, sizeof(int32_t) * (size_t)nq);
   if (st.rc) return st.rc;
+  if (cfg_len) return st.finish(wh_align_pp_len_dev(e, d_res, d_off, nq, total, max_len, d_pq, d_ph, npairs, d_co, d_cols, (float *)d_pp, d_cfg, nullptr));
   return st.finish(pp_is64 && pp ? wh_align_pp64_dev(e, d_res, d_off, nq, total, max_len, d_pq, d_ph, npairs, d_co, d_cols, (double *)d_pp, nullptr)
                                  : wh_align_pp_dev(e, d_res, d_off, nq, total, max_len, d_pq, d_ph, npairs, d_co, d_cols, (float *)d_pp, nullptr));
 }

@@ -55,6 +55,7 @@ __global__ __launch_bounds__(256) void domain_list_kernel(DomainArgs a) {
     const int ei = d.env_i[t], ej = d.env_j[t];
     a.dom_pair[lo + t] = p;
     a.dom_len[lo + t] = (ei >= 1 && ei <= ej && ej <= L) ? ej - ei + 1 : -1;
+    if (a.dom_seqlen) a.dom_seqlen[lo + t] = (int32_t)(L > 0x7FFFFFFF ? 0x7FFFFFFF : L);
   }
 }
 

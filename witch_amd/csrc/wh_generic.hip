@@ -644,8 +644,9 @@ __global__ __launch_bounds__(64, 3) void WH_GENERIC_ALIGN(GenericAlignArgs a) {
     double *oxs = pps + (size_t)(a.Lcap + 2) * xNSPEC;                        // OA special states per row
     const int64_t off = a.offsets[qi];
     const int L = (int)(a.offsets[qi + 1] - off);
+    const int Lcfg = a.cfg_len ? max(a.cfg_len[qi], 1) : L;                  // the length model's length (GenericAlignArgs::cfg_len)
     int32_t *cols = a.cols + a.col_off[p];
-    PPOut ppo;                                                               // (a double array is filled without rounding to float)
+    PPOut ppo;                                                              // (a double array is filled without rounding to float)
     if constexpr (PP) ppo = PPOut(a.pp, a.pp64, a.col_off[p]);
     double *ppsave = PP ? slab + a.pp_off : nullptr;                        // unrounded ppM / ppI per row: the OA fill below overwrites the rows
     for (int t = lane; t < L; t += 64) cols[t] = -1;
@@ -653,7 +654,7 @@ __global__ __launch_bounds__(64, 3) void WH_GENERIC_ALIGN(GenericAlignArgs a) {
     if (L <= 0 || L > a.Lcap) continue;
     for (int t = lane; t < L; t += 64) { const int r = a.residues[off + t]; seq[t] = (uint8_t)(r < a.Kp ? r : a.Kp - 1); }
     if constexpr (LONGQ) wave_mem_sync(); else __builtin_amdgcn_wave_barrier();
-    const GLen c = glen_config(L, false);
+    const GLen c = glen_config(Lcfg, false);
     const double fwd = gforward<true>(m, seq, L, c, mx, lane);
     if (!isfinite(fwd)) { if (lane == 0 && a.status) a.status[p] = 1; continue; }
     double bwd = 0.0;

@@ -104,6 +104,8 @@ struct wh_ehmm {
   std::vector<int64_t> h_env_off;           // ... host sources of asynchronous uploads: they outlive the call
   std::vector<float> h_evp;
   DevBuf d_evp, d_dom_pair, d_dom_len, d_env_res, d_env_off, d_dom_q, d_dom_h, d_dom_cols, d_dom_pp;
+  int dom_lenmodel = 0;                     // wh_set_domain_length_model: WH_LENMODEL_ENVELOPE | WH_LENMODEL_SEQUENCE
+  DevBuf d_dom_seqlen;                      // ... under the latter: each domain's sequence length, the alignment's d_cfg_len
   // wh_msa_dev: widths / layout / matmap / PP_cons sums, per-residue cells, RF and PP_cons, the rows, the posterior chunk;
   // wh_msa: the alignment's columns, posteriors and pair lists
   DevBuf d_msa_lay, d_msa_res, d_msa_gc, d_msa_rows, d_msa_pprows, d_msa_ppm, d_msa_cols, d_msa_pp;

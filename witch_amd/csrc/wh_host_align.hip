@@ -16,6 +16,7 @@ struct AlignCall {
   bool want_redo;                // pairs whose Backward sweep leaves float32 range are queued on the device and redone in log space
   int *d_redo_count; int32_t *d_redo_list;
   int launches;                  // of this call so far
+  const int32_t *d_cfg_len;      // per query: the length its pairs' length model is configured for (wh_align_pp_len_dev), or NULL: its own
 };
 
 struct AlignClassPlan {
@@ -95,7 +96,7 @@ static int align_pass(AlignCall &c, const std::vector<int32_t> &order, const std
     a.item_start = (const int32_t *)e->d_items.p + nit + p.first;
     a.item_count = (const int32_t *)e->d_items.p + 2 * nit + p.first;
     a.n_items = p.n_items;
-    a.col_offsets = c.d_col_offsets; a.cols = c.d_cols; a.pp = c.d_pp; a.pp64 = c.d_pp64;
+    a.col_offsets = c.d_col_offsets; a.cols = c.d_cols; a.pp = c.d_pp; a.pp64 = c.d_pp64; a.cfg_len = c.d_cfg_len;
     a.counter = e->counter(kSlotLaunch0 + c.launches);
     a.Lcap = c.Lm; a.SP = p.SP; a.wave_lds = p.wave_lds;
     a.K = e->K; a.Kp = e->Kp; a.Klds = p.Klds; a.swap = p.swap ? 1 : 0;
@@ -187,7 +188,7 @@ static int align_wide(AlignCall &c, const std::map<int, std::vector<int32_t>> &w
     wa.residues = c.d_residues; wa.offsets = c.d_offsets;
     wa.items = (const int32_t *)e->d_order.p + ooff; wa.n_items = (int)kv.second.size();
     ooff += kv.second.size();
-    wa.pair_q = c.d_pair_q; wa.pair_h = c.d_pair_h; wa.col_off = c.d_col_offsets; wa.cols = c.d_cols; wa.pp = c.d_pp; wa.pp64 = c.d_pp64;
+    wa.pair_q = c.d_pair_q; wa.pair_h = c.d_pair_h; wa.col_off = c.d_col_offsets; wa.cols = c.d_cols; wa.pp = c.d_pp; wa.pp64 = c.d_pp64; wa.cfg_len = c.d_cfg_len;
     wa.status = (int32_t *)e->d_recs.p;
     if (wclass >= kWideAlignClasses) { set_error("too many classes of long models"); return WH_ERANGE; }
     wa.counter = e->counter(kSlotWideAlign + wclass++);
@@ -240,7 +241,7 @@ static int align_float64(AlignCall &c, const std::vector<int32_t> &gitems) {
   g.residues = c.d_residues; g.offsets = c.d_offsets;
   HIPCHK(hipMemcpyAsync(e->d_order.p, gitems.data(), sizeof(int32_t) * gitems.size(), hipMemcpyHostToDevice, s));
   g.items = (const int32_t *)e->d_order.p; g.n_items = (int)gitems.size();
-  g.pair_q = c.d_pair_q; g.pair_h = c.d_pair_h; g.col_off = c.d_col_offsets; g.cols = c.d_cols; g.pp = c.d_pp; g.pp64 = c.d_pp64;
+  g.pair_q = c.d_pair_q; g.pair_h = c.d_pair_h; g.col_off = c.d_col_offsets; g.cols = c.d_cols; g.pp = c.d_pp; g.pp64 = c.d_pp64; g.cfg_len = c.d_cfg_len;
   if (e->d_recs.ensure(sizeof(int32_t) * ((size_t)c.npairs + 4))) return WH_ENOMEM;
   HIPCHK(hipMemsetAsync(e->d_recs.p, 0, sizeof(int32_t) * (size_t)c.npairs, s));
   g.status = (int32_t *)e->d_recs.p;
@@ -283,29 +284,37 @@ extern "C" int wh_align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t
 // both PP entry points: <d_pp> floats, or <d_pp64> doubles, or neither
 static int align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
                      int32_t max_len, const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
-                     const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, double *d_pp64, void *stream);
+                     const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, double *d_pp64, const int32_t *d_cfg_len, void *stream);
 
 extern "C" int wh_align_pp_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
                                int32_t max_len, const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
                                const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, void *stream) {
-  return align_dev(e, d_residues, d_offsets, nq, total_residues, max_len, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, d_pp, nullptr, stream);
+  return align_dev(e, d_residues, d_offsets, nq, total_residues, max_len, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, d_pp, nullptr, nullptr, stream);
+}
+
+// wh_align_pp_dev under a length model of the caller's choice: <d_cfg_len>[nq], or NULL for wh_align_pp_dev itself
+extern "C" int wh_align_pp_len_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
+                                   int32_t max_len, const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
+                                   const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, const int32_t *d_cfg_len, void *stream) {
+  return align_dev(e, d_residues, d_offsets, nq, total_residues, max_len, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, d_pp, nullptr, d_cfg_len, stream);
 }
 
 extern "C" int wh_align_pp64_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
                                  int32_t max_len, const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
                                  const int64_t *d_col_offsets, int32_t *d_cols, double *d_pp64, void *stream) {
-  return align_dev(e, d_residues, d_offsets, nq, total_residues, max_len, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, nullptr, d_pp64, stream);
+  return align_dev(e, d_residues, d_offsets, nq, total_residues, max_len, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, nullptr, d_pp64, nullptr, stream);
 }
 
 static int align_dev(wh_ehmm *e, const uint8_t *d_residues, const int64_t *d_offsets, int64_t nq, int64_t total_residues,
                      int32_t max_len, const int64_t *d_pair_q, const int32_t *d_pair_h, int64_t npairs,
-                     const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, double *d_pp64, void *stream) {
+                     const int64_t *d_col_offsets, int32_t *d_cols, float *d_pp, double *d_pp64, const int32_t *d_cfg_len, void *stream) {
   (void)nq; (void)total_residues;
   if (!e || !d_residues || !d_offsets || !d_pair_q || !d_pair_h || !d_col_offsets || !d_cols || npairs < 0 || max_len < 0) {
     set_error("wh_align_dev: bad argument");
     return WH_EINVAL;
   }
   AlignCall c = {e, (hipStream_t)stream, d_residues, d_offsets, d_pair_q, d_pair_h, npairs, d_col_offsets, d_cols, d_pp, d_pp64, max_len, std::max(max_len, 1)};
+  c.d_cfg_len = d_cfg_len;
   hipStream_t s = c.s;
   HIPCHK(hipSetDevice(e->device));
   if (npairs == 0) { e->timers[2].launches = 0; e->timers[2].ms = 0; return WH_OK; }

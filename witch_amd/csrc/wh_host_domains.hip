@@ -29,6 +29,18 @@ int wh_hmm_evparams(const char *hmm_path, float *tau, float *lambda, int32_t *pr
   return WH_OK;
 }
 
+int wh_set_domain_length_model(wh_ehmm *e, int model) {
+  if (model != WH_LENMODEL_ENVELOPE && model != WH_LENMODEL_SEQUENCE) { set_error("wh_set_domain_length_model: unknown length model %d (WH_LENMODEL_ENVELOPE = %d, WH_LENMODEL_SEQUENCE = %d)", model, WH_LENMODEL_ENVELOPE, WH_LENMODEL_SEQUENCE); return WH_EINVAL; }
+  if (!e) { set_error("wh_set_domain_length_model: null handle"); return WH_EINVAL; }
+  e->dom_lenmodel = model;
+  return WH_OK;
+}
+
+int wh_get_domain_length_model(const wh_ehmm *e) {
+  if (!e) { set_error("wh_get_domain_length_model: null handle"); return WH_EINVAL; }
+  return e->dom_lenmodel;
+}
+
 int wh_domain_counts_dev(wh_ehmm *e, const uint8_t *d_flags, const wh_pair_detail *d_detail, int64_t nq,
                          int32_t *d_counts, int32_t *d_n_unlisted, void *stream) {
   if (!e || !d_flags || !d_detail || !d_counts || nq < 0) { set_error("wh_domain_counts_dev: bad argument"); return WH_EINVAL; }
@@ -83,6 +95,8 @@ int domains_run(const char *who, wh_ehmm *e, const uint8_t *d_residues, const in
       e->d_env_off.ensure(sizeof(int64_t) * ((size_t)ndom + 1)) || e->d_dom_q.ensure(sizeof(int64_t) * (size_t)ndom + 8) ||
       e->d_dom_h.ensure(sizeof(int32_t) * (size_t)ndom + 8))
     return WH_ENOMEM;
+  const bool seq_model = e->dom_lenmodel == WH_LENMODEL_SEQUENCE;
+  if (seq_model && e->d_dom_seqlen.ensure(sizeof(int32_t) * (size_t)ndom + 8)) return WH_ENOMEM;
   if (timer_begin(e, 5, s)) return WH_EHIP;
   DomainArgs a;
   memset(&a, 0, sizeof a);
@@ -90,6 +104,7 @@ int domains_run(const char *who, wh_ehmm *e, const uint8_t *d_residues, const in
   a.dom_off = d_dom_off; a.ndom = ndom;
   a.dom_pair = (int64_t *)e->d_dom_pair.p; a.dom_len = (int32_t *)e->d_dom_len.p; a.bad = (int *)e->d_dom_len.p + ndom;
   a.residues = d_residues; a.offsets = d_offsets;
+  a.dom_seqlen = seq_model ? (int32_t *)e->d_dom_seqlen.p : nullptr;
   // every length starts as -1 (a slot the list kernel does not reach is refused like a malformed envelope), the word as 0
   if (ndom > 0) HIPCHK(hipMemsetAsync(a.dom_len, 0xFF, sizeof(int32_t) * (size_t)ndom, s));
   HIPCHK(hipMemsetAsync(a.bad, 0, sizeof(int), s));
@@ -119,9 +134,10 @@ int domains_run(const char *who, wh_ehmm *e, const uint8_t *d_residues, const in
     a.dom_q = (int64_t *)e->d_dom_q.p; a.dom_h = (int32_t *)e->d_dom_h.p;
     err = launch_envelope_gather(a, s);
     if (err != hipSuccess) { set_error("envelope gather kernel launch failed: %s", hipGetErrorString(err)); return WH_EHIP; }
-    // the alignment: "query" d is envelope d, its model the pair's; one pair per envelope, so its columns share the CSR
-    int rc = wh_align_pp_dev(e, a.env_res, a.env_off, ndom, total_env, max_env, a.dom_q, a.dom_h, ndom, a.env_off,
-                             (int32_t *)e->d_dom_cols.p, (float *)e->d_dom_pp.p, s);
+    // the alignment: "query" d is envelope d, its model the pair's; one pair per envelope, so its columns share the CSR.
+    // Its length model is the envelope's own (a null d_cfg_len) or, under WH_LENMODEL_SEQUENCE, the sequence's
+    int rc = wh_align_pp_len_dev(e, a.env_res, a.env_off, ndom, total_env, max_env, a.dom_q, a.dom_h, ndom, a.env_off,
+                                 (int32_t *)e->d_dom_cols.p, (float *)e->d_dom_pp.p, a.dom_seqlen, s);
     if (rc) return rc;
     a.cols = (const int32_t *)e->d_dom_cols.p; a.pp = (const float *)e->d_dom_pp.p; a.evp = (const float *)e->d_evp.p; a.out = d_out;
     err = launch_domain_summary(a, s);

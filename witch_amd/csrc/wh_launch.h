@@ -285,6 +285,7 @@ struct WideAlignArgs {
   // (last: the fields above keep the offsets they have without it)
   float *pp;                   // optional, CSR like <cols>: posterior probability of each residue's state on the path (wh_align_pp), or NULL
   double *pp64;                // ... or the same as doubles (wh_align_pp64); at most one of the two is set
+  const int32_t *cfg_len;      // optional, per query: the length the pair's length model is configured for (wh_align_pp_len); NULL: the query's own
 };
 size_t wide_align_lds_bytes(int Lcap);
 hipError_t launch_align_wide(int Q, const WideAlignArgs &a, int blocks, int waves, size_t lds, hipStream_t s);
@@ -344,6 +345,7 @@ struct GenericAlignArgs {
   float *pp;                   // optional, CSR like <cols>: posterior probability of each residue's state on the path (wh_align_pp), or NULL
   double *pp64;                // ... or the same as doubles (wh_align_pp64); at most one of the two is set
   size_t pp_off;               // with <pp>: where in the wave's slab the unrounded ppM / ppI rows are kept (generic_align_pp_doubles of them)
+  const int32_t *cfg_len;      // optional, per query: the length the pair's length model is configured for (wh_align_pp_len); NULL: the query's own
 };
 // <longq>: the instantiations that read the residues from the wave's slab in HBM, for queries beyond generic_lds_bytes: the
 // copy takes the last generic_seq_doubles(Lcap) doubles of the slab (slab_stride covers them), the LDS block is
@@ -535,7 +537,8 @@ struct DomainArgs {
   int64_t ndom;
   int64_t *dom_pair;           // [ndom] list kernel: the domain's pair ...
   int32_t *dom_len;            // ... and its envelope's length; -1: an envelope outside its query
-  int *bad;                    // ... set when dom_off does not match the records
+  int32_t *dom_seqlen;         // ... and (optional, WH_LENMODEL_SEQUENCE) its sequence's length
+  int *bad;                   // ... set when dom_off does not match the records
   const uint8_t *residues;
   const int64_t *offsets;      // [nq + 1]
   const int64_t *env_off;      // [ndom + 1] CSR of the packed envelopes (and of their columns and posteriors)
@@ -581,6 +584,7 @@ struct AlignArgs {
   int no_window;               // 1: Backward / OA / traceback at full width only (WH_NO_WINDOW)
   int *wstat;                  // NULL or 4 counters: pairs aligned on a 256-node window, window rejected, window not tried, 512-node window
   unsigned long long *wcyc;    // NULL or 4 wave-cycle sums of the window pairs: Forward, Backward + posteriors, OA fill, traceback
+  const int32_t *cfg_len;      // optional, per query: the length the pair's length model is configured for (wh_align_pp_len); NULL: the query's own
 };
 // what the host fills in; the kernels without the PP output take the core alone (the kernel arguments a build without the
 // feature has), the ones with it the whole

@@ -938,6 +938,7 @@ __global__ __launch_bounds__(512) void align_wide_kernel(WideAlignArgs a) {
     const float *fwG = a.tables + hm->wfw_off;
     const int64_t off = a.offsets[qi];
     const int L = (int)(a.offsets[qi + 1] - off);
+    const int Lcfg = a.cfg_len ? max(a.cfg_len[qi], 1) : (L > 0 ? L : 1);     // the length model's length (WideAlignArgs::cfg_len)
     int32_t *cols = a.cols + a.col_off[pair];
     PPOut pp;
     if constexpr (PP) pp = PPOut(a.pp, a.pp64, a.col_off[pair]);
@@ -946,7 +947,7 @@ __global__ __launch_bounds__(512) void align_wide_kernel(WideAlignArgs a) {
     bool active = L > 0 && L <= a.Lcap;
     for (int t = threadIdx.x; active && t < L; t += blockDim.x) { const int r = a.residues[off + t]; seq[t] = (uint8_t)(r < a.Kp ? r : a.Kp - 1); }
     __syncthreads();
-    const LenCfg cu = len_config(L > 0 ? L : 1, false);
+    const LenCfg cu = len_config(Lcfg, false);
     // ---------------- unihit Forward, rows to slab A (spec slots 0..5 = N, B, E, J, C, S)
     float xC_L = 0.f; int ef_L = 0;
     if (active) forward_wide<Q, true, NLT, TR>(c, seq, L, cu, xC_L, ef_L);

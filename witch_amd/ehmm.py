@@ -169,6 +169,23 @@ class EHMM:
         """Development knob on a live handle (include/witch_hip.h: wh_set_option)."""
         check(lib().wh_set_option(self._h, name.encode(), str(value).encode()), "wh_set_option")
 
+    _LENGTH_MODELS = ("envelope", "sequence")      # WH_LENMODEL_ENVELOPE, WH_LENMODEL_SEQUENCE
+
+    def set_domain_length_model(self, model: str):
+        """The length model the domain stage (domains, domain_paths, hits_msa, domain_display) aligns an envelope under:
+        "envelope" (the default) - its own Ld residues, hmmalign's alignment; "sequence" - its whole sequence's L residues,
+        hmmsearch's own alignment (include/witch_hip.h: wh_set_domain_length_model)."""
+        if model not in self._LENGTH_MODELS:
+            raise ValueError("domain length model %r: one of %s" % (model, ", ".join(map(repr, self._LENGTH_MODELS))))
+        check(lib().wh_set_domain_length_model(self._h, self._LENGTH_MODELS.index(model)), "wh_set_domain_length_model")
+
+    @property
+    def domain_length_model(self) -> str:
+        v = lib().wh_get_domain_length_model(self._h)
+        if v < 0:
+            check(v, "wh_get_domain_length_model")
+        return self._LENGTH_MODELS[v]
+
     def last_kernel_ms(self, which: int):
         ms, n = C.c_double(0), C.c_int(0)
         check(lib().wh_last_kernel_ms(self._h, which, C.byref(ms), C.byref(n)), "wh_last_kernel_ms")
@@ -348,10 +365,13 @@ class EHMM:
                             w.ctypes.data, nk.ctypes.data, nu.ctypes.data), "wh_topk")
         return idx, w, nk, nu
 
-    def align(self, residues, offsets, pair_q, pair_h, want_pp=False):
+    def align(self, residues, offsets, pair_q, pair_h, want_pp=False, cfg_len=None):
         """cols (CSR over the residues of each pair) and col_offsets; with want_pp also pp (float32, CSR like cols): the
         posterior probability of each residue's state on the returned path (include/witch_hip.h: wh_align_pp);
-        want_pp="float64": as float64 (wh_align_pp64), which the any-size float64 kernel fills unrounded."""
+        want_pp="float64": as float64 (wh_align_pp64), which the any-size float64 kernel fills unrounded.
+        cfg_len (int32 per query, each >= 1; float32 posteriors or none): the length each query's unihit length model is
+        configured for in place of its own (wh_align_pp_len) - the whole sequence's, for an envelope aligned as hmmsearch
+        aligns it."""
         residues = np.ascontiguousarray(residues, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         pair_q = np.ascontiguousarray(pair_q, dtype=np.int64)
@@ -360,6 +380,18 @@ class EHMM:
         co = np.zeros(len(pair_q) + 1, dtype=np.int64)
         co[1:] = np.cumsum(lens)
         cols = np.full(int(co[-1]), -1, dtype=np.int32)
+        if cfg_len is not None:
+            if want_pp == "float64":
+                raise ValueError("align: cfg_len comes with float32 posteriors (want_pp=True) or none")
+            cfg_len = np.ascontiguousarray(cfg_len, dtype=np.int32)
+            if cfg_len.shape != (len(offsets) - 1,):
+                raise ValueError("align: cfg_len has one entry per query")
+            pp = np.zeros(int(co[-1]), dtype=np.float32) if want_pp else None
+            if len(pair_q):
+                check(lib().wh_align_pp_len(self._h, residues.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
+                                            pair_q.ctypes.data, pair_h.ctypes.data, len(pair_q), co.ctypes.data,
+                                            cols.ctypes.data, pp.ctypes.data if want_pp else None, cfg_len.ctypes.data), "wh_align_pp_len")
+            return (cols, co, pp) if want_pp else (cols, co)
         if not want_pp:
             if len(pair_q):
                 check(lib().wh_align(self._h, residues.ctypes.data, offsets.ctypes.data, len(offsets) - 1,
@@ -835,13 +867,19 @@ class EHMM:
         return idx, w, nk, nu
 
     def align_t(self, residues_t, offsets_t, max_len: int, pair_q_t, pair_h_t, col_offsets_t, total_cols: int,
-                want_pp=False):
-        """cols on the device; with want_pp (cols, pp) - pp float32, CSR like cols (wh_align_pp_dev)."""
+                want_pp=False, cfg_len_t=None, use_len=False):
+        """cols on the device; with want_pp (cols, pp) - pp float32, CSR like cols (wh_align_pp_dev).  cfg_len_t (int32 per
+        query) or use_len: through wh_align_pp_len_dev, with that array or a null one."""
         import torch
         cols = torch.full((int(total_cols),), -1, dtype=torch.int32, device=residues_t.device)
         pp = torch.zeros((int(total_cols),), dtype=torch.float32, device=residues_t.device) if want_pp else None
         npairs = pair_q_t.numel()
-        if npairs and not want_pp:
+        if npairs and (cfg_len_t is not None or use_len):
+            check(lib().wh_align_pp_len_dev(self._h, residues_t.data_ptr(), offsets_t.data_ptr(), offsets_t.numel() - 1,
+                                            residues_t.numel(), int(max_len), pair_q_t.data_ptr(), pair_h_t.data_ptr(),
+                                            npairs, col_offsets_t.data_ptr(), cols.data_ptr(), pp.data_ptr() if want_pp else None,
+                                            cfg_len_t.data_ptr() if cfg_len_t is not None else None, self._stream()), "wh_align_pp_len_dev")
+        elif npairs and not want_pp:
             check(lib().wh_align_dev(self._h, residues_t.data_ptr(), offsets_t.data_ptr(), offsets_t.numel() - 1,
                                      residues_t.numel(), int(max_len), pair_q_t.data_ptr(), pair_h_t.data_ptr(),
                                      npairs, col_offsets_t.data_ptr(), cols.data_ptr(), self._stream()),

@@ -100,6 +100,14 @@ def alidisplay_enabled():
     return os.environ.get("WITCH_HIP_ALIDISPLAY", "") == "1"
 
 
+def domain_seqlen_enabled():
+    """WITCH_HIP_DOMAIN_SEQLEN=1 in the server's environment: the domain stage aligns every envelope under the length model of
+    its whole sequence, as hmmsearch does (EHMM.set_domain_length_model("sequence")): --domtblout, the domain tables, -A and
+    the alignment display then show hmmsearch's own alignment, and the display needs no second alignment launch for its PP
+    line.  An opt-in for now, as the bias filter and the display are.  Unset, every output is what it was."""
+    return os.environ.get("WITCH_HIP_DOMAIN_SEQLEN", "") == "1"
+
+
 def display_textw(opts):
     """The text width of the alignment display: --textw N (HMMER refuses N < 120, so does this), --notextw: None (one
     block), else 120."""
@@ -211,6 +219,8 @@ class GpuBackend:
         self.cache = collections.OrderedDict()
         self.max_models = max_models or int(os.environ.get("WITCH_HIP_MAX_MODELS", "32"))
         self.lock = threading.Lock()
+        self.seqlen = domain_seqlen_enabled()      # read once, like the handles' own environment
+        self.calls = []                            # the EHMM stages of the last search, in call order (tests)
 
     def model(self, path):
         from witch_amd.ehmm import EHMM
@@ -225,6 +235,8 @@ class GpuBackend:
                 _, (_, old, _) = self.cache.popitem(last=False)
                 old.close()
             hit = (mt, EHMM([rp], device=self.device), formats.hmm_header(rp))
+            if self.seqlen:
+                hit[1].set_domain_length_model("sequence")
             self.cache[rp] = hit
         else:
             self.cache.move_to_end(rp)
@@ -313,14 +325,20 @@ class GpuBackend:
         """ONE domain stage (EHMM.domain_paths), then the stages that read its records, columns and posteriors on the device:
         the display, and the hit selection of -A where it is asked for.  The display's PP line takes hmmsearch's own
         posteriors, decoded under the whole sequence's length model (EHMM.sequence_model_posteriors: one more alignment
-        launch over the envelopes that are shorter than their sequence); the domain records and -A keep the stage's.
+        launch over the envelopes that are shorter than their sequence); the domain records and -A keep the stage's.  With
+        WITCH_HIP_DOMAIN_SEQLEN=1 the stage itself aligns under that model: all three read the stage's, one alignment launch.
         Returns (domain records, dom_off, hits or None, display lines)."""
         import torch
         dev = torch.device("cuda", self.device)
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
         nq = len(records)
         recs, dom_off, env_off, cols, pp = e.domain_paths(res, offs, flags, det)
-        pp_seq = e.sequence_model_posteriors(res, offs, recs, env_off, cols, pp, h=0)
+        self.calls = ["domain_paths"]
+        if self.seqlen:                # (the stage's path and posteriors are hmmsearch's already: no padded-envelope pass)
+            pp_seq = pp
+        else:
+            pp_seq = e.sequence_model_posteriors(res, offs, recs, env_off, cols, pp, h=0)
+            self.calls.append("sequence_model_posteriors")
         with torch.cuda.device(dev):
             res_t, offs_t, flags_t = up(res), up(offs), up(np.asarray(flags).reshape(-1))
             dom_t, dom_off_t = up(recs.view(np.uint8).reshape(len(recs), -1)), up(dom_off)
