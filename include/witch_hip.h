@@ -481,6 +481,13 @@ int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches);
  * cells_per_lane = (cells per virtual lane: 12, 16, 24 or 48) x waves) and its HIP-event duration.  Returns the number
  * of launches (the first <cap> are written); bench.py names the measured dominant kernel from it. */
 int wh_last_score_launches(wh_ehmm *e, int32_t *cells_per_lane, int32_t *kind, double *ms, int cap);
+/* The launch shape of the one-wavefront-per-pair scoring launches (models of up to 24 cells per lane) of the last scoring
+ * pass, in launch order, timing mode or not: the cells-per-lane class, the waves per workgroup (16 = four per SIMD, the
+ * 1 024-thread object wh::k7w::score_kernel7; 12 or fewer = wh::k7::score_kernel7 and the other families) and how the
+ * multihit Backward sweep tries its node window: 0 not at all, 1 with three more rows per wave in LDS, 2 in place with the
+ * Forward sweep's rows backed up in HBM (DESIGN.md sections 4.1 and 9.12).  Returns the number of launches (the first <cap>
+ * are written; any of the arrays may be NULL).  Does not wait for the device. */
+int wh_last_score_shapes(wh_ehmm *e, int32_t *cells_per_lane, int32_t *waves, int32_t *p2win, int cap);
 /* When enabled, every kernel launch is bracketed by HIP events (bench/roofline use). */
 int wh_set_timing(wh_ehmm *e, int enabled);
 /* Development knobs (WH_SCORE_KERNEL, WH_KEEP_LOG2, WH_MAX_WAVES, WH_FORCE_SPECG,

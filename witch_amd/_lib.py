@@ -176,6 +176,7 @@ SYMBOLS = {
     "wh_last_long_score_pairs": (C.c_int, [_P, _P]),
     "wh_last_long_align_pairs": (C.c_int, [_P, _P]),
     "wh_last_score_launches": (C.c_int, [_P, _P, _P, _P, C.c_int]),
+    "wh_last_score_shapes": (C.c_int, [_P, _P, _P, _P, C.c_int]),
     "wh_last_kernel_ms": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "wh_set_timing": (C.c_int, [_P, C.c_int]),
     "wh_set_option": (C.c_int, [_P, C.c_char_p, C.c_char_p]),

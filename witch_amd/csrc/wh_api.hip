@@ -339,6 +339,17 @@ int wh_last_score_launches(wh_ehmm *e, int32_t *cells_per_lane, int32_t *kind, d
   return n;
 }
 
+int wh_last_score_shapes(wh_ehmm *e, int32_t *cells_per_lane, int32_t *waves, int32_t *p2win, int cap) {
+  if (!e || cap < 0) { set_error("wh_last_score_shapes: bad argument"); return WH_EINVAL; }
+  const int n = (int)e->last_shapes.size();
+  for (int t = 0; t < n && t < cap; t++) {
+    if (cells_per_lane) cells_per_lane[t] = e->last_shapes[(size_t)t].q;
+    if (waves) waves[t] = e->last_shapes[(size_t)t].waves;
+    if (p2win) p2win[t] = e->last_shapes[(size_t)t].p2win;
+  }
+  return n;
+}
+
 int wh_last_kernel_ms(wh_ehmm *e, int which, double *ms, int *launches) {
   if (!e || which < 0 || which >= wh_ehmm::kTimers) return WH_EINVAL;
   KernelTimer &t = e->timers[which];

@@ -156,6 +156,10 @@ struct wh_ehmm {
   std::vector<hipEvent_t> cls_ev;
   std::vector<int> cls_q, cls_kind;
   int cls_n = 0;
+  // the launches of the one-wave size classes of the last scoring pass, in launch order (timing mode or not): cells per lane,
+  // waves per workgroup, ScoreArgs::p2win - wh_last_score_shapes
+  struct ScoreShape { int q, waves, p2win; };
+  std::vector<ScoreShape> last_shapes;
   int *counter(int slot) const { return (int *)d_counter.p + slot; }      // a slot of the table above
   ResolveFeedback *d_feedback() const { return (ResolveFeedback *)counter(kSlotResolveFeedback); }
 };

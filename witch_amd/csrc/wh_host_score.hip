@@ -42,8 +42,8 @@ static ScoreCall score_call(wh_ehmm *e, const uint8_t *d_residues, const int64_t
 
 // ------------------------------------------------------------------------------------ plans of the one-wave classes
 struct StagedWaves { int wl, one, both, p2, p4; };    // floats per wave block; waves of the dense kernels (one / both orientations) and of the light ones
-enum class ScoreFamily { PhaseCall, PhaseCallB, TwoQuery, FourEnvelope, PassSync, Staged };
-static const char *const kFamilyName[] = {"phase-call", "phase-call(B)", "two-queries-per-wave", "phase-call", "pass-synchronous", "staged"};
+enum class ScoreFamily { PhaseCall, PhaseCallB, TwoQuery, FourEnvelope, PassSync, Staged, PhaseCallW };   // (W: sixteen waves, wh_score7w.o)
+static const char *const kFamilyName[] = {"phase-call", "phase-call(B)", "two-queries-per-wave", "phase-call", "pass-synchronous", "staged", "phase-call(16 waves)"};
 
 struct ScoreClassPlan {
   int Q, list_off, n_list;       // cells per lane; the class's models in d_lists
@@ -117,7 +117,8 @@ static int plan_score_class(const ScoreCall &c, int Q, int list_off, int n_list,
     const int wq = fit_waves(kLdsHeader, table, cap_waves(kn, 12), wlq);
     if (wq >= 8) { quadk = true; b = {wq, row_stride(Lc), wlq, lds_bytes(kLdsHeader, table, wq, wlq)}; }
   }
-  p.family = big ? ScoreFamily::PassSync : pairk ? ScoreFamily::TwoQuery : quadk ? ScoreFamily::FourEnvelope : kn.kernel == 8 ? ScoreFamily::PhaseCallB : ScoreFamily::PhaseCall;
+  p.family = big ? ScoreFamily::PassSync : pairk ? ScoreFamily::TwoQuery : quadk ? ScoreFamily::FourEnvelope : kn.kernel == 8 ? ScoreFamily::PhaseCallB
+             : l.four ? ScoreFamily::PhaseCallW : ScoreFamily::PhaseCall;
   p.p2win = (specg || big || pairk || quadk) ? 0 : p2win ? 1 : p2inpl ? 2 : 0;
   p.use_qorder = big || c.mixed;
   const int waves = b.waves;
@@ -164,7 +165,7 @@ static ScoreArgs class_args(const ScoreCall &c, const ScoreClassPlan &p, int lau
   a.Klds = p.Klds; a.SP = p.b.SP; a.wave_lds = p.b.wave_lds; a.spec_arrays = kScoreSpecArrays;
   // (+ the layout of the block this build expects of the default scoring object, wh_score7.o: row records or arrays.  Its
   // launchers refuse the other one - an object left over from a build with other flags - as they refuse six against eight arrays)
-  if (p.family == ScoreFamily::PhaseCall || p.family == ScoreFamily::FourEnvelope) a.spec_arrays |= kScoreSpecLayout << 8;
+  if (p.family == ScoreFamily::PhaseCall || p.family == ScoreFamily::PhaseCallW || p.family == ScoreFamily::FourEnvelope) a.spec_arrays |= kScoreSpecLayout << 8;
   a.paths = reinterpret_cast<unsigned long long *>(e->counter(kSlotScorePath));
   a.p2win = p.p2win;
   a.qorder = p.use_qorder ? c.d_qorder : nullptr;
@@ -206,11 +207,13 @@ static int launch_score_class(const ScoreCall &c, const ScoreClassPlan &p, int *
   if (e->knobs.trace) fprintf(stderr, "[wh] score Q=%d kernel=%s specg=%d waves=%d blocks=%d lds=%zu SP=%d wave_lds=%d items=%d Lcap=%d\n", Q,
                               kFamilyName[(int)p.family], (int)p.specg, waves, p.blocks, p.b.lds, a.SP, a.wave_lds, a.n_items, a.Lcap);
   HIPCHK(hipMemsetAsync(a.counter, 0, sizeof(int), s));
+  e->last_shapes.push_back({Q, waves, a.p2win});
   if (class_mark(e, s, Q, big ? 1 : 0)) return WH_EHIP;
   hipError_t err = big ? launch_score_big(Q, a, p.blocks, threads, p.b.lds, s)
                    : p.family == ScoreFamily::TwoQuery ? launch_score9(Q, a, p.blocks, threads, p.b.lds, s)
                    : p.family == ScoreFamily::FourEnvelope ? launch_score7q(Q, a, p.blocks, threads, p.b.lds, s)
                    : p.family == ScoreFamily::PhaseCallB ? launch_score7b(Q, a, p.blocks, threads, p.b.lds, s)
+                   : p.family == ScoreFamily::PhaseCallW ? launch_score7w(Q, a, p.blocks, threads, p.b.lds, s)
                                                          : launch_score7(Q, a, p.blocks, threads, p.b.lds, s);
   if (err != hipSuccess) { set_error("score kernel launch (Q=%d) failed: %s", Q, hipGetErrorString(err)); return WH_EHIP; }
   (*launches)++;
@@ -536,6 +539,7 @@ static int score_dev_pass(ScoreCall &c, bool *overflow) {
   HIPCHK(hipSetDevice(e->device));
   if (timer_begin(e, 0, s)) return WH_EHIP;
   e->cls_n = 0;
+  e->last_shapes.clear();
   e->last_staged_batches = 0;
   int launches = 0;
   bool wide_done = false;

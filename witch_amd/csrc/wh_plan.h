@@ -55,14 +55,26 @@ inline int cap_waves(int max_waves, int w) { return max_waves > 0 ? std::max(1, 
 inline size_t score_table_bytes(int K, int Q) { return (size_t)(K + 2 * FW_NARR) * Q * kWave * sizeof(float); }   // K emission rows + both transition orientations
 
 // LDS plan of the phase-call scoring kernel: tables + per wave one block (special-state arrays, null2 table, region
-// list, residues), up to twelve waves.  <b> is left alone when not even one wave fits.
-inline bool plan_block1(int max_waves, int K, int Q, int Lcap, int extra_arrays, LdsPlan *b) {
+// list, residues), up to <top> waves (twelve; sixteen for the four-waves-per-SIMD launch below).  <b> is left alone when not
+// even one wave fits.
+inline bool plan_block1(int max_waves, int K, int Q, int Lcap, int extra_arrays, LdsPlan *b, int top = 12) {
   const int sp = row_stride(Lcap);
   const int wl = (kScoreSpecArrays + extra_arrays) * sp + 32 + kRegsInts + residue_words(Lcap);
-  const int w = fit_waves(kLdsHeader, score_table_bytes(K, Q), cap_waves(max_waves, 12), wl);
+  const int w = fit_waves(kLdsHeader, score_table_bytes(K, Q), cap_waves(max_waves, top), wl);
   if (w < 1) return false;
   *b = {w, sp, wl, lds_bytes(kLdsHeader, score_table_bytes(K, Q), w, wl)};
   return true;
+}
+
+// Four waves per SIMD (wh_score7w.o: workgroups of 1 024 threads at 128 vector registers): the classes
+// that take sixteen waves where sixteen six-array blocks fit beside their tables.  Bit Q / 4 of kFourWaveClasses: the classes
+// that take it by default, each only where its own A/B run on the headline's shape showed a gain; WH_MAX_WAVES=16 asks for it
+// in every class the object serves (8, 12 and 16 cells per lane), any other cap (WH_MAX_WAVES=12: the launch as it was) for none.
+// Never thirteen to fifteen waves: they pay the 128-register budget for less than a full fourth wave.
+constexpr int kFourWaveClasses = 1 << 4;      // the 16-cell class (the headline); the 8- and 12-cell classes have no such run yet
+inline bool four_wave_class(int max_waves, int Q) {
+  if (Q != 8 && Q != 12 && Q != 16) return false;
+  return max_waves == 16 || (max_waves == 0 && ((kFourWaveClasses >> (Q / 4)) & 1));
 }
 
 // The kernel family and the LDS block of one scoring size class (Q cells per lane, K canonical residues) at the length cap
@@ -74,7 +86,7 @@ inline bool plan_block1(int max_waves, int K, int Q, int Lcap, int extra_arrays,
 //    not one wave fits beside their tables
 // and the two-queries-per-wave kernel takes the classes it fits when asked for (pairk; <with9> false: not considered).
 // false: a query of Lc residues does not fit the class.
-struct ScoreLds { LdsPlan b; bool big, specg, pairk, p2win, p2inpl; int Klds; };
+struct ScoreLds { LdsPlan b; bool big, specg, pairk, p2win, p2inpl; int Klds; bool four; };   // <four>: sixteen waves, the 1 024-thread object
 inline bool plan_score_lds(const PlanKnobs &kn, int K, int Q, int Lc, bool with9, ScoreLds *out) {
   const size_t table = score_table_bytes(K, Q);
   ScoreLds r = {};
@@ -95,6 +107,13 @@ inline bool plan_score_lds(const PlanKnobs &kn, int K, int Q, int Lc, bool with9
       LdsPlan b2 = {};
       if (plan_block1(kn.max_waves, K, Q, Lc, 3, &b2) && (b2.waves >= b.waves || (kn.p2win_force && b2.waves >= 8))) { r.p2win = true; b = b2; }
       else if (Q >= 20 && kn.kernel != 9) r.p2inpl = true;      // round 5: the window sweep in place, P1's rows backed up in HBM (ScoreArgs::p2win == 2)
+    }
+    // ... and sixteen waves, four per SIMD, where sixteen six-array blocks fit (short queries on DNA models of up to 16 cells
+    // per lane): the default kernel's own launch only, and the window sweep in place - the three more rows would leave room for
+    // thirteen blocks at most.  A length at which the sixteen do not fit keeps the plan above unchanged.
+    if (ok && b.waves >= 4 && !kn.force_specg && !kn.no_window && !kn.no_p2win && kn.kernel == 7 && four_wave_class(kn.max_waves, Q)) {
+      LdsPlan b4 = {};
+      if (plan_block1(kn.max_waves, K, Q, Lc, 0, &b4, 16) && b4.waves == 16) { r.four = true; r.p2win = false; r.p2inpl = true; b = b4; }
     }
     if (!ok || b.waves < 4 || kn.force_specg) {
       r.specg = true;

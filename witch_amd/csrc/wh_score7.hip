@@ -122,6 +122,15 @@ constexpr bool kAheadCode = ((WH_ROW_AHEAD) & 1) != 0, kAheadPiece = ((WH_ROW_AH
 static_assert(kLayout == SPEC_SOA || kSlim, "a row record has six words (WH_SLIM_SPEC)");
 template <bool SG> using SpecOf = SpecAt<SG ? (int)SPEC_SOA : kLayout>;
 constexpr int kSpecTag = kSpArr | (kLayout << 8);      // what ScoreArgs::spec_arrays must say for this object
+// WH_K7W (the four-waves-per-SIMD object, wh_score7w.o): the file compiled once more with the default object's switches for ONE
+// launch shape - 1 024 threads, 128 vector registers, rows in LDS, 8 / 12 / 16 cells per lane.  Sixteen wave blocks fit beside the
+// tables only without the three rows of the windowed multihit Backward sweep, so this object runs that window in place
+// (ScoreArgs::p2win == 2), which the other objects compile for the 20- and 24-cell classes alone.
+#ifdef WH_K7W
+constexpr int kInPlaceMinQ = 8;
+#else
+constexpr int kInPlaceMinQ = 20;
+#endif
 
 // log() / exp() in double, out of line: inlined, each call site left its polynomial's constants in registers that the kernel then
 // kept alive across every sweep of a pair (the same instructions either way)
@@ -1623,8 +1632,8 @@ __global__ __launch_bounds__(TH) void score_kernel7(ScoreArgs a) {
         if (f1.xC > 0.f && isfinite(fwdsc)) {
           WH_TICK7(4);
           RegOut ro;
-          if constexpr (!SG && Q >= 20) {
-            // (20- / 24-cell models: no LDS for three more rows - the window sweep in place, P1's rows backed up in HBM)
+          if constexpr (!SG && Q >= kInPlaceMinQ) {
+            // (20- / 24-cell models, and every class of the sixteen-wave object: no LDS for three more rows - the window sweep in place, P1's rows backed up in HBM)
             if (a.p2win == 2) ro = score_regions<Q, TH, false, true>(a, c, seq, regs, L, lane, cm, f1, fs, t_last, (glb_f *)(a.p2_backup + ((size_t)blockIdx.x * nwaves + wave) * a.p2_backup_stride));
             else ro = score_regions<Q, TH, SG, false>(a, c, seq, regs, L, lane, cm, f1, fs, t_last);
           } else ro = score_regions<Q, TH, SG, false>(a, c, seq, regs, L, lane, cm, f1, fs, t_last);
@@ -1981,7 +1990,7 @@ static hipError_t launch7_q(int Q, const ScoreArgs &a, int blocks, int threads, 
 #endif  // WH_SWEEPS_ONLY
 }  // namespace WH_K7NS
 
-#if !defined(WH_SWEEPS_ONLY) && !defined(WH_K7B)
+#if !defined(WH_SWEEPS_ONLY) && !defined(WH_K7B) && !defined(WH_K7W)
 // four envelopes per Backward sweep (score_kernel7q): models of 16 cells per lane
 hipError_t launch_score7q(int Q, const ScoreArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
   using namespace WH_K7NS;
@@ -1990,7 +1999,19 @@ hipError_t launch_score7q(int Q, const ScoreArgs &a, int blocks, int threads, si
   return hipErrorInvalidValue;
 }
 #endif
-#ifndef WH_SWEEPS_ONLY
+#ifdef WH_K7W
+// sixteen waves per workgroup, four per SIMD: exactly 1 024 threads, rows in LDS, the classes whose sixteen blocks can fit
+hipError_t WH_K7LAUNCH(int Q, const ScoreArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
+  using namespace WH_K7NS;
+  if (a.spec_scratch || a.spec_arrays != kSpecTag || threads != 1024) return hipErrorInvalidValue;
+  switch (Q) {
+    case 8:  return launch7sg<8, 1024, false>(a, blocks, threads, lds, s);
+    case 12: return launch7sg<12, 1024, false>(a, blocks, threads, lds, s);
+    case 16: return launch7sg<16, 1024, false>(a, blocks, threads, lds, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+#elif !defined(WH_SWEEPS_ONLY)
 hipError_t WH_K7LAUNCH(int Q, const ScoreArgs &a, int blocks, int threads, size_t lds, hipStream_t s) {
   using namespace WH_K7NS;
   if (!a.spec_scratch && a.spec_arrays != kSpecTag) return hipErrorInvalidValue;   // planner and kernel disagree about the LDS block: arrays, or their layout

@@ -200,6 +200,14 @@ class EHMM:
         check(min(n, 0), "wh_last_score_launches")
         return [(int(q[t]), int(kind[t]), float(ms[t])) for t in range(min(n, 64))]
 
+    def last_score_shapes(self):
+        """[(cells per lane, waves per workgroup, multihit window mode 0 / 1 / 2)] of the one-wave scoring launches of the
+        last scoring pass, timing mode or not (include/witch_hip.h: wh_last_score_shapes)."""
+        q, waves, p2win = (np.zeros(64, dtype=np.int32) for _ in range(3))
+        n = lib().wh_last_score_shapes(self._h, q.ctypes.data, waves.ctypes.data, p2win.ctypes.data, 64)
+        check(min(n, 0), "wh_last_score_shapes")
+        return [(int(q[t]), int(waves[t]), int(p2win[t])) for t in range(min(n, 64))]
+
     # ------------------------------------------------------------------ host (numpy) operators
     def last_score_paths(self):
         """Backward sweeps of the last score call by path: envelope sweeps {"window256", "window512", "window_rejected",
